@@ -11,7 +11,10 @@ backward (+ bucketed RCCL all-reduce when N > 1), conditional grad-norm clip, fu
 reference's per-step torch.distributed.barrier() (pipeline/train_val_utils.py:286-287; --no-step-barrier leaves it out).
 Workload = BASELINE.json configs[1]: SROIE line-level, resnet_34_fpn_pretrained + bert-base-uncased (12 layers,
 vocab 30522, random init: no network for checkpoints), 512x512, seq_len 512, 128 segments, batch 8 per GPU.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and reports them; --full then runs every other
+leg (roofline event timing, PCIe-inclusive, stock loop, amp / fp32-MFMA / strict forms, the ranks' parameter check, CPU baseline).
+--dump-outputs DIR writes the last timed step's loss and a seeded sample of the parameters and gradients it left as DIR/*.npy;
+that step then starts from the seeded initial training state, so its outputs are the same every run.
 """
 import argparse
 import json
@@ -233,6 +236,60 @@ def stock_loop_leg(make_net, batch, dev, world, steps, warm, amp=False, resident
     return dt, last
 
 
+def dump_outputs(d, net, loss, n_sample=1 << 22, seed=0):
+    """What a caller of the timed step holds after its last step: the loss that step returned (loss.npy, float64) and the parameters
+    the optimizers left and the gradients they stepped with, over net.named_parameters() flattened in order -- the same seeded sample
+    of n_sample positions of each (params.npy, grads.npy, float32: 32 MB; the whole model is ~540 MB), so two builds compare entry
+    for entry.  A parameter without a gradient (unused in the step) contributes zeros to grads.npy.  With --dump-outputs that last
+    step starts from the seeded initial training state (snapshot_state / restore_state), so what it computes is the same every run
+    up to the rounding order of float atomics."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    ps = [p for _, p in net.named_parameters()]
+    n = sum(p.numel() for p in ps)
+    idx = np.unique(np.random.default_rng(seed).integers(0, n, size=min(n_sample, n)))
+    idx_dev = torch.from_numpy(idx).to(ps[0].device)
+    with torch.no_grad():
+        flat = torch.cat([p.detach().reshape(-1) for p in ps])
+        np.save(os.path.join(d, "params.npy"), flat[idx_dev].float().cpu().numpy())
+        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps])
+        np.save(os.path.join(d, "grads.npy"), flat[idx_dev].float().cpu().numpy())
+    del flat
+    np.save(os.path.join(d, "loss.npy"), np.array([loss], dtype=np.float64))
+
+
+def snapshot_state(net, opts):
+    """Everything a training step reads besides the batch and leaves for the next one: parameters, buffers (BatchNorm running
+    statistics), the optimizers' moments and step counts, the encoder's dropout step counter, python's `random` (the OHEM subsets) and
+    torch's generators.  Float atomics make every step differ from run to run in the last bits, and training amplifies that from step
+    to step (OHEM top-k selections, AdamW on near-zero gradients: ~2 % in the loss after 5 steps), so a step computes the same outputs
+    every run only from a state restored like this."""
+    with torch.no_grad():
+        return {"tensors": {k: t.detach().clone() for k, t in list(net.named_parameters()) + list(net.named_buffers())},
+                "opts": [({k: getattr(o, k).clone() for k in ("mom", "m", "v") if hasattr(o, k)}, o.steps, o.grad_scale) for o in opts],
+                "step_seeds": [(m, m._step_seed) for m in net.modules() if hasattr(m, "_step_seed")],
+                "random": random.getstate(), "torch_rng": torch.get_rng_state(), "cuda_rng": torch.cuda.get_rng_state_all()}
+
+
+def restore_state(net, opts, st):
+    from vbg import ops
+    with torch.no_grad():
+        for k, t in list(net.named_parameters()) + list(net.named_buffers()):
+            if k in st["tensors"]:          # (a buffer first registered by a forward after the snapshot keeps its value)
+                assert t.shape == st["tensors"][k].shape, k
+                t.detach().copy_(st["tensors"][k])
+        for o, (moments, steps, grad_scale) in zip(opts, st["opts"]):
+            for k, v in moments.items():
+                getattr(o, k).copy_(v)
+            o.steps, o.grad_scale = steps, grad_scale
+    for m, v in st["step_seeds"]:
+        m._step_seed = v
+    random.setstate(st["random"])
+    torch.set_rng_state(st["torch_rng"])
+    torch.cuda.set_rng_state_all(st["cuda_rng"])
+    ops.bump_weight_epoch()          # cached plane images of the weights are stale (vbg/optim.py: invalidate)
+
+
 def _free_port():
     import socket
     sk = socket.socket()
@@ -286,7 +343,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0, help="documents per GPU (default: the configuration's own: 8, cfg5: 16)")
     ap.add_argument("--no-step-barrier", action="store_true", help="N > 1: leave out the reference loop's per-step torch.distributed.barrier()")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default: all cores AND 16, both reported)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline of a --full run (default: all cores AND 16, both reported)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-syncbn", action="store_true")
     ap.add_argument("--no-single-stream-pass", action="store_true",
@@ -303,8 +360,8 @@ def main():
     ap.add_argument("--dist-timeout", type=int, default=int(os.environ.get("VBG_DIST_TIMEOUT", "240")),
                     help="N > 1: process-group timeout in seconds; a stalled step also prints which bucket / SyncBatchNorm collective every rank is at")
     ap.add_argument("--amp", action="store_true", help="time the `amp: True` path (one reduced-precision product per product) as the headline value instead "
-                    "of fp32; the default run reports it beside the fp32 value under \"amp\"")
-    ap.add_argument("--no-amp-leg", action="store_true", help="skip the secondary amp / fp32-MFMA measurements of the default run")
+                    "of fp32; a --full run reports it beside the fp32 value under \"amp\"")
+    ap.add_argument("--no-amp-leg", action="store_true", help="skip the secondary amp / fp32-MFMA measurements of a --full run")
     ap.add_argument("--fp32-mfma", action="store_true", help="time the step with every product on the fp32 matrix pipe "
                     "(vbg.ops.set_precision('fp32')) as the headline instead of the fp32-grade split form")
     ap.add_argument("--shape", default="cfg2", choices=["cfg2", "cfg3", "cfg4", "cfg5"],
@@ -312,17 +369,25 @@ def main():
                          "runs (FUNSD 4 classes own-layout resnet / char-level S=T=512, 12 classes, vocab 21128 / 1024x1024 images with "
                          "roberta-base dimensions at 16 documents per GPU), reported under config.workload")
     ap.add_argument("--h2d", action="store_true", help="make the headline the PCIe-inclusive step (packed pinned H2D transfer of the batch "
-                    "inside every step: SURVEY.md §8d's step body); the default run reports that rate beside the HBM-resident headline")
+                    "inside every step: SURVEY.md §8d's step body); a --full run reports that rate beside the HBM-resident headline")
     ap.add_argument("--sync-loss", action="store_true", help="read the loss with a blocking .item() between forward and backward")
-    ap.add_argument("--no-h2d-leg", action="store_true", help="skip the PCIe-inclusive leg of the default run")
+    ap.add_argument("--no-h2d-leg", action="store_true", help="skip the PCIe-inclusive leg of a --full run")
     ap.add_argument("--no-stock-leg", action="store_true", help="skip the `stock_loop` leg (the reference's loop verbatim: torch.optim, .item(), "
-                    "per-tensor pageable H2D, GradScaler under amp) of the default run")
+                    "per-tensor pageable H2D, GradScaler under amp) of a --full run")
     ap.add_argument("--stock", action="store_true", help="N > 1: run the stock_loop leg as well (DistributedDataParallel + SyncBatchNorm around the "
                     "drop-in model; by default only N = 1 runs it)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run everything else the bench measures or checks: the roofline "
+                    "legs, the PCIe-inclusive, stock_loop, amp / fp32-MFMA / strict legs, the ranks' parameter check and the CPU baseline (the "
+                    "--no-* switches above leave parts of it out); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed (loss, a fixed seeded sample of the updated parameters "
+                         "and of their gradients) as DIR/<name>.npy; that step starts from the seeded initial training state (see snapshot_state)")
     ap.add_argument("--cpu-baseline-only", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-shape", default="cfg2", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.cpu_baseline_only:          # child process of the default run: the CPU oracle at that many threads, one JSON line
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_baseline_only:          # child process of a --full run: the CPU oracle at that many threads, one JSON line
         print(json.dumps(cpu_baseline(args.cpu_baseline_only, args.cpu_baseline_shape)), flush=True)
         return
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -489,6 +554,7 @@ def main():
         if rank == 0:
             print(f"[bench] communicator probe passed: 3 steps, {int(vbg_functions.SyncCtx.seq)} SyncBatchNorm collectives on '{reducer.sync_bn_mode}'", file=sys.stderr, flush=True)
         os._exit(0)                     # (no teardown of two communicators in a probe)
+    state0 = snapshot_state(net, opts) if args.dump_outputs else None
     for _ in range(args.warmup):
         last = step()
 
@@ -496,17 +562,29 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    off_clock = 0.0
+    for i in range(args.steps):
+        if state0 is not None and i == args.steps - 1:
+            # --dump-outputs: the last timed step starts from the seeded initial state, so that what it computes (and dump_outputs writes)
+            # is the same every run; the restore is off the clock
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            restore_state(net, opts, state0)
+            torch.cuda.synchronize()
+            off_clock += time.perf_counter() - t1
         last = step()
-    t_enq = time.perf_counter() - t0          # the host has enqueued every timed step (what it could not run ahead of, it waited for inside)
+    t_enq = time.perf_counter() - t0 - off_clock          # the host has enqueued every timed step (what it could not run ahead of, it waited for inside)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - off_clock
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:          # (the ranks hold the same parameters after every step)
+        dump_outputs(args.dump_outputs, net, last)
+
     def timed_leg(n_warm=2):
         for _ in range(n_warm):
             step()
@@ -527,22 +605,23 @@ def main():
         return d, lv
 
     # roofline leg: the same steps again with the dense NT GEMM launches timed one by one (start / stop events in the dispatch packets:
-    # vbg_*_timed) -- in a leg of its own, so that the headline region above carries no instrumentation
-    prof = ops.GemmProfiler(OP_DENSE_K, OP_DENSE_K, False)       # the dense NT GEMM (BERT linears, 1x1 convs): dominant kernel
-    ops.set_gemm_profiler(prof)
-    c3rec = []
-    ops.set_conv3_profiler(c3rec)                                # the second family by time: the row-reuse 3x3 convolutions (fwd + dgrad)
-    timed_leg(0)
-    ops.set_gemm_profiler(None)
-    ops.set_conv3_profiler(None)
-    launches, flops, ms, mfma_flops = prof.summary()
-    c3_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in c3rec)
-    c3_fl, c3_exec = sum(r[0] for r in c3rec), sum(r[0] * r[1] for r in c3rec)
+    # vbg_*_timed) -- in a leg of its own, so that the headline region above carries no instrumentation (--full only, like every leg below)
+    if args.full:
+        prof = ops.GemmProfiler(OP_DENSE_K, OP_DENSE_K, False)       # the dense NT GEMM (BERT linears, 1x1 convs): dominant kernel
+        ops.set_gemm_profiler(prof)
+        c3rec = []
+        ops.set_conv3_profiler(c3rec)                                # the second family by time: the row-reuse 3x3 convolutions (fwd + dgrad)
+        timed_leg(0)
+        ops.set_gemm_profiler(None)
+        ops.set_conv3_profiler(None)
+        launches, flops, ms, mfma_flops = prof.summary()
+        c3_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in c3rec)
+        c3_fl, c3_exec = sum(r[0] for r in c3rec), sum(r[0] * r[1] for r in c3rec)
     # In the step as it runs the encoder's launches share the chip with the CNN's first stage (second stream, VBG_OVERLAP): the step is
     # shorter, every overlapped launch longer -- the figures above are those of the launches AS RUN (what a kernel trace of this command
     # shows).  One more pass on ONE stream gives the same launches alone on the chip: `roofline*.single_stream`.
     single = None
-    if ops.overlap_enabled() and world == 1 and not args.no_single_stream_pass:
+    if args.full and ops.overlap_enabled() and world == 1 and not args.no_single_stream_pass:
         ops.set_overlap(False)
         prof1, c3rec1 = ops.GemmProfiler(OP_DENSE_K, OP_DENSE_K, False), []
         ops.set_gemm_profiler(prof1)
@@ -556,14 +635,14 @@ def main():
         single = {"nt": (l1, ms1, mf1), "c3": (len(c3rec1), c3_ms1, sum(r[0] * r[1] for r in c3rec1))}
 
     h2d_leg = None
-    if not args.h2d and not args.no_h2d_leg:      # the same steps with the batch uploaded inside every step (SURVEY §8d step body)
+    if args.full and not args.h2d and not args.no_h2d_leg:      # the same steps with the batch uploaded inside every step (SURVEY §8d step body)
         use_h2d[0] = True
         hdt, _ = timed_leg()
         use_h2d[0] = False
         h2d_leg = {"value": round(B * world * args.steps / hdt, 3), "unit": "docs/sec", "ms_per_step": round(1e3 * hdt / args.steps, 3),
                    "bytes_per_step": packed_src.nbytes(), "how": "one pinned packed buffer, one asynchronous H2D copy per step (vbg/batch.py)"}
     stock_leg = None
-    if not args.no_stock_leg and (world == 1 or args.stock) and not args.fp32_mfma:
+    if args.full and not args.no_stock_leg and (world == 1 or args.stock) and not args.fp32_mfma:
         def make_net():
             with contextlib.redirect_stdout(sys.stderr):
                 torch.manual_seed(42)
@@ -580,7 +659,7 @@ def main():
                             ".to(device), autocast(enabled=amp), train_loss.item(), optimizer.zero_grad() x2 (set_to_none), backward, "
                             "`train_loss > 10` on the device tensor, torch.optim.SGD + torch.optim.AdamW (GradScaler when amp); nothing from vbg.optim / vbg.batch"}
     amp_leg = None
-    if not args.amp and not args.no_amp_leg:      # the same steps with `amp: True` (reported beside the fp32 headline, never as it)
+    if args.full and not args.amp and not args.no_amp_leg:      # the same steps with `amp: True` (reported beside the fp32 headline, never as it)
         amp_on[0] = True
         for _ in range(2):
             step()
@@ -636,7 +715,7 @@ def main():
                    "dtype": "one reduced-precision MFMA product per product (fp16 hi pieces on the plane / row-reuse kernels, bf16 on the generic ones), "
                             "f32 accumulate / storage / everything else", "last_loss": round(float(amp_last), 4)}
     ranks_in_sync = None
-    if world > 1:          # self-check of the gradient exchange: every rank must hold bit-identical parameters after the timed steps
+    if args.full and world > 1:          # self-check of the gradient exchange: every rank must hold bit-identical parameters after the timed steps
         chk = torch.stack([o.group.pflat.double().sum() for o in opts] + [o.group.pflat.double().abs().sum() for o in opts])
         lo, hi = chk.clone(), chk.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -672,15 +751,10 @@ def main():
                 if fam in d:
                     return float(d[fam]["avg_us"]), f"profiles/{rnd}_trace_avg.json"
         return None, None
-    traffic, traffic_src = pmc_traffic("gemm_hbm_traffic")
-    traffic_c3, traffic_c3_src = pmc_traffic("conv3_hbm_traffic")
 
     if rank == 0:
         docs = B * world * args.steps
         value = docs / dt
-        ach = (flops / (ms * 1e-3)) / 1e12 if ms > 0 else 0.0
-        mfma_rate = (mfma_flops / (ms * 1e-3)) / 1e12 if ms > 0 else 0.0       # what the matrix pipe executes: piece products included
-        mfma_peak = PEAK_F32_TF if args.fp32_mfma else PEAK_BF16_TF
         f_step = {"cfg2": F_STEP_GF, "cfg3": 689.7, "cfg4": 862.4, "cfg5": 1715.3}[args.shape]
         out = {
             "metric": "training docs/sec, 512x512 img + seq_len 512, bert-base+resnet34; 1/2/4/8 GPU",
@@ -715,61 +789,67 @@ def main():
             # device still had queued at that moment (a few ms: the device paces and the host runs ahead; ~0: the host does)
             "host": {"enqueue_ms_per_step": round(1e3 * t_enq / args.steps, 3), "device_tail_ms": round(1e3 * (dt - t_enq), 3)},
         }
-        # Roofline objects (the step is bound by the matrix cores).  Definition, the same for both: `achieved` = ALGORITHMIC
-        # (fp32-equivalent, 2 M N K per product; only real pixels on the 7x7 region maps) TFLOP/s over the launches' own time -- event pairs
-        # in the dispatch packets / on the launch stream, in a leg of its own --; `peak` = the dense bf16 / fp16 MFMA peak divided by the
-        # piece products the arithmetic form issues per product (3: two fp16 pieces, 6: three bf16 pieces; the launch-weighted mean when a
-        # family mixes them); `frac` = achieved / peak = executed matrix-core flops / the dense peak (`mfma_executed` / `mfma_peak`).
-        pp_nt = mfma_flops / max(flops, 1.0)
-        nt = {"bound": "mfma",
-              "kernel": ("vbg::plane_gemm_kernel<*,*,*,*,*,false,*,2> + vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,1> (one-product NT GEMM, amp: fp16 hi planes / bf16; every ungrouped launch)" if args.amp else
-                         "vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,0> (fp32 MFMA NT GEMM; every ungrouped launch)" if args.fp32_mfma else
-                         "vbg::plane_gemm_kernel<*,*,*,*,*,false,*,0|1> + vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,3> (fp32-grade NT GEMM: the BERT linears from pre-split planes, 1x1 convs / heads with the in-kernel split; every ungrouped launch)"),
-              "achieved": round(ach, 2), "peak": round(mfma_peak / max(pp_nt, 1.0), 1), "unit": "TFLOP/s", "frac": round(mfma_rate / mfma_peak, 4),
-              "mfma_executed": round(mfma_rate, 1), "mfma_peak": round(mfma_peak, 1), "piece_products_per_product": round(pp_nt, 3),
-              "traffic": traffic, "traffic_source": traffic_src, "launches": launches, "avg_us": round(1e3 * ms / max(launches, 1), 2),
-              "ms_per_step": round(ms / args.steps, 3), "vs_fp32_mfma_peak": round(ach / PEAK_F32_TF, 4)}
-        tavg, tsrc = trace_avg("nt")
-        if tavg and launches and not (args.amp or args.fp32_mfma):
-            # `frac` with the committed kernel trace's average launch duration in place of this run's event pairs
-            nt["frac_trace"] = round(mfma_flops / launches / (tavg * 1e-6) / 1e12 / mfma_peak, 4)
-            nt["frac_trace_source"] = f"{tsrc}: {tavg:.2f} us per launch in the rocprofv3 kernel trace of this command (another run, same box class)"
-        if getattr(prof, "ingest", None) and prof.ingest[0] and prof.ingest[2] > 0:
-            # what the plane products of the family are bound by: bytes their workgroups move from L2 into LDS -- tiles x k-tiles
-            # x stage bytes, every operand panel once per tile that uses it -- over the same launch times
-            nt["l2_to_lds"] = {"launches": prof.ingest[0], "MB_per_launch": round(prof.ingest[1] / prof.ingest[0] / 1e6, 1),
-                               "TB_per_s": round(prof.ingest[1] / (prof.ingest[2] * 1e-3) / 1e12, 2), "ms_per_step": round(prof.ingest[2] / args.steps, 3)}
-        if c3rec and c3_ms > 0:
-            # the dominant kernel family by time since round 3: the row-reuse 3x3 convolutions, forward + input gradient
-            pp_c3 = c3_exec / max(c3_fl, 1.0)
-            c3 = {"bound": "mfma", "kernel": "vbg::conv3x3_kernel<*,*,*> (3x3 / stride-1 convolutions, forward + input gradient, csrc/conv3.hip)",
-                               "achieved": round(c3_fl / c3_ms / 1e9, 2), "peak": round(mfma_peak / max(pp_c3, 1.0), 1), "unit": "TFLOP/s",
-                               "frac": round(c3_exec / c3_ms / 1e9 / mfma_peak, 4), "mfma_executed": round(c3_exec / c3_ms / 1e9, 1), "mfma_peak": round(mfma_peak, 1),
-                               "piece_products_per_product": round(pp_c3, 3), "traffic": traffic_c3, "traffic_source": traffic_c3_src,
-                               "launches": len(c3rec), "avg_us": round(1e3 * c3_ms / len(c3rec), 2), "ms_per_step": round(c3_ms / args.steps, 3),
-                               "vs_fp32_mfma_peak": round(c3_fl / c3_ms / 1e9 / PEAK_F32_TF, 4)}
-            tavg, tsrc = trace_avg("conv3")
-            if tavg and not (args.amp or args.fp32_mfma):
-                c3["frac_trace"] = round(c3_exec / len(c3rec) / (tavg * 1e-6) / 1e12 / mfma_peak, 4)
-                c3["frac_trace_source"] = f"{tsrc}: {tavg:.2f} us per launch in the rocprofv3 kernel trace of this command (another run, same box class)"
-            if single is not None and single["c3"][1] > 0 and single["nt"][1] > 0:
-                how = "the same launches in a pass with everything on ONE stream (VBG_OVERLAP=0): alone on the chip"
-                n1, m1, x1 = single["nt"]
-                nt["single_stream"] = {"frac": round(x1 / m1 / 1e9 / mfma_peak, 4), "avg_us": round(1e3 * m1 / max(n1, 1), 2),
-                                       "ms_per_step": round(m1 / (args.steps + 1), 3), "how": how}          # (the pass runs one warm-up step)
-                n1, m1, x1 = single["c3"]
-                c3["single_stream"] = {"frac": round(x1 / m1 / 1e9 / mfma_peak, 4), "avg_us": round(1e3 * m1 / max(n1, 1), 2),
-                                       "ms_per_step": round(m1 / (args.steps + 1), 3), "how": how}
-                nt["as_run"] = c3["as_run"] = ("`frac` / `avg_us` are the launches as they run in the step: the encoder on a second stream beside the "
-                                               "CNN's first stage -- a shorter step made of longer launches; `single_stream` is the kernel alone")
-            # `roofline` = the family that takes more of the step (ms_per_step); the other one rides beside it under its own name
-            if c3["ms_per_step"] >= nt["ms_per_step"]:
-                out["roofline"], out["roofline_nt"] = c3, nt
+        if args.full:
+            traffic, traffic_src = pmc_traffic("gemm_hbm_traffic")
+            traffic_c3, traffic_c3_src = pmc_traffic("conv3_hbm_traffic")
+            ach = (flops / (ms * 1e-3)) / 1e12 if ms > 0 else 0.0
+            mfma_rate = (mfma_flops / (ms * 1e-3)) / 1e12 if ms > 0 else 0.0       # what the matrix pipe executes: piece products included
+            mfma_peak = PEAK_F32_TF if args.fp32_mfma else PEAK_BF16_TF
+            # Roofline objects (the step is bound by the matrix cores).  Definition, the same for both: `achieved` = ALGORITHMIC
+            # (fp32-equivalent, 2 M N K per product; only real pixels on the 7x7 region maps) TFLOP/s over the launches' own time -- event pairs
+            # in the dispatch packets / on the launch stream, in a leg of its own --; `peak` = the dense bf16 / fp16 MFMA peak divided by the
+            # piece products the arithmetic form issues per product (3: two fp16 pieces, 6: three bf16 pieces; the launch-weighted mean when a
+            # family mixes them); `frac` = achieved / peak = executed matrix-core flops / the dense peak (`mfma_executed` / `mfma_peak`).
+            pp_nt = mfma_flops / max(flops, 1.0)
+            nt = {"bound": "mfma",
+                  "kernel": ("vbg::plane_gemm_kernel<*,*,*,*,*,false,*,2> + vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,1> (one-product NT GEMM, amp: fp16 hi planes / bf16; every ungrouped launch)" if args.amp else
+                             "vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,0> (fp32 MFMA NT GEMM; every ungrouped launch)" if args.fp32_mfma else
+                             "vbg::plane_gemm_kernel<*,*,*,*,*,false,*,0|1> + vbg::gemm_kernel<*,*,*,DENSE_K,DENSE_K,*,3> (fp32-grade NT GEMM: the BERT linears from pre-split planes, 1x1 convs / heads with the in-kernel split; every ungrouped launch)"),
+                  "achieved": round(ach, 2), "peak": round(mfma_peak / max(pp_nt, 1.0), 1), "unit": "TFLOP/s", "frac": round(mfma_rate / mfma_peak, 4),
+                  "mfma_executed": round(mfma_rate, 1), "mfma_peak": round(mfma_peak, 1), "piece_products_per_product": round(pp_nt, 3),
+                  "traffic": traffic, "traffic_source": traffic_src, "launches": launches, "avg_us": round(1e3 * ms / max(launches, 1), 2),
+                  "ms_per_step": round(ms / args.steps, 3), "vs_fp32_mfma_peak": round(ach / PEAK_F32_TF, 4)}
+            tavg, tsrc = trace_avg("nt")
+            if tavg and launches and not (args.amp or args.fp32_mfma):
+                # `frac` with the committed kernel trace's average launch duration in place of this run's event pairs
+                nt["frac_trace"] = round(mfma_flops / launches / (tavg * 1e-6) / 1e12 / mfma_peak, 4)
+                nt["frac_trace_source"] = f"{tsrc}: {tavg:.2f} us per launch in the rocprofv3 kernel trace of this command (another run, same box class)"
+            if getattr(prof, "ingest", None) and prof.ingest[0] and prof.ingest[2] > 0:
+                # what the plane products of the family are bound by: bytes their workgroups move from L2 into LDS -- tiles x k-tiles
+                # x stage bytes, every operand panel once per tile that uses it -- over the same launch times
+                nt["l2_to_lds"] = {"launches": prof.ingest[0], "MB_per_launch": round(prof.ingest[1] / prof.ingest[0] / 1e6, 1),
+                                   "TB_per_s": round(prof.ingest[1] / (prof.ingest[2] * 1e-3) / 1e12, 2), "ms_per_step": round(prof.ingest[2] / args.steps, 3)}
+            if c3rec and c3_ms > 0:
+                # the dominant kernel family by time since round 3: the row-reuse 3x3 convolutions, forward + input gradient
+                pp_c3 = c3_exec / max(c3_fl, 1.0)
+                c3 = {"bound": "mfma", "kernel": "vbg::conv3x3_kernel<*,*,*> (3x3 / stride-1 convolutions, forward + input gradient, csrc/conv3.hip)",
+                                   "achieved": round(c3_fl / c3_ms / 1e9, 2), "peak": round(mfma_peak / max(pp_c3, 1.0), 1), "unit": "TFLOP/s",
+                                   "frac": round(c3_exec / c3_ms / 1e9 / mfma_peak, 4), "mfma_executed": round(c3_exec / c3_ms / 1e9, 1), "mfma_peak": round(mfma_peak, 1),
+                                   "piece_products_per_product": round(pp_c3, 3), "traffic": traffic_c3, "traffic_source": traffic_c3_src,
+                                   "launches": len(c3rec), "avg_us": round(1e3 * c3_ms / len(c3rec), 2), "ms_per_step": round(c3_ms / args.steps, 3),
+                                   "vs_fp32_mfma_peak": round(c3_fl / c3_ms / 1e9 / PEAK_F32_TF, 4)}
+                tavg, tsrc = trace_avg("conv3")
+                if tavg and not (args.amp or args.fp32_mfma):
+                    c3["frac_trace"] = round(c3_exec / len(c3rec) / (tavg * 1e-6) / 1e12 / mfma_peak, 4)
+                    c3["frac_trace_source"] = f"{tsrc}: {tavg:.2f} us per launch in the rocprofv3 kernel trace of this command (another run, same box class)"
+                if single is not None and single["c3"][1] > 0 and single["nt"][1] > 0:
+                    how = "the same launches in a pass with everything on ONE stream (VBG_OVERLAP=0): alone on the chip"
+                    n1, m1, x1 = single["nt"]
+                    nt["single_stream"] = {"frac": round(x1 / m1 / 1e9 / mfma_peak, 4), "avg_us": round(1e3 * m1 / max(n1, 1), 2),
+                                           "ms_per_step": round(m1 / (args.steps + 1), 3), "how": how}          # (the pass runs one warm-up step)
+                    n1, m1, x1 = single["c3"]
+                    c3["single_stream"] = {"frac": round(x1 / m1 / 1e9 / mfma_peak, 4), "avg_us": round(1e3 * m1 / max(n1, 1), 2),
+                                           "ms_per_step": round(m1 / (args.steps + 1), 3), "how": how}
+                    nt["as_run"] = c3["as_run"] = ("`frac` / `avg_us` are the launches as they run in the step: the encoder on a second stream beside the "
+                                                   "CNN's first stage -- a shorter step made of longer launches; `single_stream` is the kernel alone")
+                # `roofline` = the family that takes more of the step (ms_per_step); the other one rides beside it under its own name
+                if c3["ms_per_step"] >= nt["ms_per_step"]:
+                    out["roofline"], out["roofline_nt"] = c3, nt
+                else:
+                    out["roofline"], out["roofline_conv3"] = nt, c3
+                out["roofline"]["kernel"] += ": the largest kernel family of the step by time"
             else:
-                out["roofline"], out["roofline_conv3"] = nt, c3
-            out["roofline"]["kernel"] += ": the largest kernel family of the step by time"
-        else:
-            out["roofline"] = nt
+                out["roofline"] = nt
         if stock_leg is not None:
             out["stock_loop"] = stock_leg
         if h2d_leg is not None:
@@ -780,7 +860,7 @@ def main():
                 out["fp32_mfma"] = fp32_leg
             if strict_leg is not None:
                 out["bf16x3_strict"] = strict_leg
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the CPU restatement of the step on this box's host cores, cfg2 shape (B = 2) and cfg1 beside it.  The
             # oracle's many small ops oversubscribe at torch.set_num_threads(os.cpu_count()) (256 threads: minutes per step), so the thread
             # count is swept -- each count in a child process with a time limit -- and the BEST count that finishes is the baseline

@@ -91,12 +91,42 @@ def test_overlay_import_resolution(tmp_path, launch):
     assert os.path.realpath(res["net_module_file"]) == os.path.realpath(os.path.join(PKG, "model", "ViBERTgrid_net.py"))
 
 
-def test_overlay_against_the_real_checkout():
-    """in the build container the real checkout is there: `pipeline.distributed_utils` (torch only) must come from it, the model from
-    here, launched from inside the checkout like `python train_SROIE.py`.  Skipped where /root/reference does not exist (GPU box)."""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "pipeline")) or not os.path.exists(os.path.join(PKG, "libvbg.so")):
-        pytest.skip("no reference checkout here")
+def _checkout_like_tree(top):
+    """a tree with the reference checkout's full module list (every module of its `model/` and `pipeline/`, no `__init__.py`, the entry
+    scripts beside them); `pipeline/distributed_utils.py` imports torch.distributed and defines the names the entry points import from it"""
+    for d in ("pipeline", "model", "data", "utils", "deployment"):
+        os.makedirs(os.path.join(top, d))
+    marker = "WHO = 'checkout'\n"
+    for f in ("criteria", "custom_loss", "ephoie_data_preprocessing", "funsd_data_preprocessing", "sroie_data_preprocessing",
+              "train_val_utils", "transform"):
+        open(os.path.join(top, "pipeline", f + ".py"), "w").write(marker)
+    open(os.path.join(top, "pipeline", "distributed_utils.py"), "w").write(marker + textwrap.dedent("""
+        import torch
+        import torch.distributed
+        def setup_seed(seed):
+            torch.manual_seed(seed)
+        def is_main_process():
+            return not torch.distributed.is_initialized() or torch.distributed.get_rank() == 0
+        def save_on_master(*args, **kwargs):
+            if is_main_process():
+                torch.save(*args, **kwargs)
+        def init_distributed_mode(args):
+            args.distributed = False
+    """))
+    for f in ("BERTgrid_generator", "ResNetFPN_ViBERTgrid", "ViBERTgrid_net", "crf", "field_type_classification_head", "grid_roi_align",
+              "semantic_segmentation_head"):
+        open(os.path.join(top, "model", f + ".py"), "w").write(marker)
+    for f in ("train_SROIE", "train_FUNSD", "train_EPHOIE", "eval_SROIE", "eval_FUNSD", "eval_EPHOIE"):
+        open(os.path.join(top, f + ".py"), "w").write(marker)
+    return top
+
+
+def test_overlay_against_the_real_checkout(tmp_path):
+    """a checkout with the reference's layout: `pipeline.distributed_utils` (torch only) must come from it, the model from here, launched
+    from inside the checkout like `python train_SROIE.py` (the checkout's directory in front of sys.path)."""
+    if not os.path.exists(os.path.join(PKG, "libvbg.so")):
+        pytest.skip("libvbg.so not built (model.* imports load it)")
+    ref = _checkout_like_tree(str(tmp_path / "ViBERTgrid-PyTorch"))
     code = ("import json, sys, torch\n"
             "sys.path.insert(0, %r)\n"                       # what `python train_SROIE.py` does with the script's directory
             "from model.ViBERTgrid_net import ViBERTgridNet\n"
@@ -104,7 +134,7 @@ def test_overlay_against_the_real_checkout():
             "import pipeline.transform, pipeline.custom_loss\n"
             "print('RESOLVED ' + json.dumps({m: sys.modules[m].__file__ for m in ['model.ViBERTgrid_net', 'pipeline.distributed_utils', "
             "'pipeline.transform', 'pipeline.custom_loss']}))\n" % ref)
-    res = _run([sys.executable, "-c", code], "/tmp", [PKG, ref])
-    assert res["pipeline.distributed_utils"].startswith(ref + os.sep)
+    res = _run([sys.executable, "-c", code], str(tmp_path), [PKG, ref])
+    assert os.path.realpath(res["pipeline.distributed_utils"]).startswith(os.path.realpath(ref) + os.sep)
     for m in ("model.ViBERTgrid_net", "pipeline.transform", "pipeline.custom_loss"):
         assert os.path.realpath(res[m]).startswith(os.path.realpath(PKG) + os.sep), (m, res[m])

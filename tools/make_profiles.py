@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Summarise the rocprofv3 runs of gpurun_out/ into the committed profiles/ (names carry the round tag).
+"""Summarise the rocprofv3 runs of $PROF_DIR (default prof_raw/) into the committed profiles/ (names carry the round tag).
 
     python tools/make_profiles.py [r04] [steps in the kernel trace = 23] [steps in the PMC traces = 7]
 
-expects (tools/collect_profiles.sh): gpurun_out/prof_e (kernel-trace + stats of `bench.py --steps 10 --warmup 3 --no-h2d-leg`),
-gpurun_out/pmc_f / pmc_w (FETCH_SIZE / WRITE_SIZE passes of `bench.py --steps 3 --warmup 1 --no-h2d-leg`), gpurun_out/pmc_m (SQ / GRBM
-pass of the same command), gpurun_out/gemm_shapes.txt, gpurun_out/bench_line.json"""
+expects (tools/collect_profiles.sh): prof_e (kernel-trace + stats of `bench.py --full --steps 10 --warmup 3 --no-h2d-leg`),
+pmc_f / pmc_w (FETCH_SIZE / WRITE_SIZE passes of `bench.py --full --steps 3 --warmup 1 --no-h2d-leg`), pmc_m (SQ / GRBM
+pass of the same command), gemm_shapes.txt, bench_line.json"""
 import collections, csv, json, os, re, shutil, subprocess, sys
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r06"
 NSTEP = int(sys.argv[2]) if len(sys.argv) > 2 else 23          # bench.py --steps 10 --warmup 3: 3 + 10 (headline) + 10 (roofline leg)
 NPMC = int(sys.argv[3]) if len(sys.argv) > 3 else 7            # bench.py --steps 3 --warmup 1: 1 + 3 + 3
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))) + "/"
-G = R + "gpurun_out/"
+G = os.path.join(R, os.environ.get("PROF_DIR", "prof_raw"), "")
 P = R + "profiles/" + TAG + "_"
 MATRIX = ("gemm_kernel", "attn_kernel<", "conv3x3_kernel", "conv3x3_wgrad_kernel")          # kernels that run on the matrix cores
 
@@ -164,7 +164,7 @@ print("\n".join(summary))
 line = json.loads(open(P + "bench_line.json").read().strip().splitlines()[-1])
 agr = ["# agreement check of bench.py's roofline objects with rocprofv3's kernel trace (tools/make_profiles.py; all runs on one box).",
        "# `live` = bench.py's event timing in the committed bench line (run WITHOUT the profiler); `live, traced run` = the same timing in the",
-       "# very run the trace is of (its JSON line, gpurun_out/prof_e.log).  Since the two-stream defaults (end of round 5) the launches of both",
+       "# very run the trace is of (its JSON line, prof_e.log).  Since the two-stream defaults (end of round 5) the launches of both",
        "# families share the chip with launches of other streams.  The event pair brackets the DISPATCH (start / stop events in the packet):",
        "# with several queues active it includes what the dispatch waits for workgroup slots held by the other streams' kernels; the trace's",
        "# begin / end timestamps are the kernel's own.  One stream (rounds 1-4, and `alone on the chip` below): the two agreed within 1-2 %;",

@@ -1,6 +1,6 @@
 set -x
 mkdir -p gpurun_out/ov
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-amp-leg --no-h2d-leg"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-amp-leg --no-h2d-leg"
 VBG_OVERLAP=0 $B > gpurun_out/ov/b_off.json 2> gpurun_out/ov/b_off.err
 VBG_OVERLAP=1 VBG_WGRAD_STREAM=0 $B > gpurun_out/ov/b_side.json 2> gpurun_out/ov/b_side.err
 VBG_OVERLAP=1 VBG_WGRAD_STREAM=1 $B > gpurun_out/ov/b_both.json 2> gpurun_out/ov/b_both.err

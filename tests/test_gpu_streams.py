@@ -4,14 +4,14 @@ Round 5's committed evidence (profiles/r05_stream_race.txt line 10) held one run
 one-stream step -- 700x the float-atomics noise floor -- with the convolution weight gradients on their own stream (the default).  Nothing
 in the suite could see it: the toy test (r18, 96 x 128) never has three busy streams, and 7.9e-4 slides under the 1e-3 gates of the
 full-scale fixtures.  Root cause (profiles/r06_stream_race.txt; NOT the amax slots VERDICT / ADVICE r5 suspected, though those are now
-reserved for the side stream as well): the pipelined pre-split convolution kernel (csrc/conv3.hip, PWM = 2) read k-tile 0 of its filter
+reserved for the side stream as well): the pipelined pre-split convolution kernel (csrc/conv3.hip, PW) read k-tile 0 of its filter
 ring behind the prologue barrier and let the first k-tile of the loop refill the same stage with k-tile 4 -- no barrier in between; on
 64-filter tiles (six MFMAs per k-tile) a wave that fell one k-tile behind multiplied the wrong filter slice.  It takes three busy streams.
 
 test_default_streams_equal_one_stream_at_batch8 runs the cfg2 batch-8 step (bench.py's model and batch: resnet-34 + 12-layer BERT,
 8 x 512 x 512) 48 times with every default stream on, with 16-slot amax pools (a pool then turns over ~20 times inside one backward
-instead of once per step), against the same step on ONE stream from identical state, and gates at 1e-5 (noise floor 1.3e-6).  With the
-guard barrier left out (VBG_DEBUG_CONV3_NO_RING_GUARD=1) this test FAILS on the GPU box (12 outliers in 160 runs); with it: 0 in 400."""
+instead of once per step), against the same step on ONE stream from identical state, and gates at 1e-5 (noise floor 1.3e-6).  Without
+the guard barrier this test failed on the GPU box (12 outliers in 160 runs); with it: 0 in 400."""
 import contextlib
 import os
 import random
@@ -137,11 +137,10 @@ def _ring_contention_mismatches(reps=400):
 
 
 def test_pipelined_conv3_ring_is_safe_under_contention():
-    """Root cause of the round-5 outlier (csrc/conv3.hip, PWM = 2 prologue): k-tile 0's fragments were read behind the prologue barrier
+    """Root cause of the round-5 outlier (csrc/conv3.hip, PW prologue): k-tile 0's fragments were read behind the prologue barrier
     and the first k-tile of the loop ended with the DMA of k-tile 4 into the same ring stage, with no barrier between the two -- a wave
     that fell one (six-MFMA) k-tile behind read the wrong filter slice.  With the guard barrier every one of 400 contended launches is
-    bit-identical to the first.  (tools/calls/r6_call06.sh runs the same function with VBG_DEBUG_CONV3_NO_RING_GUARD=1 to show that it
-    SEES the race when the barrier is left out.)"""
+    bit-identical to the first."""
     assert _ring_contention_mismatches(400) == 0
 
 

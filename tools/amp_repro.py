@@ -23,7 +23,7 @@ g = np.load(os.path.join(ROOT, "tests", "golden", "e2e.npz"))
 dbatch = to_dev(_e2e_inputs(g), dev)
 ops.set_overlap(os.environ.get("OVERLAP", "0") != "0")
 if os.environ.get("ONE_STREAM", "0") != "0":
-    ops._CONV_WGRAD_STREAM[0] = 0; ops.set_wgrad_stream(False)
+    ops._CONV_WGRAD_STREAM[0] = 0
 ops.set_pair(True, force=True)
 runs = []
 for r in range(5):

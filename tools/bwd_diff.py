@@ -38,7 +38,7 @@ with contextlib.redirect_stdout(sys.stderr):
         batch = PackedBatch.pack(*bench.synthetic_batch(8, 512, 512, 512, 128, bench.NCLS, bench.VOCAB, 1234)).to(dev)
 cnn, bert = split_parameters(net)
 opts = [FusedSGD(cnn, dev, lr=0.0), FusedAdamW(bert, dev, lr=0.0)]
-ops.set_overlap(False); ops._CONV_WGRAD_STREAM[0] = 0; ops.set_wgrad_stream(False)          # one stream
+ops.set_overlap(False); ops._CONV_WGRAD_STREAM[0] = 0          # one stream
 
 
 def fp(t):

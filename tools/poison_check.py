@@ -71,7 +71,7 @@ def main():
     groups = [o.group for o in opts]
     batch = PackedBatch.pack(*bench.synthetic_batch(8, 512, 512, 512, 128, bench.NCLS, bench.VOCAB, 1234)).to(dev)
     gen = net.BERTgrid_generator
-    ops.set_overlap(False); ops._CONV_WGRAD_STREAM[0] = 0; ops.set_wgrad_stream(False)
+    ops.set_overlap(False); ops._CONV_WGRAD_STREAM[0] = 0
 
     def one():
         for o in opts:

@@ -4,12 +4,10 @@ from identical state (same dropout seed, same host RNG): every flat gradient buf
 worst single PARAMETER (a stale operand hits one layer: a group norm can hide it), several repetitions each -- the single-stream
 repetitions give the noise floor of the float atomics.  A race shows as a difference far above it.
 
-    python tools/stream_race_check.py [--reps 4] [--amax-pool 16] [--no-reserve] [--only-default]
+    python tools/stream_race_check.py [--reps 4] [--amax-pool 16] [--only-default]
 
 --amax-pool N   slots per amax pool (default 256): small pools turn over several times inside one backward, which is what a
                 use-after-free of a pool needs to show
---no-reserve    the round-5 behaviour: amax slots read by the weight-gradient stream are NOT record_stream-ed (the A/B that names
-                the root cause of profiles/r05_stream_race.txt line 10)
 --only-default  skip the intermediate configurations: one stream vs the default streams only"""
 import argparse, contextlib, os, random, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,7 +37,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--amax-pool", type=int, default=0)
-    ap.add_argument("--no-reserve", action="store_true")
     ap.add_argument("--only-default", action="store_true")
     ap.add_argument("--no-encoder-stream", action="store_true", help="the conv weight-gradient stream WITHOUT the encoder's side stream")
     ap.add_argument("--cw-level", type=int, default=2, help="VBG_CONV_WGRAD_STREAM level of the streams-on runs (1: conv + BatchNorm nodes only)")
@@ -56,7 +53,6 @@ def main():
     from vbg.optim import FusedAdamW, FusedSGD, split_parameters
     if args.amax_pool:
         ops._AMAX_POOL_SLOTS[0] = args.amax_pool
-    ops._RESERVE_AMAX[0] = not args.no_reserve
     dev = torch.device("cuda", 0)
     with contextlib.redirect_stdout(sys.stderr):
         torch.manual_seed(42)
@@ -72,8 +68,8 @@ def main():
     batch = PackedBatch.pack(*bench.synthetic_batch(shp["batch"], shp["img"], shp["img"], 512, shp["S"], shp["ncls"], shp["vocab"], 1234)).to(dev)
     gen = net.BERTgrid_generator
 
-    def one(overlap, cw, bw):
-        ops.set_overlap(overlap and not args.no_encoder_stream); ops._CONV_WGRAD_STREAM[0] = args.cw_level if cw else 0; ops.set_wgrad_stream(bw)
+    def one(overlap, cw):
+        ops.set_overlap(overlap and not args.no_encoder_stream); ops._CONV_WGRAD_STREAM[0] = args.cw_level if cw else 0
         for o in opts:
             o.zero_grad()
         gen._step_seed = 0x5EED
@@ -85,7 +81,7 @@ def main():
         torch.cuda.synchronize()
         return float(loss), out
 
-    one(False, False, False)                                  # warm-up (flat storage, plane images)
+    one(False, False)                                         # warm-up (flat storage, plane images)
     TR = {"on": False, "rec": []}
     if args.trace:
         _red, _app, _dg = ops.bn_bwd_reduce, ops.bn_bwd_apply_fold, ops.conv2d_dgrad
@@ -136,11 +132,11 @@ def main():
         return "\n".join(lines) if lines else "      (no captured intermediate deviates)"
 
     if args.trace:
-        l0, g0, ref_trace = traced(False, False, False)
+        l0, g0, ref_trace = traced(False, False)
     else:
-        l0, g0 = one(False, False, False)
+        l0, g0 = one(False, False)
     names = ("cnn", "bert")
-    print(f"amax pool slots {ops._AMAX_POOL_SLOTS[0]}, amax slots reserved for the side streams: {ops._RESERVE_AMAX[0]}", flush=True)
+    print(f"amax pool slots {ops._AMAX_POOL_SLOTS[0]}", flush=True)
     worst_seen = {}
 
     def cmp(tag, l, g):
@@ -162,7 +158,7 @@ def main():
                         print(f"      offender @{off:>9d} {n:60s} rel-L2 {r:.2e}  |g| {nx:.3e}  share of the group's error {float((x - y).norm() / (a - b).norm()):.3f}", flush=True)
 
     for r in range(args.reps):
-        cmp(f"one stream again (noise floor) #{r}", *one(False, False, False))
+        cmp(f"one stream again (noise floor) #{r}", *one(False, False))
     if args.jitter:
         rng = random.Random(99)
         for r in range(args.reps):
@@ -171,7 +167,7 @@ def main():
             junk = [torch.full((rng.randrange(1 << 18, 1 << 25),), float("nan"), device=dev) for _ in range(rng.randrange(4, 16))]
             held = junk[::2]
             del junk
-            cmp(f"one stream, shifted allocations #{r}", *one(False, False, False))
+            cmp(f"one stream, shifted allocations #{r}", *one(False, False))
             del held
         print("worst over the repetitions (group rel-L2, parameter rel-L2):")
         for (key, n), (a, b) in worst_seen.items():
@@ -179,19 +175,16 @@ def main():
         return
     if not args.only_default:
         for r in range(args.reps):
-            cmp(f"encoder on the side stream #{r}", *one(True, False, False))
+            cmp(f"encoder on the side stream #{r}", *one(True, False))
     for r in range(args.reps):
         if args.trace:
-            l, g, rec = traced(True, True, False)
+            l, g, rec = traced(True, True)
             cmp(f"+ conv weight gradients on their stream #{r}", l, g)
             if float((g0[0] - g[0]).norm() / g0[0].norm()) > 2e-5:
                 print(first_deviation(ref_trace, rec), flush=True)
             del rec
         else:
-            cmp(f"+ conv weight gradients on their stream #{r}", *one(True, True, False))
-    if not args.only_default:
-        for r in range(args.reps):
-            cmp(f"+ encoder weight gradients on theirs #{r}", *one(True, True, True))
+            cmp(f"+ conv weight gradients on their stream #{r}", *one(True, True))
     print("worst over the repetitions (group rel-L2, parameter rel-L2):")
     for (key, n), (a, b) in worst_seen.items():
         print(f"  {key:44s} {n:5s} {a:.2e} {b:.2e}")

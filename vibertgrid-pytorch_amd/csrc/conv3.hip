@@ -40,7 +40,6 @@ struct conv3_args {
     unsigned* tickets;     // [tiles] arrival counters of the split form, zero between launches
     int accumulate;
     const unsigned* a_amax; // F16 form: bits of max |X| (a device word written by the producer of X), or null: X is used as it is
-    int dbg_no_ring_guard; // VBG_DEBUG_CONV3_NO_RING_GUARD=1: leave out the round-6 barrier behind the read of k-tile 0 (tests prove they can see the race)
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t c3_rsrc(const float* base) {
@@ -134,47 +133,22 @@ struct c3_pipe2 {
 // writes it ONCE per weight version as fp16-pair planes in the order this kernel walks it: one contiguous 64 * BN byte block per
 // (filter tile, tap, 16-channel chunk) = [plane][32-row block][8-channel half][row][8 x fp16] -- the image a lane-linear LDS-DMA
 // lands conflict free for the ds_read_b128 fragment pattern (a 16-lane group reads 16 different 16-byte bank quads).  The k-loop then
-// issues BN / 64 `buffer_load ... lds` per wave and k-tile into a ring of NSB stages (counted vmcnt, D = NSB - 1 tiles in flight) and
+// issues BN / 64 `buffer_load ... lds` per wave and k-tile into a ring of NSB = 4 stages (counted vmcnt, NSB - 2 k-tiles of lead) and
 // spends no VALU and no ds_write on the filter: 4 bytes per element from L2 as before (two fp16 pieces = one fp32), in full 128-byte
 // lines instead of 64-byte row pieces, and three quarters of the kernel's split work gone (the activation super-tile, loaded every
-// third k-tile, is the rest).
-// PWM = 2: the same with a software-pipelined k-loop -- the fragments of k-tile t + 1 are read from LDS in the gaps of the MFMAs of
-// k-tile t (two register sets), the activation super-tile is stored one k-tile earlier (loaded at kw = 0, split and stored at kw = 1,
-// first read during kw = 2), and the DMA runs one k-tile further ahead of its readers.  A wave's k-tile is then MFMAs + one barrier: what
-// the one-round launches of the trunk (one wave per SIMD, nobody to hide the LDS latency behind) were missing.  Same products in the
-// same order per accumulator: bit-identical.
-// ONEP (`amp`, PWM = 2 only): ONE product -- the hi pieces of both operands (x rounded to fp16: the operand of the reference's autocast
+// third k-tile, is the rest).  The loop is software-pipelined: the fragments of k-tile t + 1 are read from LDS in the gaps of the MFMAs
+// of k-tile t (two register sets), and the activation super-tile is stored one k-tile early (loaded at kw = 0, split and stored at
+// kw = 1, first read during kw = 2).  A wave's k-tile is then MFMAs + one barrier: what the one-round launches of the trunk (one wave
+// per SIMD, nobody to hide the LDS latency behind) need.
+// ONEP (`amp`, PW only): ONE product -- the hi pieces of both operands (x rounded to fp16: the operand of the reference's autocast
 // convolution; gradients scaled into range as in the pair form), fp32 accumulation.  The lo pieces are neither written, loaded (128-filter
 // tiles: the hi plane is the first half of a k-tile's block) nor read.
-#ifndef VBG_C3_NSB64
-#define VBG_C3_NSB64 4          // ring stages of the pipelined pre-split kernel on 64-filter tiles (4 KB each); 8 measured: no change (round 6)
-#endif
-#ifndef VBG_C3_ASMW
-#define VBG_C3_ASMW 0           // 1: the pipelined loop's activation pieces go to LDS through inline-asm ds_write_b64 (c3_lds_store_b64); measured: no change
-#endif
-// (Round 6 experiment, compiled out by default: -DVBG_C3_ASMW=1 / -DVBG_C3_NSB64=8.  Both were built on the reading that the one-round
-//  64-filter launches wait for their filter DMA; four builds, bit-identical results, every cfg2 shape within +-1 % and the step within
-//  0.2 % -- tools/calls/r6_call09.sh, gpurun_out/r6c09_*: the reading was wrong, the switches stay for the record.)
-// An LDS store the compiler does not see as one.  hipcc puts `s_waitcnt vmcnt(0)` in front of every LDS WRITE that follows an LDS-DMA in
-// program order (it cannot prove that the DMA's destination and the store do not overlap), i.e. in front of the activation pieces of
-// every third k-tile -- which waits for the filter DMA issued ONE k-tile earlier to land: the ring's lead is gone exactly where a
-// 64-filter k-tile (six MFMAs) needs it most (ISA of round 5: `s_waitcnt vmcnt(0)` + 4 ds_write_b64 in the kw = 1 tile).  The stores
-// go to the activation buffers, the DMA to the filter ring: disjoint by construction.  Ordering against the readers is what it was: the
-// explicit `s_waitcnt lgkmcnt(0)` + s_barrier that ends every k-tile.
-__device__ __forceinline__ void c3_lds_store_b64(unsigned* dst, const uint2& v) {
-    typedef __attribute__((address_space(3))) unsigned* lds_u32;
-    const unsigned addr = (unsigned)(size_t)(lds_u32)dst;
-    const unsigned long long d = ((unsigned long long)v.y << 32) | v.x;
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(d) : "memory");
-}
-
-template <int BM, int BN, bool F16, int PWM = 0, bool ONEP = false>
+template <int BM, int BN, bool F16, bool PW = false, bool ONEP = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
-    constexpr bool PW = PWM != 0;
     static_assert(!PW || (F16 && BM == 128), "pre-split weights: the fp16-pair form on 128-pixel tiles");
-    static_assert(!ONEP || PWM == 2, "the one-product form exists for the pipelined pre-split kernels");
+    static_assert(!ONEP || PW, "the one-product form exists for the pre-split kernels");
     constexpr int NT = 256, SKH = 24;
-    constexpr int NSB = (PWM == 2 && BN == 64) ? VBG_C3_NSB64 : 4, DPF = NSB - 1;      // PW: stages of the filter ring / k-tiles in flight
+    constexpr int NSB = 4;                                     // PW: stages of the filter ring
     constexpr int BTILE = 64 * BN;                             // PW: bytes of one k-tile of the filter (2 planes x BN rows x 32 B)
     constexpr int NDB = BN / 64;                               // PW: 1 KiB DMA units per wave and k-tile
     constexpr int NDBE = (ONEP && NDB == 2) ? 1 : NDB;         // ... that are issued (ONEP at 128 filters: the hi plane = units 0-3 only)
@@ -375,19 +349,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) fa[q][i] = as[q * (PA / 4) + (arow[i] + kw) * (SKH / 8) + lk];
 #pragma unroll
-            for (int j = 0; j < TNF; ++j) {
-                if constexpr (PW) fb[q][j] = *reinterpret_cast<const c3_u32x4*>(ring + bbuf * BTILE + q * (BTILE / 2) + (wn * TNF + j) * 1024 + lk * 512 + lr * 16);
-                else fb[q][j] = bs[q * (PB / 4) + (brow + j * 32) * (SKH / 8) + lk];
-            }
+            for (int j = 0; j < TNF; ++j) fb[q][j] = bs[q * (PB / 4) + (brow + j * 32) * (SKH / 8) + lk];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PW) {
-            if constexpr (LOADA) load_a();     // (in front of the DMA: waiting for these registers must not wait for the DMA behind them)
-            issue_b();
-        } else {
-            if constexpr (MORE) load_b();
-            if constexpr (LOADA) load_a();
-        }
+        if constexpr (MORE) load_b();
+        if constexpr (LOADA) load_a();
         __builtin_amdgcn_sched_barrier(0);
         // piece products, smallest first: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi); F16: (lo,hi) (hi,lo) -> cross sums, (hi,hi)
         constexpr int qa[6] = {F16 ? 1 : 2, 0, 1, 1, 0, 0}, qb[6] = {0, F16 ? 1 : 2, F16 ? 0 : 1, 0, 1, 0};
@@ -411,19 +377,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
         using i0 = std::integral_constant<int, 0>;
         using ih = std::integral_constant<int, F16 ? 1 : 2>;
         using i1 = std::integral_constant<int, F16 ? 3 : 6>;
-        if constexpr (MORE && PW) {
-            mma_range(i0{}, ih{});
-            __builtin_amdgcn_sched_barrier(0);
-            mma_range(ih{}, i1{});
-            if constexpr (LOADA) {
-                store_a(abuf ^ 1);
-                c3_pipe<0, 2 * TNF * TM, NAI * 10, NAI * 2>::run();
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // this wave's share of the NEXT k-tile has landed (the DPF - 1 tiles behind it stay in flight), then everybody's
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DPF - 1) * NDB) : "memory");
-            __syncthreads();
-        } else if constexpr (MORE) {
+        if constexpr (MORE) {
             mma_range(i0{}, ih{});
             __builtin_amdgcn_sched_barrier(0);
             mma_range(ih{}, i1{});
@@ -444,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
     for (int e = tid; e < 2 * ASZ / 4; e += NT) reinterpret_cast<uint4*>(As)[e] = make_uint4(0u, 0u, 0u, 0u);
     set_a(kh0);
     const int nsup = (p.ksplit == 3 ? 1 : 3) * cw / 16;
-    if constexpr (PWM == 2) {
+    if constexpr (PW) {
         // Ring of NSB stages (4); the DMA of k-tile t + NSB is issued at the END of k-tile t into the
         // stage of k-tile t itself (its fragments were read during k-tile t - 1), and must have landed by the end of k-tile t + NSB - 2:
         // NSB - 2 k-tiles of lead.
@@ -505,23 +459,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
 #pragma unroll
             for (int i = 0; i < NAI; ++i) {
                 const int o = a_lrow[i] * (SKH / 2) + kc / 2;
-#if VBG_C3_ASMW
-                c3_lds_store_b64(&dst[o], sh[i]);
-                if constexpr (!ONEP) c3_lds_store_b64(&dst[o + PA], sl[i]);
-#else
                 *reinterpret_cast<uint2*>(&dst[o]) = sh[i];
                 if constexpr (!ONEP) *reinterpret_cast<uint2*>(&dst[o + PA]) = sl[i];
-#endif
             }
             if (wide && tid < 8) {
                 const int o = h_row * (SKH / 2) + kc / 2;
-#if VBG_C3_ASMW
-                c3_lds_store_b64(&dst[o], sh[NAI]);
-                if constexpr (!ONEP) c3_lds_store_b64(&dst[o + PA], sl[NAI]);
-#else
                 *reinterpret_cast<uint2*>(&dst[o]) = sh[NAI];
                 if constexpr (!ONEP) *reinterpret_cast<uint2*>(&dst[o + PA]) = sl[NAI];
-#endif
             }
         };
         using p0 = std::integral_constant<int, 0>;
@@ -562,39 +506,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
         // k-tile's contribution (1/6 of its magnitude), seen in 5-12 % of cfg2 steps once three streams shared the chip -- the "conv
         // weight-gradient stream" outlier of profiles/r05_stream_race.txt (tools/stream_race_check.py --trace named the tensor, the wave
         // and the size).  Every wave now holds k-tile 0's fragments in registers before anybody may refill the stage.
-        if (!p.dbg_no_ring_guard) {                            // (uniform: a kernel argument)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
         using k0 = std::integral_constant<int, 0>;
         using k1 = std::integral_constant<int, 1>;
         using k2 = std::integral_constant<int, 2>;
         for (int s = 0; s < nsup; s += 2) {
             tile(p0{}, k0{}, s); tile(p1{}, k1{}, s); tile(p0{}, k2{}, s);
             if (s + 1 < nsup) { tile(p1{}, k0{}, s + 1); tile(p0{}, k1{}, s + 1); tile(p1{}, k2{}, s + 1); }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the zero-writing DMAs past the end must not land in the staged tile
-    } else if constexpr (PW) {
-        d_left = 3 * nsup;
-        load_a();
-        __syncthreads();                       // (the zero fill above)
-#pragma unroll
-        for (int d = 0; d < DPF; ++d) issue_b();
-        store_a(0);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DPF - 1) * NDB) : "memory");       // k-tile 0 has landed
-        __syncthreads();
-        int bst = 0;
-        auto nx = [&]() { const int c = bst; bst = bst + 1 == NSB ? 0 : bst + 1; return c; };
-        for (int s = 0; s + 1 < nsup; ++s) {
-            k_tile(no_t{}, yes_t{}, s & 1, nx(), 0);
-            k_tile(no_t{}, yes_t{}, s & 1, nx(), 1);
-            k_tile(yes_t{}, yes_t{}, s & 1, nx(), 2);
-        }
-        {
-            const int s = nsup - 1;
-            k_tile(no_t{}, yes_t{}, s & 1, nx(), 0);
-            k_tile(no_t{}, yes_t{}, s & 1, nx(), 1);
-            k_tile(no_t{}, no_t{}, s & 1, nx(), 2);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the zero-writing DMAs past the end must not land in the staged tile
     } else {
@@ -1221,8 +1140,6 @@ static int conv3x3_impl(const float* x, const float* w, const unsigned short* wp
     const long long M = (long long)B * H * W;
     VBG_CHECK_ARG(M < (1ll << 31));
     a.M = (int)M; a.accumulate = accumulate; a.a_amax = x_amax; a.roi = roi ? B : 0;
-    static const int no_ring_guard = [] { const char* e = getenv("VBG_DEBUG_CONV3_NO_RING_GUARD"); return (e && e[0] == '1') ? 1 : 0; }();
-    a.dbg_no_ring_guard = no_ring_guard;
     // split form: nsplit blocks per tile meet in split_slab [tiles][nsplit][128 * 128] / split_tickets [tiles] (zero; left zero)
     const bool split = nsplit > 1;
     VBG_CHECK_ARG(nsplit >= 1 && (!split || (split_slab && split_tickets && !roi && N % (bn_req ? bn_req : 128) == 0 && ((long long)H * W) % 128 == 0)));
@@ -1241,17 +1158,12 @@ static int conv3x3_impl(const float* x, const float* w, const unsigned short* wp
     if (wp) {
         // the plane image was written for conv3_pw_bn(N) rows per filter tile: the launch must walk it with the same tile
         VBG_CHECK_ARG(big && (bn_req || bn == conv3_pw_bn(N)));
-        // VBG_CONV3_PIPE=0: the lockstep k-loop of the PW kernels (A/B switch of the software-pipelined loop)
-        static const bool pipe = !(getenv("VBG_CONV3_PIPE") && atoi(getenv("VBG_CONV3_PIPE")) == 0);
         if (form == 2) {
-            if (n64) { VBG_LAUNCH((vbg::conv3x3_kernel<128, 64, true, 2, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
-            else { VBG_LAUNCH((vbg::conv3x3_kernel<128, 128, true, 2, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
-        } else if (pipe) {
-            if (n64) { VBG_LAUNCH((vbg::conv3x3_kernel<128, 64, true, 2>), g, dim3(256), 0, (hipStream_t)stream, a); }
-            else { VBG_LAUNCH((vbg::conv3x3_kernel<128, 128, true, 2>), g, dim3(256), 0, (hipStream_t)stream, a); }
+            if (n64) { VBG_LAUNCH((vbg::conv3x3_kernel<128, 64, true, true, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
+            else { VBG_LAUNCH((vbg::conv3x3_kernel<128, 128, true, true, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
         } else {
-            if (n64) { VBG_LAUNCH((vbg::conv3x3_kernel<128, 64, true, 1>), g, dim3(256), 0, (hipStream_t)stream, a); }
-            else { VBG_LAUNCH((vbg::conv3x3_kernel<128, 128, true, 1>), g, dim3(256), 0, (hipStream_t)stream, a); }
+            if (n64) { VBG_LAUNCH((vbg::conv3x3_kernel<128, 64, true, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
+            else { VBG_LAUNCH((vbg::conv3x3_kernel<128, 128, true, true>), g, dim3(256), 0, (hipStream_t)stream, a); }
         }
         VBG_LAUNCH_RET();
     }

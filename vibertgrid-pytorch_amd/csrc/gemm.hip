@@ -31,10 +31,6 @@
 #include <hip/hip_ext.h>
 #include "../../include/vbg.h"
 
-#ifndef VBG_PIPE2_X16
-#define VBG_PIPE2_X16 0
-#endif
-
 namespace vbg {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -108,7 +104,6 @@ struct sched_pipe {
 template <int BM, int BN, int BK, int NT, int AK, int BKD, bool VEC, int PREC = 0>
 __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
     constexpr bool HB = PREC != 0;
-    constexpr bool PIPE2_X16 = VBG_PIPE2_X16;      // 16-deep bf16 k-tiles on the two-tiles-in-flight loop as well (measured, see below)
     // PREC 2 (round 6): fp32-grade products on the fp16 matrix cores for operands inside fp16's range (FORWARD products: activations and
     // weights) -- two pieces per operand, hi = fp16(x), lo' = fp16((x - hi) 2^11), both rounded to nearest, three piece products (hi hi into
     // the main accumulators, lo' hi + hi lo' into a second set that is scaled by 2^-11 once, behind the loop): the arithmetic of
@@ -668,7 +663,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
     using no_t = std::integral_constant<bool, false>;
     const int ntiles = kt1 - kt0;
     const bool tail_in_range = HAS_TAIL && kt1 == nkt && (K % BK) != 0;      // the LAST tile of this block is a reduction tail
-    if constexpr (HB && (BK == 32 || PIPE2_X16)) {
+    if constexpr (HB && BK == 32) {
         // ---- bf16 forms: two tiles in flight ---------------------------------------------------------------------------
         // Their MFMA phase is 4-16x shorter than the fp32 form's and no longer covers the latency of loads issued in the same
         // iteration (measured: ~2700 cycles per 128x128x16 k-tile against 768 cycles of MFMAs).  Two register sets: tile j

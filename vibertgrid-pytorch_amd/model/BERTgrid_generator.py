@@ -220,7 +220,7 @@ class BERTgridGenerator(nn.Module):
         # the attention-dropout keeps of all layers in one launch (stream ids as BertLayerFn numbers them: layer * 8)
         flash_ok = maxlen > 0 and ops.flash_ok(hidden, int(cfg.intermediate_size), dh, maxlen)      # (BertLayerFn's own test)
         meta.mask_pool = (ops.attn_mask_layers(meta, pa, seed, 0, 8, len(m.encoder.layer))
-                          if (pa > 0 and flash_ok and ops.mask_pool_enabled() and torch.is_grad_enabled()) else None)
+                          if (pa > 0 and flash_ok and torch.is_grad_enabled()) else None)
         x = Fn.BertEmbedFn.apply(emb.word_embeddings.weight, emb.position_embeddings.weight, emb.token_type_embeddings.weight,
                                  emb.LayerNorm.weight, emb.LayerNorm.bias, ids, pos, eps, p, seed, 1000)
         xpl = None                       # bf16 planes of x, handed from each layer's closing LayerNorm to the next layer's first product

@@ -674,14 +674,15 @@ class BertLayerFn(torch.autograd.Function):
         # (round 6: nothing to differentiate -- inference, validation -- and a problem below the 8-wave tiles: the form runs on the 64 x 64 tile,
         #  half the matrix-core work of the six-product form that single documents used to take)
         nograd = not any(ctx.needs_input_grad)
-        pair = planes and ops.pair_enabled() and (ops.pair_tile(ntok, hid) != 0 or (nograd and ops.pair_small_enabled()))
+        pair = planes and ops.pair_enabled() and (ops.pair_tile(ntok, hid) != 0 or nograd)
         ptile = lambda n, wide=False: ops.pair_tile(ntok, n, wide) or 64004          # (four LDS stages: the weights of a lone document come from HBM)
         carrier_is_pair = xpl is not None and xpl.shape[0] == 2          # (the previous layer ran the all-pair path: xpl ARE the pair planes)
         xq = (ops.Planes(xpl, ntok, hid, xpl.shape[2]) if carrier_is_pair else getattr(xpl, "_vbg_pair", None)) if (pair and xpl is not None) else None
         # all-pair path: the backward products run on two fp16 pieces as well (needs every weight / bias gradient of the layer sunk into
         # the flat buffers, the stacked Q/K/V layout and the fused attention), and so does the attention-output projection; the
         # activations saved for backward are pair planes, no bf16 planes of x1 / gelu(h) / y / ctx are written at all
-        pair_bwd = (pair and ops.pair_bwd_enabled() and fused_qkv and dh == 64 and meta.maxlen <= 512 and ops.flash_enabled()
+        # (pair_bwd implies flash -- pair implies the plane shapes --, one_qkv and, below, xq: its q / k / v are always pair planes)
+        pair_bwd = (pair and ops.pair_bwd_enabled() and fused_qkv and dh == 64 and meta.maxlen <= 512
                     and any(ctx.needs_input_grad)
                     and all(sinks(t) for t in (wq, wk, wv, bq, bk, bv, wo, bo, wi, bi, wo2, bo2)))
         assert not carrier_is_pair or pair, "pair planes handed to a layer that does not run the pair form"
@@ -693,8 +694,7 @@ class BertLayerFn(torch.autograd.Function):
         # parameters NOT stored back to back and nothing to differentiate (inference, validation): the stacked planes of the three
         # projections are cached on the weights (round 6) -- one Q/K/V product as in training instead of three
         one_qkv = fused_qkv or (planes and nograd)
-        attn_pair = (flash and pair and one_qkv and xq is not None and ops.attn_pair_enabled() and ops.bound_planes_enabled()
-                     and (pair_bwd or not any(ctx.needs_input_grad)))
+        attn_pair = flash and pair and one_qkv and xq is not None and (pair_bwd or nograd)
         # round 6: the layer's seven launches leave from ONE library call (csrc/encoder.hip) -- same descriptors, a third of the host time
         fast = planes and flash and one_qkv and ops.layer_entry_ok()
         if flash:
@@ -872,7 +872,7 @@ class BertLayerFn(torch.autograd.Function):
         #      no split pass.  s_dfo = true max |dfo| (the next bound's input), s_dfo_ref = the scale the planes were written with.
         dg2, db2, sunk2 = _affine_dest(rg2, rb2)
         s_dfo = ops.amax_slot(dev)
-        bound = ops.bound_planes_enabled() and sunk2 and hid % 256 == 0
+        bound = sunk2 and hid % 256 == 0
         dyc = _c(dy)
         if bound:
             s_dy = _amax_tag(dy)
@@ -891,17 +891,10 @@ class BertLayerFn(torch.autograd.Function):
         #      BOUND -- max |dfo| (measured: s_dfo) * the largest column L1 norm of Wo2 (once per weight version) * max gelu' (1.129) -- instead
         #      of a measured maximum, so it needs no fp32 round trip and no split pass; s_dh receives the bound (the consumers' scale)
         s_dh = ops.amax_slot(dev)
-        if ops.bound_planes_enabled():
-            qdh = ops.pair_empty(ntok, inter, dev)
-            ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=wo2, pair=True), None, epi=EPI_MUL_GELU_GRAD, C2=h, tile=tile(inter, True), form=1,
-                           a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=wo2), q_mul=1.13 * 1.01, q_ref_out=s_dh,
-                           colsum_out=wgrad_dest(rbi))
-        else:
-            dh_ = torch.empty((ntok, inter), device=dev, dtype=f32)
-            ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=wo2, pair=True), dh_, epi=EPI_MUL_GELU_GRAD, C2=h, tile=tile(inter, True), form=1,
-                           a_amax=s_dfo_ref, c_amax=s_dh)
-            qdh = ops.split_planes_pair(dh_, amax_slot_=s_dh, colsum_out=wgrad_dest(rbi))
-            del dh_
+        qdh = ops.pair_empty(ntok, inter, dev)
+        ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=wo2, pair=True), None, epi=EPI_MUL_GELU_GRAD, C2=h, tile=tile(inter, True), form=1,
+                       a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=wo2), q_mul=1.13 * 1.01, q_ref_out=s_dh,
+                       colsum_out=wgrad_dest(rbi))
         wgrad_done(rbi)
         s_dx1 = ops.amax_slot(dev) if bound else None           # (max |dx1| rides on the product that completes it: LayerNorm 1's bound)
         ops.plane_gemm(qdh, ops.weight_planes(ri, True, view=wi, pair=True), dx1, accumulate=True, tile=tile(hid), form=1, a_amax=s_dh, c_amax=s_dx1)
@@ -918,19 +911,14 @@ class BertLayerFn(torch.autograd.Function):
             del dao
         dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
         wgrad_done(rbo)
-        # ---- d(context), the dO operand of the fused attention backward: as the planes the forward's q / k / v planes call for -- fp16-pair
-        #      planes scaled by a bound (max |dao| x the largest column L1 norm of W_o; the attention kernels read the scale from s_dctx),
-        #      or three bf16 planes (six-product attention)
+        # ---- d(context), the dO operand of the fused attention backward: fp16-pair planes like the forward's q / k / v planes, scaled by a
+        #      bound (max |dao| x the largest column L1 norm of W_o; the attention kernels read the scale from s_dctx)
+        assert bqkv.shape[0] == 2, "the all-pair backward's q / k / v are fp16-pair planes"
         pqkv = ops.Planes(bqkv, ntok, 3 * hid, bqkv.shape[2])
-        s_dctx = None
-        if bqkv.shape[0] == 2:
-            pdctx = ops.pair_empty(ntok, hid, dev)
-            s_dctx = ops.amax_slot(dev)
-            ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=wo, pair=True), None, tile=tile(hid), form=1, a_amax=s_dao_ref, out_pair=pdctx,
-                           q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=wo), q_mul=1.01, q_ref_out=s_dctx)
-        else:
-            pdctx = ops.planes_empty(ntok, hid, dev)
-            ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=wo, pair=True), None, out_planes=pdctx, tile=tile(hid), form=1, a_amax=s_dao_ref)
+        pdctx = ops.pair_empty(ntok, hid, dev)
+        s_dctx = ops.amax_slot(dev)
+        ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=wo, pair=True), None, tile=tile(hid), form=1, a_amax=s_dao_ref, out_pair=pdctx,
+                       q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=wo), q_mul=1.01, q_ref_out=s_dctx)
         delta = ctx.delta_buf
         dqkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
         sc = 1.0 / (dh ** 0.5)
@@ -948,26 +936,9 @@ class BertLayerFn(torch.autograd.Function):
         # ---- the four weight gradients: one grouped TN launch on pair planes
         jobs = [(qdfo, qg, wgrad_dest(ro2)), (qdh, qx1, wgrad_dest(ri)), (qdao, qctx, wgrad_dest(ro)), (qdqkv, qx, _stack3(gq[0]))]
         scales = [s_dfo_ref, s_dh, s_dao_ref, s_dqkv]
-        if ops.wgrad_stream_enabled():
-            # nothing in the rest of the backward waits for these 216 tiles: on the weight-gradient stream they share the chip with the
-            # data-gradient products of the layer below (198 / 408 / 594 tiles: 0.77 / 0.80 / 0.77 of their rounds).  The operands stay
-            # reserved for that stream when this node releases them; the callback (end of backward) / FlatReducer's staging stream join it.
-            cur, ws = torch.cuda.current_stream(dev), ops.side_stream(dev, "wgrad")
-            ws.wait_stream(cur)
-            with torch.cuda.stream(ws):
-                ops.plane_gemm_grouped(jobs, trans=True, accumulate=True, form=1, a_amax=scales)
-                for a_, b_, _ in jobs:
-                    a_.buf.record_stream(ws)
-                    b_.buf.record_stream(ws)
-                for t in scales:
-                    t.record_stream(ws)
-                for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
-                    wgrad_done(t)
-            torch.autograd.Variable._execution_engine.queue_callback(lambda: torch.cuda.current_stream(dev).wait_stream(ws))
-        else:
-            ops.plane_gemm_grouped(jobs, trans=True, accumulate=True, form=1, a_amax=scales)
-            for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
-                wgrad_done(t)
+        ops.plane_gemm_grouped(jobs, trans=True, accumulate=True, form=1, a_amax=scales)
+        for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
+            wgrad_done(t)
         return (dx, None, None, None, None, None, None, None, None, None, dg1, db1, None, None, None, None, dg2, db2, None, None, None, None, None)
 
     @staticmethod
@@ -1066,20 +1037,6 @@ class BertLayerFn(torch.autograd.Function):
             fresh.append(d_ is None)
             dests.append(d_ if d_ is not None else torch.zeros_like(wp))
         jobs = [(pdfo, pg, dests[0]), (pdh, px1, dests[1]), (pdao, pctx, dests[2]), (pdqkv, px, dw_qkv)]
-        if qkv_sunk and not any(fresh) and ctx.side_ok and ops.wgrad_stream_enabled():
-            # every destination is a flat gradient buffer nothing else in this backward touches: the launch goes on the
-            # weight-gradient stream and shares the chip with the backward of the layer below.  The operands stay reserved for
-            # that stream when this node releases them; JoinSideFn's callback / FlatReducer's staging stream wait for it.
-            cur, ws = torch.cuda.current_stream(dev), ops.side_stream(dev, "wgrad")
-            ws.wait_stream(cur)
-            with torch.cuda.stream(ws):
-                ops.plane_gemm_grouped(jobs, trans=True, accumulate=True)
-                for a_, b_, _ in jobs:
-                    a_.buf.record_stream(ws)
-                    b_.buf.record_stream(ws)
-                for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
-                    wgrad_done(t)
-            return (dx, None, None, None, None, None, None, None, None, dbo, dg1, db1, None, dbi, None, dbo2, dg2, db2, None, None, None, None, None)
         ops.plane_gemm_grouped(jobs, trans=True, accumulate=True)
         for wp, fr in zip((ro2, ri, ro), fresh):
             if not fr:

@@ -11,7 +11,7 @@ import torch  # noqa: F401  -- MUST be imported before libvbg.so is dlopen'ed: p
 #                              both have to bind to the SAME libamdhip64 instance (torch ships its own copy)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# VBG_LIB_PATH: another build of the SAME library (A/B measurements of compile-time switches, tools/calls/*.sh); never a different product
+# VBG_LIB_PATH: another build of the SAME library (e.g. one compiled with other flags, for an A/B measurement); never a different product
 LIB_PATH = os.environ.get("VBG_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "libvbg.so")
 
 c_int, c_ll, c_f, c_d, c_vp, c_ull = C.c_int, C.c_longlong, C.c_float, C.c_double, C.c_void_p, C.c_ulonglong
@@ -53,7 +53,6 @@ class PlaneGemmDesc(C.Structure):
                 ("Cp", c_vp), ("c_plane", c_ll), ("ldp", c_ll),
                 ("epi", c_int), ("alpha", c_f), ("accumulate", c_int), ("splitk", c_int), ("tile", c_int), ("trans", c_int),
                 ("ngroups", c_int), ("grp", PlaneGroup * 4),
-                ("sk_ws", c_vp), ("sk_cnt", c_vp), ("sk_blocks", c_int), ("sk_full", c_int), ("sk_tiles_m", c_int), ("sk_tiles_n", c_int),
                 ("colsum", c_vp), ("form", c_int), ("Cq", c_vp), ("q_plane", c_ll), ("ldq", c_ll), ("a_amax", c_vp), ("c_amax", c_vp),
                 ("cq_ref_in", c_vp), ("cq_l1_in", c_vp), ("cq_mul", c_f), ("cq_ref_out", c_vp)]
 

@@ -43,19 +43,6 @@ def set_overlap(on: bool):
     _OVERLAP[0] = bool(on)
 
 
-_WGRAD_STREAM = [os.environ.get("VBG_WGRAD_STREAM", "0") != "0"]
-
-
-def wgrad_stream_enabled() -> bool:
-    """the grouped weight-gradient launch of an encoder layer goes on its own stream (it depends on nothing the rest of the
-    backward waits for): its 216 tiles and the next layer's data-gradient products share the chip"""
-    return _WGRAD_STREAM[0]
-
-
-def set_wgrad_stream(on: bool):
-    _WGRAD_STREAM[0] = bool(on)
-
-
 _CONV_WGRAD_STREAM = [int(os.environ.get("VBG_CONV_WGRAD_STREAM", "2"))]
 
 
@@ -69,19 +56,6 @@ def conv_wgrad_stream_enabled(level: int = 1, pixels: int = 0) -> bool:
     if _CONV_WGRAD_STREAM_MAXPIX[0] > 0 and pixels > _CONV_WGRAD_STREAM_MAXPIX[0]:
         return False
     return int(_CONV_WGRAD_STREAM[0]) >= level
-
-
-_HEADS_STREAM = [os.environ.get("VBG_HEADS_STREAM", "1") != "0"]          # round 6: +2.3 % at cfg2 (A/B x 3 on one box: 31.26 -> 30.56 ms)
-
-
-def heads_stream_enabled() -> bool:
-    """the RoI / field-type branch (RoIAlign, region-map convolutions, late fusion, classifier, its losses) on a stream of its own beside
-    the segmentation head -- both start from P_fuse and meet again in the loss sum, forward and backward (same conditions as VBG_OVERLAP)"""
-    return _HEADS_STREAM[0]
-
-
-def set_heads_stream(on: bool):
-    _HEADS_STREAM[0] = bool(on)
 
 
 _STAGE1_BWD_AFTER = [int(os.environ.get("VBG_STAGE1_BWD_AFTER", "6"))]          # round 6: +0.5 % at cfg2 (A/B x 2 over n = -1, 0, 2 ... 10: profiles/r06_stage1_bwd_order.txt)
@@ -104,16 +78,12 @@ def side_stream(device, name: str = "side") -> "torch.cuda.Stream":
     return s
 
 
-_RESERVE_AMAX = [os.environ.get("VBG_AMAX_RESERVE", "1") != "0"]
-
-
 def reserve_for(stream, *tensors):
     """every operand a launch on `stream` reads that was allocated under ANOTHER stream: the caching allocator must not hand the block
-    to anybody else before that launch has run (record_stream marks the whole block, so a slot view reserves its pool).
-    VBG_AMAX_RESERVE=0 leaves the amax slots (int32 views) out -- the round-5 behaviour, kept ONLY as the A/B that names the root
-    cause of the intermittent weight-gradient mismatch (tools/stream_race_check.py --amax-pool 16)"""
+    to anybody else before that launch has run (record_stream marks the whole block, so a slot view reserves its pool -- leaving the
+    amax slots out was the round-5 intermittent weight-gradient mismatch)"""
     for t in tensors:
-        if t is not None and (_RESERVE_AMAX[0] or t.dtype != torch.int32):
+        if t is not None:
             t.record_stream(stream)
 
 
@@ -123,16 +93,13 @@ def side_streams():
     return list(_SIDE.values())
 
 
-_ASYNC_H2D = [os.environ.get("VBG_ASYNC_H2D", "1") != "0"]
-
-
 def h2d(host, device):
     """numpy array / CPU tensor -> device tensor through pinned staging memory and an ASYNCHRONOUS copy.  A pageable `.to(device)`
     returns only when the copy has run, i.e. after everything enqueued before it: one such upload in the middle of the forward costs
     the host its whole lead over the device (measured: 30-200 us idle gaps behind every one of them, tools/gap_report.py)"""
     t = torch.from_numpy(host) if not torch.is_tensor(host) else host
     device = torch.device(device)
-    if device.type != "cuda" or not _ASYNC_H2D[0]:
+    if device.type != "cuda":
         return t.to(device)
     return t.pin_memory().to(device, non_blocking=True)
 
@@ -321,29 +288,8 @@ def set_pair_bwd(on: bool):
     _PAIR_BWD[0] = bool(on)
 
 
-_BOUND_PLANES = [os.environ.get("VBG_BOUND_PLANES", "1") != "0"]
-
-
-def bound_planes_enabled() -> bool:
-    """gradient pair planes straight from the producing GEMM's epilogue, scaled by a bound instead of a measured maximum (no split pass)"""
-    return _BOUND_PLANES[0]
-
-
 def pair_bwd_enabled() -> bool:
     return pair_enabled() and _PAIR_BWD[0]
-
-
-_PAIR_SMALL = [os.environ.get("VBG_PAIR_SMALL", "1") != "0"]
-
-
-def set_pair_small(on: bool):
-    """forward-only encoder layers (inference, validation) below the 8-wave tiles on the fp16-pair form's 64 x 64 tile instead of the
-    six-product bf16 form (`VBG_PAIR_SMALL=0`: the A/B)"""
-    _PAIR_SMALL[0] = bool(on)
-
-
-def pair_small_enabled() -> bool:
-    return _PAIR_SMALL[0]
 
 
 def pair_tile(M, N, wide=False):
@@ -419,9 +365,6 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
     if _DISPATCH[0] is not None:
         _seen(("plane_gemm:onep" if _AMP[0] else "plane_gemm:pair") if form else "plane_gemm:bf16x3")
         _seen(f"plane_gemm:tile{int(tile)}")
-    if _STREAMK[0] and not form and c_amax is None and colsum_out is None and not trans and splitk == 1 and tile in (128129, 128130):
-        ws, cnt, ncu = _sk_workspace(a.buf.device)
-        d.sk_ws, d.sk_cnt, d.sk_blocks = ws.data_ptr(), cnt.data_ptr(), ncu
     prof = _GEMM_PROF
     if prof is not None and not trans and prof.match(OP_DENSE_K, OP_DENSE_K, False):
         e0, e1 = prof.events()
@@ -433,27 +376,6 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
         return out
     check(lib.vbg_plane_gemm(C.byref(d), _stream()), "vbg_plane_gemm")
     return out
-
-
-_STREAMK = [os.environ.get("VBG_STREAMK", "0") != "0"]          # off: measured slower than the plain rounds at the BERT shapes (csrc/gemm_planes.hip)
-_SK_WS = {}
-
-
-def set_streamk(on: bool):
-    """stream-K tail of the NT plane products (csrc/gemm_planes.hip plane_gemm_sk_kernel)"""
-    _STREAMK[0] = bool(on)
-
-
-def _sk_workspace(device):
-    """(slabs, zeroed tile counters, CU count) of the stream-K tail: one set per (device, stream) -- launches on one stream are
-    ordered, launches on different streams must not share slabs"""
-    key = (device.index, raw_stream())
-    w = _SK_WS.get(key)
-    if w is None:
-        ncu = torch.cuda.get_device_properties(device).multi_processor_count
-        w = (torch.empty((ncu * 2 * 128 * 128,), device=device, dtype=f32), torch.zeros((ncu,), device=device, dtype=i32), ncu)
-        _SK_WS[key] = w
-    return w
 
 
 def plane_gemm_grouped(problems, *, trans=True, accumulate=True, tile=0, alpha=1.0, form=0, a_amax=None):
@@ -505,22 +427,10 @@ def planes_enabled() -> bool:
     return _PLANES[0] and _SPLIT3[0] and not _amp_generic()
 
 
-_FLASH = [os.environ.get("VBG_FLASH", "1") != "0"]
-
-
-def set_flash(on: bool):
-    """fused attention kernels (csrc/attn.hip) for the plane path with 64-wide heads; off = grouped score GEMMs + row softmax"""
-    _FLASH[0] = bool(on)
-
-
 def flash_ok(hidden: int, inter: int, dh: int, maxlen: int) -> bool:
     """does an encoder layer of these dimensions run the fused attention?  ONE predicate for vbg.functions.BertLayerFn and for the
     generator's all-layer dropout-mask launch (the two hand-written copies had drifted apart by the `inter % 32` term)"""
-    return planes_enabled() and hidden % 32 == 0 and inter % 32 == 0 and dh == 64 and maxlen <= 512 and flash_enabled()
-
-
-def flash_enabled() -> bool:
-    return _FLASH[0]
+    return planes_enabled() and hidden % 32 == 0 and inter % 32 == 0 and dh == 64 and maxlen <= 512
 
 
 _HOME = [os.environ.get("VBG_HOME", "1") != "0"]
@@ -793,20 +703,16 @@ def colsum(x, out=None, accumulate=False):
     if out is None:
         out = torch.empty((N,), device=x.device, dtype=f32)
         accumulate = False
-    if _COLSUM_F64[0]:
-        key = (x.device, raw_stream(x.device))
-        ws = _COLSUM_WS.get(key)
-        if ws is None or ws.numel() < N:
-            ws = _COLSUM_WS[key] = torch.empty((max(N, 4096),), device=x.device, dtype=torch.float64)
-        check(lib.vbg_colsum_f64(P(x), x.stride(0), M, N, P(out), int(accumulate), P(ws), _stream()), "vbg_colsum_f64")
-        return out
-    check(lib.vbg_colsum(P(x), x.stride(0), M, N, P(out), int(accumulate), _stream()), "vbg_colsum")
+    key = (x.device, raw_stream(x.device))
+    ws = _COLSUM_WS.get(key)
+    if ws is None or ws.numel() < N:
+        ws = _COLSUM_WS[key] = torch.empty((max(N, 4096),), device=x.device, dtype=torch.float64)
+    check(lib.vbg_colsum_f64(P(x), x.stride(0), M, N, P(out), int(accumulate), P(ws), _stream()), "vbg_colsum_f64")
     return out
 
 
 # bias gradients that do not ride on a split pass are summed in fp64 (csrc/rowops.hip colsum_f64_*: the 1x1 segmentation classifiers'
-# bias gradients cancel to 1e-3 of their running partial sums); VBG_COLSUM_F64=0 restores the fp32 atomics
-_COLSUM_F64 = [os.environ.get("VBG_COLSUM_F64", "1") != "0"]
+# bias gradients cancel to 1e-3 of their running partial sums)
 _COLSUM_WS = {}
 
 
@@ -840,10 +746,6 @@ _CONV3_MIN_TILES = [int(os.environ.get("VBG_CONV3_MIN_TILES", "480"))]
 _CONV3_MIN_TILES_FWD = [int(os.environ.get("VBG_CONV3_MIN_TILES_FWD", "256"))]
 
 
-_CONV3_ROI = [os.environ.get("VBG_CONV3_ROI", "1") != "0"]       # [N, 7, 7, C] region maps on the row-reuse kernels (two images per 128-slot tile)
-_CONV3_N64 = [os.environ.get("VBG_CONV3_N64", "1") != "0"]       # 64-filter tiles (the 64-channel stage of the trunk)
-
-
 def conv3_ok(B, H, W, Cs, N, kh, kw, stride, pad, fwd=False) -> bool:
     """shapes the row-reuse kernel takes: whole image rows per pixel tile, full 128-wide column tiles and at least 480 64-pixel tiles
     (= 240 of the 128-pixel tiles the kernel then uses).  Below that the kernel would run 64-pixel tiles, one 4-wave workgroup per CU:
@@ -854,12 +756,12 @@ def conv3_ok(B, H, W, Cs, N, kh, kw, stride, pad, fwd=False) -> bool:
         return False
     min_tiles = _CONV3_MIN_TILES_FWD[0] if fwd and _CONV3_F16[0] else _conv3_min_tiles_bwd()
     if H == 7 and W == 7:
-        return _CONV3_ROI[0] and N % 128 == 0 and B * 49 * Cs < (1 << 29) and ((B + 1) // 2) * 2 * (N // 128) >= min_tiles
+        return N % 128 == 0 and B * 49 * Cs < (1 << 29) and ((B + 1) // 2) * 2 * (N // 128) >= min_tiles
     if not (W in (16, 32, 64, 128, 256, 512, 1024) and (H * W) % 64 == 0 and H * W * Cs < (1 << 29)):
         return False
     if N % 128 == 0:
         return (B * H * W // 64) * (N // 128) >= min_tiles or conv3_split(B, H, W, Cs, N) > 1
-    if N % 64 == 0 and _CONV3_N64[0]:
+    if N % 64 == 0:
         return (H * W) % 128 == 0 and (B * H * W // 128) * (N // 64) >= 240
     return False
 
@@ -1065,13 +967,7 @@ def weight_col_l1max(owner, view=None):
 
 
 # ---- pre-split filter images for the PW form of the row-reuse kernels (csrc/conv3.hip conv3_wprep_kernel) ------------------------------
-_CONV3_PW = [os.environ.get("VBG_CONV3_PW", "1") != "0"]
 _C3PW = {"entries": [], "table": None, "host": None, "n": 0}
-
-
-def set_conv3_pw(on: bool):
-    """filters of the fp16-form 3x3 convolutions as pre-split planes streamed by LDS-DMA (on) or split inside every workgroup (off)"""
-    _CONV3_PW[0] = bool(on)
 
 
 class _C3Entry:
@@ -1121,7 +1017,7 @@ def conv3_planes(owner, w_ohwi, flip, bn=0):
     """fp16-pair plane image of the 3x3 filter `owner` (an OIHW parameter in channels_last memory, `w_ohwi` its free [O,3,3,I] view) for
     vbg_conv3x3_pw: flip = False the forward filter, True the filter of the input gradient.  Written once per weight version for ALL
     registered filters by one launch (first use: one launch for the new image).  None: no PW form for this filter."""
-    if owner is None or not _CONV3_PW[0] or not w_ohwi.is_cuda or w_ohwi.data_ptr() != owner.data_ptr():
+    if owner is None or not w_ohwi.is_cuda or w_ohwi.data_ptr() != owner.data_ptr():
         return None
     Cout, kh, kw, Cin = w_ohwi.shape
     if kh != 3 or kw != 3 or Cin % 8 != 0 or (Cout if flip else Cin) % 16 != 0:
@@ -1158,9 +1054,9 @@ def conv3x3_wflip(w_ohwi):
 
 def conv3w_ok(B, H, W, Cs, Cout, kh, kw, stride, pad) -> bool:
     """shapes the row-reuse weight-gradient kernel takes (csrc/conv3.hip): default split form, strips of at least 8 k-tiles"""
-    roi = H == 7 and W == 7 and _CONV3_ROI[0]              # region maps: four two-row chunks per image
+    roi = H == 7 and W == 7                                 # region maps: four two-row chunks per image
     if not (_CONV3[0] and _SPLIT3[0] and not _amp_generic() and kh == 3 and kw == 3 and stride == 1 and pad == 1 and (W % 16 == 0 or roi)
-            and Cs % 32 == 0 and (Cout % 128 == 0 or (_CONV3W_N64[0] and Cout % 64 == 0 and Cs % 64 == 0))
+            and Cs % 32 == 0 and (Cout % 128 == 0 or (Cout % 64 == 0 and Cs % 64 == 0))
             and (3 * W + 18) * Cs < (1 << 28)):
         return False
     strips = int(lib.vbg_conv3x3_wgrad_strips(B, H, W, Cs, Cout))
@@ -1171,8 +1067,7 @@ _CONV3W_MIN = [int(os.environ.get("VBG_CONV3W_MIN", "8"))]
 # odd multiples of 64 filters (the 64 -> 64 convolutions of the first trunk stage) on the row-reuse weight-gradient kernel's [64 x 9 x 64]
 # blocks in the fp16 form instead of the generic fp32-MFMA product: 116 -> 40 us + a 9.5 us strip reduction per layer at cfg2 (round 5;
 # until the strips were reduced in parallel -- conv3_wgrad_reduce_par_kernel -- the 256 slabs of a 9216-float4 dW took 64 us to add and
-# the generic kernel was as fast).  VBG_CONV3W_N64=0: the generic product
-_CONV3W_N64 = [os.environ.get("VBG_CONV3W_N64", "1") != "0"]
+# the generic kernel was as fast)
 
 
 def conv3x3_wgrad(dy, x, dw_ohwi, slabs=True, f16x2=False, dy_amax=None, x_amax=None):
@@ -1229,25 +1124,15 @@ def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=
 _BWD_SPLIT = 0          # backward products run with grad mode off; they are training-only, so the library may always split them
 
 
-_CONV3_F16_BWD = [os.environ.get("VBG_CONV3_F16_BWD", "1") != "0"]
-
-
-def set_conv3_f16_bwd(on: bool):
-    """input gradients of the wide 3x3 convolutions in the two-piece fp16 form, dy scaled by the power of two derived from its largest
-    magnitude (exact; csrc/conv3.hip); off: three bf16 pieces / six piece products"""
-    _CONV3_F16_BWD[0] = bool(on)
-
-
 def conv3_f16_bwd_enabled() -> bool:
-    return _CONV3[0] and _SPLIT3[0] and not _amp_generic() and _CONV3_F16[0] and _CONV3_F16_BWD[0]
+    """input and weight gradients of the wide 3x3 convolutions run the two-piece fp16 form (with the forward's), dy scaled by the power
+    of two derived from its largest magnitude (exact; csrc/conv3.hip)"""
+    return _CONV3[0] and _SPLIT3[0] and not _amp_generic() and _CONV3_F16[0]
 
 
 def conv3_f16_bwd_ok(B, H, W, Cout, Cin, kh, kw, stride, pad) -> bool:
     """will conv2d_dgrad of this convolution run the fp16 form (and want the largest magnitude of dy)?"""
-    return _CONV3_F16[0] and _CONV3_F16_BWD[0] and conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad)
-
-
-_CONV3_BN64 = [os.environ.get("VBG_CONV3_BN64", "1") != "0"]
+    return _CONV3_F16[0] and conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad)
 
 
 def conv3_late_choice(B, H, W, Cs, N):
@@ -1255,7 +1140,7 @@ def conv3_late_choice(B, H, W, Cs, N):
     64-filter tiles double the tile count: 256 channels at 32 x 32 then fill the chip with ONE workgroup per tile (no slabs, no tickets:
     37 vs 48 us with three workgroups per 128-filter tile), 512 channels at 16 x 16 take four per tile on half the slab bytes (42 vs 49 us;
     tools/conv3_bn_sweep.py)"""
-    if not (_CONV3_BN64[0] and _CONV3_PW[0] and _CONV3_SPLITK[0]) or (H == 7 and W == 7) or N % 128 or (H * W) % 128 or W >= 128 or Cs % 16:
+    if not _CONV3_SPLITK[0] or (H == 7 and W == 7) or N % 128 or (H * W) % 128 or W >= 128 or Cs % 16:
         return None
     t128 = (B * H * W // 128) * (N // 128)
     if t128 >= 240 or t128 < 4:          # (round 6: from 4 tiles on -- a single document's last stage)
@@ -1296,7 +1181,7 @@ def conv2d_dgrad(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, d
     M = B * H * W
     if conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad):
         # the input gradient of a 3x3 / s1 / p1 convolution is the same convolution of dy with the turned, channel-swapped filter
-        if _CONV3_F16[0] and _CONV3_F16_BWD[0]:
+        if _CONV3_F16[0]:
             late = conv3_late_choice(B, H, W, Cout, Cin)
             if late is not None:
                 wp = conv3_planes(w_owner, w_ohwi, True, bn=late[0])
@@ -1320,7 +1205,7 @@ def conv2d_dgrad(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, d
 
 def conv3_f16_wgrad_ok(B, H, W, Cin, Cout, kh, kw, stride, pad) -> bool:
     """will conv2d_wgrad of this convolution run the fp16 form (and want the largest magnitudes of dy and x)?"""
-    return _CONV3_F16[0] and _CONV3_F16_BWD[0] and conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad)
+    return _CONV3_F16[0] and conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad)
 
 
 def conv2d_wgrad(dy, x, dw_ohwi, stride, pad, accumulate=True, dy_amax=None, x_amax=None):
@@ -1334,7 +1219,7 @@ def conv2d_wgrad(dy, x, dw_ohwi, stride, pad, accumulate=True, dy_amax=None, x_a
     if conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad):
         if not accumulate:
             dw_ohwi.zero_()
-        if _CONV3_F16[0] and _CONV3_F16_BWD[0]:
+        if _CONV3_F16[0]:
             return conv3x3_wgrad(dy, x, dw_ohwi, f16x2=True, dy_amax=dy_amax, x_amax=x_amax)
         return conv3x3_wgrad(dy, x, dw_ohwi)
     sk = _pick_splitk(Cout, Kc, Mpix)
@@ -1479,14 +1364,6 @@ def attn_mask(meta, p, seed, sid):
     return mq, mk
 
 
-_MASK_POOL = [os.environ.get("VBG_MASK_POOL", "1") != "0"]
-
-
-def mask_pool_enabled() -> bool:
-    """attention-dropout keeps of all encoder layers of a step from ONE launch (on) or one launch per layer (off)"""
-    return _MASK_POOL[0]
-
-
 def attn_mask_layers(meta, p, seed, sid0, sid_stride, nlayers):
     """the dropout keeps of `nlayers` encoder layers of one step in ONE launch -> [(mask_q, mask_k)] per layer (views of two buffers);
     layer l draws from stream id sid0 + l * sid_stride: the same bits as attn_mask(meta, p, seed, sid0 + l * sid_stride)"""
@@ -1497,19 +1374,6 @@ def attn_mask_layers(meta, p, seed, sid0, sid_stride, nlayers):
     check(lib.vbg_attn_mask_layers(P(meta.lens), P(meta.mask_off), meta.nseq, meta.heads, meta.maxlen, float(p), seed, sid0, sid_stride, nlayers,
                                    words, P(mq), P(mk), _stream()), "vbg_attn_mask_layers")
     return [(mq[l, :meta.mask_words], mk[l, :meta.mask_words]) for l in range(nlayers)]
-
-
-_ATTN_PAIR = [os.environ.get("VBG_ATTN_PAIR", "1") != "0"]
-
-
-def set_attn_pair(on: bool):
-    """fused attention on two fp16 pieces per operand / three piece products (csrc/attn.hip FORM 1; inside an autocast region the hi pieces
-    alone, FORM 2) wherever the encoder layer runs its fp16-pair path; off: three bf16 pieces / six piece products everywhere"""
-    _ATTN_PAIR[0] = bool(on)
-
-
-def attn_pair_enabled() -> bool:
-    return _ATTN_PAIR[0]
 
 
 def attn(meta, mode, qkv: Planes, dO, out, lse, delta, masks, scale, p, kbar=None, out_planes=None, o=None, out_amax=None, out_pair=None,
@@ -1566,8 +1430,8 @@ def set_layer_entry(on: bool):
 
 
 def layer_entry_ok() -> bool:
-    """the measurement hooks time single launches and the stream-K tail needs its workspace: both stay on the per-launch path"""
-    return _LAYER_ENTRY[0] and _GEMM_PROF is None and not _STREAMK[0]
+    """the measurement hooks time single launches: they stay on the per-launch path"""
+    return _LAYER_ENTRY[0] and _GEMM_PROF is None
 
 
 def stacked_qkv(wq, wk, wv, bq, bk, bv, pair):
@@ -1747,18 +1611,13 @@ def _bn_workspace(device, C_):
     return ws
 
 
-_BN_FOLD = [os.environ.get("VBG_BN_FOLD", "1") != "0"]
 _BN_ZPOOL = {}
 
 
-def set_bn_fold(on: bool):
-    """BatchNorm finalize / affine-gradient folds inside the apply kernels' prologues (vbg_bn_apply_fold / vbg_bn_bwd_apply_fold: one
-    launch instead of two per layer and direction) or as launches of their own (off)"""
-    _BN_FOLD[0] = bool(on)
-
-
 def bn_fold_ok(C_, sync=False) -> bool:
-    return _BN_FOLD[0] and not sync and C_ % 64 == 0
+    """BatchNorm finalize / affine-gradient folds inside the apply kernels' prologues (vbg_bn_apply_fold / vbg_bn_bwd_apply_fold: one
+    launch instead of two per layer and direction)"""
+    return not sync and C_ % 64 == 0
 
 
 def bn_zero_slots(device, C_):

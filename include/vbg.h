@@ -614,6 +614,46 @@ int vbg_adamw_step(float* p, const float* g, float* m, float* v, long long n, fl
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * a16. deterministic mode (vbg.ops.set_deterministic): fixed-order forms of the float-atomic reductions (DESIGN.md
+ * "Deterministic mode").  Two launches on the same inputs return the same bits.
+ * ------------------------------------------------------------------------------------------ */
+/* out[c] (+)= sum over rows of x[r][c] in fp64, rows in fixed chunks; ws: vbg_colsum_det_ws_elems(M, N) doubles */
+long long vbg_colsum_det_ws_elems(long long M, int N);
+int vbg_colsum_det(const float* x, long long ld, long long M, int N, float* out, int accumulate, double* ws, void* stream);
+/* out[0] += sum(x) (squares = 0) or sum(x^2) (squares = 1); ws: vbg_sum_det_ws_elems() floats */
+int vbg_sum_det_ws_elems(void);
+int vbg_sum_det(const float* x, long long n, int squares, float* out_accum, float* ws, void* stream);
+/* stable ascending sort of int keys -> sorted keys and their source positions; ws: vbg_sort_i32_ws_bytes(n) bytes */
+long long vbg_sort_i32_ws_bytes(long long n);
+int vbg_sort_i32(const int* keys, long long n, int* keys_out, int* idx_out, void* ws, long long ws_bytes, void* stream);
+/* dst[key][0..C) += sum of src[perm[k]][0..C) over each run of equal sorted keys, in sorted order (keys < 0 skipped) */
+int vbg_segment_rows_add(const float* src, long long lds, const int* perm, const int* sorted_keys, long long n, int C,
+                         float* dst_accum, long long ldd, void* stream);
+/* CE backward per element: grow[i][0..ncls) = its gradient row, keys[i] = its logits row (-1: label out of range); the rows are
+ * then added by vbg_sort_i32 + vbg_segment_rows_add */
+int vbg_ce_bwd_rows(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n,
+                    const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W, float* grow, int* keys,
+                    void* stream);
+/* RoIAlign backward, one owner per feature row: RoIs added in RoI order (out <= 8, out * W * 4 <= 48 KB) */
+int vbg_roi_align_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out,
+                          float scale, float* dfeat_accum, void* stream);
+/* BatchNorm reductions: one partials row per row block (ws: vbg_bn_det_ws_rows(M, C) rows of 2C doubles, plain stores), the rows
+ * added in block order into slot row 0 of zero_slots (which must be zero) */
+int vbg_bn_det_ws_rows(long long M, int C);
+int vbg_bn_stats_det(const float* x, long long M, int C, double* ws, double* zero_slots, void* stream);
+int vbg_bn_bwd_reduce_det(const float* dy, const float* y, const float* x, long long M, int C, const float* mean,
+                          const float* invstd, int relu, double* ws, double* zero_slots, void* stream);
+/* embedding LayerNorm backward: dz_rows [ntok][hidden], part [vbg_embed_ln_bwd_det_blocks(ntok)][3][hidden] = per-block
+ * (dgamma, dbeta, dtype0) partials */
+int vbg_embed_ln_bwd_det_blocks(int ntok);
+int vbg_embed_ln_bwd_det(const float* dout, const float* xhat, const float* rstd, int ntok, int hidden, const float* gamma,
+                         float drop_p, unsigned long long seed, unsigned long long sid, float* dz_rows, float* part, void* stream);
+/* CRF backward: dtrans_part [ndoc][ntag * ntag] (zeroed: an empty document writes nothing) instead of dtrans += */
+int vbg_crf_nll_bwd_det(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
+                        int start_tag, int stop_tag, const float* alpha, const float* logz, const float* gout, float* demissions,
+                        float* dtrans_part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,9 @@ static inline int ew_grid(long long n, int block) {
 // 134 MB stem map; more blocks only add atomics): <= 16 atomics per address, and small maps (layer4: 2048 rows) still
 // spread over > 100 blocks instead of 16.
 constexpr int BN_SLOTS = 32;
-template <bool BWD>
+// STORE (deterministic mode): every row block writes its sums into its OWN row of a partials workspace with plain stores (same grid, same
+// per-lane accumulation as the atomic form); bn_det_fold_kernel then adds the rows in block order into slot row 0
+template <bool BWD, bool STORE = false>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ a, const float* __restrict__ y,
                                                         const float* __restrict__ x, long long M, int C,
                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -73,11 +75,16 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
         for (int l = 0; l < RL; ++l)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { a0[j] += sh[0][l * QB + q][j]; a1[j] += sh[1][l * QB + q][j]; }
-        double* o = out + (size_t)(blockIdx.y % BN_SLOTS) * 2 * C;
+        double* o = out + (size_t)(STORE ? blockIdx.y : blockIdx.y % BN_SLOTS) * 2 * C;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            unsafeAtomicAdd(o + cq * 4 + j, a0[j]);
-            unsafeAtomicAdd(o + C + cq * 4 + j, a1[j]);
+            if (STORE) {
+                o[cq * 4 + j] = a0[j];
+                o[C + cq * 4 + j] = a1[j];
+            } else {
+                unsafeAtomicAdd(o + cq * 4 + j, a0[j]);
+                unsafeAtomicAdd(o + C + cq * 4 + j, a1[j]);
+            }
         }
     }
 }
@@ -803,5 +810,44 @@ extern "C" int vbg_im2col(const float* x, int B, int H, int W, int C, int kh, in
     if (total == 0) return VBG_OK;
     VBG_LAUNCH(im2col_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, S_, x, B, H, W, C, kh, kw, stride, pad, Ho, Wo, Kpad,
                        out);
+    VBG_LAUNCH_RET();
+}
+
+// deterministic forms of vbg_bn_stats / vbg_bn_bwd_reduce: the default grid, one partials row per row block (plain stores), then the
+// rows added in block order into slot row 0 of the (zero) slot rows -- the consumers fold the slot rows as before
+__global__ void bn_det_fold_kernel(const double* __restrict__ ws, int nblk, int C2, double* __restrict__ slot0) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= C2) return;
+    double s = 0.0;
+    for (int k = 0; k < nblk; ++k) s += ws[(long long)k * C2 + i];
+    slot0[i] = s;
+}
+
+extern "C" int vbg_bn_det_ws_rows(long long M, int C) {
+    if (M <= 0 || C <= 0 || C % 4 != 0) return 0;
+    return cdiv(M, bn_rows_per_block(M, C));
+}
+
+extern "C" int vbg_bn_stats_det(const float* x, long long M, int C, double* ws, double* zero_slots, void* stream) {
+    VBG_CHECK_ARG(x && ws && zero_slots && M >= 0 && C > 0 && C % 4 == 0 && ALIGNED16(x));
+    VBG_CHECK_ARG(C / 4 <= 64 ? (256 % (C / 4) == 0) : (C / 4) % 64 == 0);
+    if (M == 0) return VBG_OK;
+    const int rpb = bn_rows_per_block(M, C), nblk = cdiv(M, rpb);
+    VBG_LAUNCH((bn_reduce_kernel<false, true>), dim3(cdiv(C / 4, 64), nblk), dim3(256), 0, S_, x, nullptr, nullptr, M, C, nullptr,
+               nullptr, 0, rpb, ws);
+    VBG_LAUNCH(bn_det_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, S_, ws, nblk, 2 * C, zero_slots);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_bn_bwd_reduce_det(const float* dy, const float* y, const float* x, long long M, int C, const float* mean,
+                                     const float* invstd, int relu, double* ws, double* zero_slots, void* stream) {
+    VBG_CHECK_ARG(dy && x && mean && invstd && ws && zero_slots && M >= 0 && C > 0 && (!relu || y) && C % 4 == 0);
+    VBG_CHECK_ARG(ALIGNED16(dy) && ALIGNED16(x) && ALIGNED16(mean) && ALIGNED16(invstd) && (!relu || ALIGNED16(y)));
+    VBG_CHECK_ARG(C / 4 <= 64 ? (256 % (C / 4) == 0) : (C / 4) % 64 == 0);
+    if (M == 0) return VBG_OK;
+    const int rpb = bn_rows_per_block(M, C), nblk = cdiv(M, rpb);
+    VBG_LAUNCH((bn_reduce_kernel<true, true>), dim3(cdiv(C / 4, 64), nblk), dim3(256), 0, S_, dy, y, x, M, C, mean, invstd, relu,
+               rpb, ws);
+    VBG_LAUNCH(bn_det_fold_kernel, dim3(cdiv(2 * C, 256)), dim3(256), 0, S_, ws, nblk, 2 * C, zero_slots);
     VBG_LAUNCH_RET();
 }

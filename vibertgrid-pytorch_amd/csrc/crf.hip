@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void crf_nll_bwd_kernel(const float* __restrict
                                                          const int* __restrict__ doc_off, const float* __restrict__ trans, int ntag,
                                                          int start, int stop, const float* __restrict__ alpha,
                                                          const float* __restrict__ logz, const float* __restrict__ gout,
-                                                         float* __restrict__ dem, float* dtrans) {
+                                                         float* __restrict__ dem, float* dtrans, float* dtrans_part) {
     __shared__ float beta[CRF_MAX_TAGS], nb[CRF_MAX_TAGS], prev[CRF_MAX_TAGS], tr[CRF_MAX_TAGS * CRF_MAX_TAGS];
     __shared__ float dtr[CRF_MAX_TAGS * CRF_MAX_TAGS];
     const int d = blockIdx.x, i = threadIdx.x;
@@ -109,7 +109,11 @@ __global__ __launch_bounds__(64) void crf_nll_bwd_kernel(const float* __restrict
         dtr[stop * ntag + pt] -= 1.f;
     }
     __syncthreads();
-    for (int k = i; k < ntag * ntag; k += 64) unsafeAtomicAdd(dtrans + k, g * dtr[k]);
+    if (dtrans_part) {            // deterministic mode: this document's row of the partials slab (the host adds the rows in order)
+        for (int k = i; k < ntag * ntag; k += 64) dtrans_part[(long long)d * ntag * ntag + k] = g * dtr[k];
+    } else {
+        for (int k = i; k < ntag * ntag; k += 64) unsafeAtomicAdd(dtrans + k, g * dtr[k]);
+    }
 }
 
 // Viterbi decode (model/crf.py:99-145): first maximal previous tag on ties, like torch.max
@@ -197,7 +201,18 @@ extern "C" int vbg_crf_nll_bwd(const float* emissions, const int* tags, const in
     VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_nll_bwd_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, alpha, logz,
-               gout, demissions, dtrans_accum);
+               gout, demissions, dtrans_accum, (float*)nullptr);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_crf_nll_bwd_det(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
+                                   int start_tag, int stop_tag, const float* alpha, const float* logz, const float* gout, float* demissions,
+                                   float* dtrans_part, void* stream) {
+    VBG_CHECK_ARG(emissions && tags && doc_off && trans && alpha && logz && gout && demissions && dtrans_part && ndoc >= 0);
+    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    if (ndoc == 0) return VBG_OK;
+    VBG_LAUNCH(crf_nll_bwd_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, alpha, logz,
+               gout, demissions, (float*)nullptr, dtrans_part);
     VBG_LAUNCH_RET();
 }
 

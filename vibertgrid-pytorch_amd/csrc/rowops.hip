@@ -75,6 +75,9 @@ __device__ __forceinline__ void ln_backward_row(const float (&g)[LN_MAXPER], con
 
 constexpr int LN_ROWS_PER_BLOCK = 16;
 
+// DET (deterministic mode): dz of every token goes to dword = [ntok][hidden] (the host adds the rows into the tables by sorted id) and
+// the block's (dgamma, dbeta, dtype0) partials to row blockIdx.x of dgamma = [blocks][3][hidden] (added in block order by the host)
+template <bool DET>
 __global__ __launch_bounds__(LN_THREADS) void embed_ln_bwd_kernel(
     const float* __restrict__ dout, const float* __restrict__ xhat, const float* __restrict__ rstd,
     const int* __restrict__ ids, const int* __restrict__ pos_ids, int ntok, int hidden, const float* __restrict__ gamma,
@@ -105,13 +108,17 @@ __global__ __launch_bounds__(LN_THREADS) void embed_ln_bwd_kernel(
             }
         }
         ln_backward_row(g, xh, gam, rstd[t], hidden, sh, dz);
-        const long long wid = ids[t], pid = pos_ids[t];
+        const long long wid = DET ? 0 : ids[t], pid = DET ? 0 : pos_ids[t];
 #pragma unroll
         for (int j = 0; j < LN_MAXPER; ++j) {
             const int c = threadIdx.x + j * LN_THREADS;
             if (c < hidden) {
-                unsafeAtomicAdd(dword + wid * hidden + c, dz[j]);
-                unsafeAtomicAdd(dpos + pid * hidden + c, dz[j]);
+                if (DET) {
+                    dword[(long long)t * hidden + c] = dz[j];
+                } else {
+                    unsafeAtomicAdd(dword + wid * hidden + c, dz[j]);
+                    unsafeAtomicAdd(dpos + pid * hidden + c, dz[j]);
+                }
                 at[j] += dz[j];
             }
         }
@@ -120,9 +127,14 @@ __global__ __launch_bounds__(LN_THREADS) void embed_ln_bwd_kernel(
     for (int j = 0; j < LN_MAXPER; ++j) {
         const int c = threadIdx.x + j * LN_THREADS;
         if (c < hidden) {
-            unsafeAtomicAdd(dgamma + c, ag[j]);
-            unsafeAtomicAdd(dbeta + c, ab[j]);
-            unsafeAtomicAdd(dtype0 + c, at[j]);
+            if (DET) {
+                float* part = dgamma + (long long)blockIdx.x * 3 * hidden;
+                part[c] = ag[j]; part[hidden + c] = ab[j]; part[2 * hidden + c] = at[j];
+            } else {
+                unsafeAtomicAdd(dgamma + c, ag[j]);
+                unsafeAtomicAdd(dbeta + c, ab[j]);
+                unsafeAtomicAdd(dtype0 + c, at[j]);
+            }
         }
     }
 }
@@ -670,9 +682,23 @@ extern "C" int vbg_embed_ln_bwd(const float* dout, const float* xhat, const floa
     VBG_CHECK_ARG(dout && xhat && rstd && ids && pos_ids && gamma && dword && dpos && dtype0 && dgamma && dbeta);
     VBG_CHECK_ARG(hidden > 0 && hidden <= LN_THREADS * LN_MAXPER && drop_p >= 0.f && drop_p < 1.f);
     if (ntok <= 0) return VBG_OK;
-    VBG_LAUNCH(embed_ln_bwd_kernel, dim3(cdiv(ntok, LN_ROWS_PER_BLOCK)), dim3(LN_THREADS), 0, (hipStream_t)stream,
+    VBG_LAUNCH(embed_ln_bwd_kernel<false>, dim3(cdiv(ntok, LN_ROWS_PER_BLOCK)), dim3(LN_THREADS), 0, (hipStream_t)stream,
                        dout, xhat, rstd, ids, pos_ids, ntok, hidden, gamma, drop_threshold(drop_p), 1.0f / (1.0f - drop_p),
                        seed, sid, dword, dpos, dtype0, dgamma, dbeta);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_embed_ln_bwd_det_blocks(int ntok) { return ntok > 0 ? cdiv(ntok, LN_ROWS_PER_BLOCK) : 0; }
+
+// deterministic form: dz_rows [ntok][hidden] and part [vbg_embed_ln_bwd_det_blocks(ntok)][3][hidden] (dgamma, dbeta, dtype0 partials)
+extern "C" int vbg_embed_ln_bwd_det(const float* dout, const float* xhat, const float* rstd, int ntok, int hidden, const float* gamma,
+                                    float drop_p, unsigned long long seed, unsigned long long sid, float* dz_rows, float* part, void* stream) {
+    VBG_CHECK_ARG(dout && xhat && rstd && gamma && dz_rows && part);
+    VBG_CHECK_ARG(hidden > 0 && hidden <= LN_THREADS * LN_MAXPER && drop_p >= 0.f && drop_p < 1.f);
+    if (ntok <= 0) return VBG_OK;
+    VBG_LAUNCH(embed_ln_bwd_kernel<true>, dim3(cdiv(ntok, LN_ROWS_PER_BLOCK)), dim3(LN_THREADS), 0, (hipStream_t)stream,
+                       dout, xhat, rstd, (const int*)nullptr, (const int*)nullptr, ntok, hidden, gamma, drop_threshold(drop_p),
+                       1.0f / (1.0f - drop_p), seed, sid, dz_rows, (float*)nullptr, (float*)nullptr, part, (float*)nullptr);
     VBG_LAUNCH_RET();
 }
 

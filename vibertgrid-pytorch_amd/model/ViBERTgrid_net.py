@@ -283,6 +283,7 @@ class ViBERTgridNet(nn.Module):
     def inference(self, image: Tuple[torch.Tensor], seg_indices: Tuple[torch.Tensor], coors: torch.Tensor, corpus: torch.Tensor,
                   mask: torch.Tensor):
         ops.set_amp(torch.is_autocast_enabled("cuda"))
+        ops.latch_deterministic()
         self.BERTgrid_generator.prefetch_host(corpus, mask, seg_indices)
         try:
             batch, icoors, packed, B, H, W = self._trunk(image, seg_indices, coors, corpus, mask)
@@ -338,6 +339,8 @@ class ViBERTgridNet(nn.Module):
         # `amp: True`: the caller wraps this call in torch.cuda.amp.autocast (reference pipeline/train_val_utils.py:264); the
         # matrix products of this forward AND of its backward then run on the bf16 matrix cores (see vbg.ops.set_amp)
         ops.set_amp(torch.is_autocast_enabled("cuda"))
+        # deterministic mode (vbg.ops.set_deterministic, or torch.use_deterministic_algorithms(True)): latched like autocast
+        ops.latch_deterministic()
         batch, icoors, packed, B, H, W = self._trunk(image, seg_indices, coors, corpus, mask)
         seg_head, cls_head = self.semantic_segmentation_head, self.field_type_classification_head
         if self.classifier_mode != "simp":

@@ -1273,19 +1273,21 @@ def _pin_arithmetic(cls):
     cls.apply = staticmethod(apply)
 
     def forward(ctx, *a, **k):
-        ctx._vbg_form = (ops.amp_enabled(), ops.precision())
+        ctx._vbg_form = (ops.amp_enabled(), ops.precision(), ops.deterministic_active())
         return fwd(ctx, *a, **k)
 
     def backward(ctx, *g):
-        amp, prec = ctx._vbg_form
-        prev_amp, prev_prec = ops.amp_enabled(), ops.precision()
+        amp, prec, det = ctx._vbg_form
+        prev_amp, prev_prec, prev_det = ops.amp_enabled(), ops.precision(), ops.deterministic_active()
         ops.set_amp(amp)
         ops.set_precision(prec)
+        ops._set_det_active(det)
         try:
             return bwd(ctx, *g)
         finally:
             ops.set_amp(prev_amp)
             ops.set_precision(prev_prec)
+            ops._set_det_active(prev_det)
 
     cls.forward, cls.backward = staticmethod(forward), staticmethod(backward)
 

@@ -193,6 +193,21 @@ SIGNATURES = {
     "vbg_crf_viterbi": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),
+    "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
+    "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
+    "vbg_sum_det_ws_elems": (c_int, []),
+    "vbg_sum_det": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_vp]),
+    "vbg_sort_i32_ws_bytes": (c_ll, [c_ll]),
+    "vbg_sort_i32": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp]),
+    "vbg_segment_rows_add": (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_int, c_vp, c_ll, c_vp]),
+    "vbg_ce_bwd_rows": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "vbg_roi_align_bwd_det": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp]),
+    "vbg_bn_det_ws_rows": (c_int, [c_ll, c_int]),
+    "vbg_bn_stats_det": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_vp]),
+    "vbg_bn_bwd_reduce_det": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "vbg_embed_ln_bwd_det_blocks": (c_int, [c_int]),
+    "vbg_embed_ln_bwd_det": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_f, c_ull, c_ull, c_vp, c_vp, c_vp]),
+    "vbg_crf_nll_bwd_det": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 

@@ -36,7 +36,8 @@ _SIDE = {}
 
 
 def overlap_enabled() -> bool:
-    return _OVERLAP[0]
+    """(deterministic mode: one stream -- see conv_wgrad_stream_enabled)"""
+    return _OVERLAP[0] and not _DET[0]
 
 
 def set_overlap(on: bool):
@@ -53,6 +54,11 @@ def conv_wgrad_stream_enabled(level: int = 1, pixels: int = 0) -> bool:
     """weight gradients of the conv + BatchNorm nodes on a stream of their own, beside the input gradient of the same node (level 2:
     those of the plain convolution nodes -- FPN, heads -- as well); pixels: B * H * W of the node's output (VBG_CONV_WGRAD_STREAM_MAXPIX > 0:
     only nodes with at most that many)"""
+    if _DET[0]:
+        # deterministic mode runs the step on ONE stream, whatever the stream switches say: at cfg2 the all-streams step differed from
+        # the one-stream step by 3e-4 of the CNN gradients' norm with every reduction in fixed order (DESIGN.md §7a), so placement is
+        # fixed by the mode instead of promised by it
+        return False
     if _CONV_WGRAD_STREAM_MAXPIX[0] > 0 and pixels > _CONV_WGRAD_STREAM_MAXPIX[0]:
         return False
     return int(_CONV_WGRAD_STREAM[0]) >= level
@@ -176,6 +182,14 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
         splitk = 0          # training: let the library split few-tile / long-K products; no_grad (inference, eval) stays bit-reproducible
     if splitk == 0 and accumulate:
         splitk = 1
+    if splitk == 0 or (accumulate and splitk > 1):
+        if _DET[0]:
+            splitk = 1
+            _seen("det:gemm_splitk")
+        else:
+            _seen("fatomic:gemm_splitk")
+    if stats is not None:
+        _seen("fatomic:gemm_stats")
     if accumulate:
         _untag(Cout)
     d.epi, d.alpha, d.accumulate, d.splitk, d.tile = epi, float(alpha), int(bool(accumulate)), int(splitk), int(tile)
@@ -240,6 +254,13 @@ def split_planes(x, relu=False, out=None, colsum_out=None):
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == f32
     rows, cols = x.shape
     o = out if out is not None else planes_empty(rows, cols, x.device)
+    if colsum_out is not None and _DET[0]:
+        assert not relu
+        colsum(x, out=colsum_out, accumulate=True)
+        colsum_out = None
+        _seen("det:split_colsum")
+    elif colsum_out is not None:
+        _seen("fatomic:split_colsum")
     check(lib.vbg_split_planes(P(x), x.stride(0), rows, cols, P(o.buf), o.ld, o.plane, int(relu), P(colsum_out), _stream()), "vbg_split_planes")
     return o
 
@@ -256,6 +277,12 @@ def split_planes_pair(x, out=None, amax_slot_=None, colsum_out=None):
     assert x.dim() == 2 and x.stride(1) == 1 and x.dtype == f32
     rows, cols = x.shape
     o = out if out is not None else pair_empty(rows, cols, x.device)
+    if colsum_out is not None and _DET[0]:
+        colsum(x, out=colsum_out, accumulate=True)
+        colsum_out = None
+        _seen("det:split_colsum")
+    elif colsum_out is not None:
+        _seen("fatomic:split_colsum")
     check(lib.vbg_split_planes_pair(P(x), x.stride(0), rows, cols, P(o.buf), o.ld, o.plane, P(amax_slot_), P(colsum_out), _stream()), "vbg_split_planes_pair")
     return o
 
@@ -335,6 +362,14 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
         d.M, d.N, d.K = a.rows, b.rows, _ld32(a.cols)
     d.A, d.a_plane, d.lda = a.buf.data_ptr(), a.plane, a.ld
     d.B, d.b_plane, d.ldb = b.buf.data_ptr(), b.plane, b.ld
+    det_colsum = None
+    if colsum_out is not None and _DET[0]:
+        # deterministic mode: the column sums of the stored values are taken from the stored fp32 output in a fixed order (a scratch
+        # output when the caller wants planes only)
+        det_colsum, colsum_out = colsum_out, None
+        if out is None:
+            out = torch.empty((d.M, (d.N + 3) // 4 * 4), device=a.buf.device, dtype=f32)
+            ldc = out.stride(0)
     if out is not None:
         d.C, d.ldc = out.data_ptr(), int(ldc if ldc is not None else out.stride(-2))
     else:
@@ -362,6 +397,13 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
             d.cq_ref_out = None if q_ref_out is None else q_ref_out.data_ptr()
     if colsum_out is not None:             # += column sums of the stored values (a bias gradient)
         d.colsum = colsum_out.data_ptr()
+        _seen("fatomic:plane_colsum")
+    if accumulate and int(splitk) > 1:
+        if _DET[0]:
+            d.splitk = 1
+            _seen("det:plane_splitk")
+        else:
+            _seen("fatomic:plane_splitk")
     if _DISPATCH[0] is not None:
         _seen(("plane_gemm:onep" if _AMP[0] else "plane_gemm:pair") if form else "plane_gemm:bf16x3")
         _seen(f"plane_gemm:tile{int(tile)}")
@@ -375,6 +417,9 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
         prof.add(2.0 * d.M * d.N * (a.rows if trans else a.cols), e0, e1, (1 if _AMP[0] else 3) if form else 6, ingest=ing)
         return out
     check(lib.vbg_plane_gemm(C.byref(d), _stream()), "vbg_plane_gemm")
+    if det_colsum is not None:
+        colsum(out.as_strided((d.M, d.N), (d.ldc, 1)), out=det_colsum, accumulate=True)
+        _seen("det:plane_colsum")
     return out
 
 
@@ -622,6 +667,47 @@ class amp_scope:
         _AMP[0] = self.prev
 
 
+# Deterministic mode (DESIGN.md "Deterministic mode"): every reduction that adds floats across threads takes a fixed-order form
+# (csrc/det.hip, slab / per-tile forms of the existing kernels), so two identical steps return the same bits.  _DET_USER is the
+# switch (set_deterministic, VBG_DETERMINISTIC); _DET is what the launches read: ViBERTgridNet.forward / inference latch
+# `torch.are_deterministic_algorithms_enabled() or switch` into it, and the backward of that forward sees the same setting.
+_DET_USER = [os.environ.get("VBG_DETERMINISTIC", "0") not in ("", "0")]
+_DET = [_DET_USER[0]]
+
+
+def set_deterministic(on: bool):
+    _DET_USER[0] = _DET[0] = bool(on)
+
+
+def deterministic() -> bool:
+    """what the next forward latches: the switch, or torch.use_deterministic_algorithms(True)"""
+    return _DET_USER[0] or torch.are_deterministic_algorithms_enabled()
+
+
+def deterministic_active() -> bool:
+    return _DET[0]
+
+
+def latch_deterministic():
+    _DET[0] = deterministic()
+
+
+def _set_det_active(on: bool):
+    _DET[0] = bool(on)
+
+
+class deterministic_scope:
+    def __init__(self, on=True):
+        self.on = on
+
+    def __enter__(self):
+        self.prev = (_DET_USER[0], _DET[0])
+        _DET_USER[0] = _DET[0] = bool(self.on)
+
+    def __exit__(self, *exc):
+        _DET_USER[0], _DET[0] = self.prev
+
+
 def _pick_splitk(M, N, Kred, bk=32):
     """Split the reduction of a weight-gradient GEMM so the launch has ~2048 blocks (two rounds of the 1024 resident 64x64 blocks),
     keeping >= 20 k-tiles per split (>= 16 beyond 64 splits: the atomic epilogue grows with them).  Measured on MI355X with every
@@ -703,6 +789,9 @@ def colsum(x, out=None, accumulate=False):
     if out is None:
         out = torch.empty((N,), device=x.device, dtype=f32)
         accumulate = False
+    if _DET[0]:
+        return _colsum_det(x, out, accumulate)
+    _seen("fatomic:colsum")
     key = (x.device, raw_stream(x.device))
     ws = _COLSUM_WS.get(key)
     if ws is None or ws.numel() < N:
@@ -714,6 +803,14 @@ def colsum(x, out=None, accumulate=False):
 # bias gradients that do not ride on a split pass are summed in fp64 (csrc/rowops.hip colsum_f64_*: the 1x1 segmentation classifiers'
 # bias gradients cancel to 1e-3 of their running partial sums)
 _COLSUM_WS = {}
+
+
+def _colsum_det(x, out, accumulate):
+    M, N = x.shape
+    ws = torch.empty((int(lib.vbg_colsum_det_ws_elems(M, N)),), device=x.device, dtype=torch.float64)
+    check(lib.vbg_colsum_det(P(x), x.stride(0), M, N, P(out), int(accumulate), P(ws), _stream()), "vbg_colsum_det")
+    _seen("det:colsum")
+    return out
 
 
 def conv_geo(Hs, Ws, Cs, Hr, Wr, kh, kw, stride, pad, dgrad=0):
@@ -728,7 +825,10 @@ def conv_out_hw(H, W, k, stride, pad):
 
 def fuse_stats_ok(M, N, K):
     """fuse the BatchNorm statistics into the producing GEMM unless that GEMM is one the library would rather split (few tiles, long
-    reduction: the layer4 convolutions), mirroring the rule in csrc/gemm.hip"""
+    reduction: the layer4 convolutions), mirroring the rule in csrc/gemm.hip.  Never in deterministic mode: the epilogue adds its row
+    tiles into the slot rows with atomics; bn_stats then takes its one-block-per-slot form."""
+    if _DET[0]:
+        return False
     tiles = ((M + 63) // 64) * ((N + 63) // 64)
     return N % 4 == 0 and not (tiles <= 384 and (K + 31) // 32 >= 48)
 
@@ -869,6 +969,8 @@ def conv3x3(x, w_ohwi, bias=None, out=None, stats=None, accumulate=False, f16x2=
     if _CONV3_PROF[0] is not None:           # bench.py's second roofline object: events around the launch, on the launch stream
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
+    if stats is not None:
+        _seen("fatomic:conv3_stats")
     if w_planes is not None:                 # the filter as pre-split fp16-pair planes (conv3_planes): no filter work in the kernel
         _seen("conv3:pw")
         onep = _AMP[0] and _AMP_FAST[0]       # autocast region: the hi pieces only, one product
@@ -1077,6 +1179,11 @@ def conv3x3_wgrad(dy, x, dw_ohwi, slabs=True, f16x2=False, dy_amax=None, x_amax=
     B, H, W, Cs = x.shape
     Cout = dy.shape[3]
     slab = None
+    if _DET[0] and not slabs:
+        slabs = True
+        _seen("det:conv3_wgrad")
+    elif not slabs:
+        _seen("fatomic:conv3_wgrad")
     if slabs:
         strips = int(lib.vbg_conv3x3_wgrad_strips(B, H, W, Cs, Cout))
         slab = torch.empty((strips, dw_ohwi.numel()), device=x.device, dtype=f32)
@@ -1259,6 +1366,22 @@ def embed_ln_fwd(ids, pos_ids, word, pos, type0, gamma, beta, eps, p, seed, sid)
 
 def embed_ln_bwd(dout, xhat, rstd, ids, pos_ids, gamma, p, seed, sid, dword, dpos, dtype0, dgamma, dbeta):
     ntok, hidden = xhat.shape
+    if _DET[0]:
+        # dz of every token, the per-block (dgamma, dbeta, dtype0) partials, then ordered adds: table rows by sorted id, partials by block
+        dev = xhat.device
+        dz = torch.empty((ntok, hidden), device=dev, dtype=f32)
+        part = torch.empty((max(int(lib.vbg_embed_ln_bwd_det_blocks(ntok)), 1), 3, hidden), device=dev, dtype=f32)
+        check(lib.vbg_embed_ln_bwd_det(P(dout), P(xhat), P(rstd), ntok, hidden, P(gamma), p, seed, sid, P(dz), P(part), _stream()),
+              "vbg_embed_ln_bwd_det")
+        rows_add_sorted(dz, ids, dword)
+        rows_add_sorted(dz, pos_ids, dpos)
+        if ntok > 0:
+            nb = int(lib.vbg_embed_ln_bwd_det_blocks(ntok))
+            for j, dst in enumerate((dgamma, dbeta, dtype0)):
+                colsum(part[:nb, j], out=dst.view(-1), accumulate=True)
+        _seen("det:embed_ln_bwd")
+        return
+    _seen("fatomic:embed_ln_bwd")
     check(lib.vbg_embed_ln_bwd(P(dout), P(xhat), P(rstd), P(ids), P(pos_ids), ntok, hidden, P(gamma), p, seed, sid, P(dword),
                                P(dpos), P(dtype0), P(dgamma), P(dbeta), _stream()), "vbg_embed_ln_bwd")
 
@@ -1331,7 +1454,9 @@ def dropout_add_ln_bwd(dy, xhat, rstd, gamma, p, seed, sid, dgamma, dbeta, dx_am
     rows, hidden = xhat.shape
     dx = torch.empty_like(xhat)
     dres = torch.empty_like(xhat)
-    ws = _ln_workspace(xhat.device, hidden, rows) if rows >= 512 else None
+    ws = _ln_workspace(xhat.device, hidden, rows) if (rows >= 512 or _DET[0]) else None
+    if rows < 512:
+        _seen("det:ln_bwd" if ws is not None else "fatomic:ln_bwd")
     check(lib.vbg_dropout_add_ln_bwd(P(dy), P(xhat), P(rstd), rows, hidden, P(gamma), p, seed, sid, P(dx), P(dres), P(dgamma),
                                      P(dbeta), P(ws), P(dx_amax), _stream()), "vbg_dropout_add_ln_bwd")
     return dx, dres
@@ -1665,12 +1790,23 @@ def bn_bwd_apply_fold(dy, y, x, mean, invstd, gamma, slots, count, relu, want_dr
     return dx, dres
 
 
+def _bn_det_ws(device, M, C_):
+    """partials rows of the deterministic BatchNorm reductions (every row written before it is read: uninitialised)"""
+    return torch.empty((max(int(lib.vbg_bn_det_ws_rows(M, C_)), 1) * 2 * C_,), device=device, dtype=torch.float64)
+
+
 def bn_stats(x2d, stats=None):
     """per-channel (sum, sum of squares) partials in the persistent slot workspace (MUST be consumed by bn_finalize / bn_fold next), or in
     the zeroed rows `stats`"""
     M, C_ = x2d.shape
     if stats is None:
         stats = _bn_workspace(x2d.device, C_)
+    if _DET[0]:
+        ws = _bn_det_ws(x2d.device, M, C_)
+        check(lib.vbg_bn_stats_det(P(x2d), M, C_, P(ws), P(stats), _stream()), "vbg_bn_stats_det")
+        _seen("det:bn_reduce")
+        return stats
+    _seen("fatomic:bn_reduce")
     check(lib.vbg_bn_stats(P(x2d), M, C_, P(stats), _stream()), "vbg_bn_stats")
     return stats
 
@@ -1716,6 +1852,13 @@ def bn_bwd_reduce(dy, y, x, mean, invstd, relu, sums=None):
     M, C_ = x.shape
     if sums is None:
         sums = _bn_workspace(x.device, C_)
+    if _DET[0]:
+        ws = _bn_det_ws(x.device, M, C_)
+        check(lib.vbg_bn_bwd_reduce_det(P(dy), P(y), P(x), M, C_, P(mean), P(invstd), int(relu), P(ws), P(sums), _stream()),
+              "vbg_bn_bwd_reduce_det")
+        _seen("det:bn_reduce")
+        return sums
+    _seen("fatomic:bn_reduce")
     check(lib.vbg_bn_bwd_reduce(P(dy), P(y), P(x), M, C_, P(mean), P(invstd), int(relu), P(sums), _stream()), "vbg_bn_bwd_reduce")
     return sums
 
@@ -1835,6 +1978,12 @@ def roi_align_fwd(feat, boxes, box_doc, out_size, scale):
 def roi_align_bwd(dy, feat_shape, boxes, box_doc, out_size, scale, dfeat):
     B, H, W, C_ = feat_shape
     n = boxes.shape[0]
+    if _DET[0]:
+        check(lib.vbg_roi_align_bwd_det(P(dy), B, H, W, C_, P(boxes) if n else None, P(box_doc) if n else None, n, out_size, scale, P(dfeat),
+                                        _stream()), "vbg_roi_align_bwd_det")
+        _seen("det:roi_align_bwd")
+        return
+    _seen("fatomic:roi_align_bwd")
     check(lib.vbg_roi_align_bwd(P(dy), B, H, W, C_, P(boxes) if n else None, P(box_doc) if n else None, n, out_size, scale, P(dfeat), _stream()), "vbg_roi_align_bwd")
 
 
@@ -1848,6 +1997,18 @@ def ce_fwd(logits2d, elem, labels, n, weight=None, up_shift=0, H=0, W=0):
 
 
 def ce_bwd(logits2d, elem, labels, n, weight, gscale_dev, gmul, up_shift, H, W, dlogits):
+    if _DET[0]:
+        # every element's gradient row, then the rows added into their logits rows by sorted row index (repeated picks and the
+        # up_shift upsampling land on one row in element order)
+        ncls = logits2d.shape[1]
+        grow = torch.empty((max(n, 1), ncls), device=logits2d.device, dtype=f32)
+        keys = torch.empty((max(n, 1),), device=logits2d.device, dtype=i32)
+        check(lib.vbg_ce_bwd_rows(P(logits2d), logits2d.stride(0), ncls, P(elem), P(labels), n, P(weight), P(gscale_dev), float(gmul), up_shift,
+                                  H, W, P(grow), P(keys), _stream()), "vbg_ce_bwd_rows")
+        rows_add_sorted(grow[:n], keys[:n], dlogits, ldd=logits2d.stride(0))
+        _seen("det:ce_bwd")
+        return
+    _seen("fatomic:ce_bwd")
     check(lib.vbg_ce_bwd(P(logits2d), logits2d.stride(0), logits2d.shape[1], P(elem), P(labels), n, P(weight), P(gscale_dev), float(gmul), up_shift,
                          H, W, P(dlogits), _stream()), "vbg_ce_bwd")
 
@@ -1896,7 +2057,37 @@ def gather_rows(src, idx):
     return out
 
 
+def sort_i32(keys):
+    """stable ascending sort of int32 keys -> (sorted keys, source positions)"""
+    n = keys.numel()
+    ko = torch.empty((max(n, 1),), device=keys.device, dtype=i32)
+    io = torch.empty_like(ko)
+    if n == 0:
+        return ko[:0], io[:0]
+    wsb = int(lib.vbg_sort_i32_ws_bytes(n))
+    ws = torch.empty((wsb,), device=keys.device, dtype=torch.uint8)
+    check(lib.vbg_sort_i32(P(keys), n, P(ko), P(io), P(ws), wsb, _stream()), "vbg_sort_i32")
+    return ko[:n], io[:n]
+
+
+def rows_add_sorted(src, idx, dst, ldd=None):
+    """dst[idx[r]] += src[r] in a fixed order: idx sorted stably, one owner per destination row adds its source rows in ascending r"""
+    n, C_ = src.shape
+    if n == 0:
+        return dst
+    assert idx.dtype == i32 and idx.numel() == n and src.stride(1) == 1
+    ks, perm = sort_i32(idx.contiguous().view(-1))
+    check(lib.vbg_segment_rows_add(P(src), src.stride(0), P(perm), P(ks), n, C_, P(dst), int(ldd if ldd is not None else C_), _stream()),
+          "vbg_segment_rows_add")
+    return dst
+
+
 def scatter_rows_add(src, idx, dst):
+    if _DET[0]:
+        rows_add_sorted(src, idx, dst)
+        _seen("det:scatter_rows_add")
+        return dst
+    _seen("fatomic:scatter_rows_add")
     check(lib.vbg_scatter_rows_add(P(src), P(idx), idx.numel(), src.shape[1], P(dst), _stream()), "vbg_scatter_rows_add")
     return dst
 
@@ -1916,6 +2107,15 @@ def crf_nll_fwd(em, tags, doc_off, trans, start, stop):
 def crf_nll_bwd(em, tags, doc_off, trans, start, stop, alpha, logz, gout, dtrans):
     N, ntag = em.shape
     dem = torch.empty_like(em)
+    if _DET[0]:
+        ndoc = doc_off.numel() - 1
+        part = torch.zeros((max(ndoc, 1), ntag * ntag), device=em.device, dtype=f32)
+        check(lib.vbg_crf_nll_bwd_det(P(em), P(tags), P(doc_off), ndoc, P(trans), ntag, start, stop, P(alpha), P(logz), P(gout),
+                                      P(dem), P(part), _stream()), "vbg_crf_nll_bwd_det")
+        colsum(part[:ndoc], out=dtrans.view(-1), accumulate=True)
+        _seen("det:crf_nll_bwd")
+        return dem
+    _seen("fatomic:crf_nll_bwd")
     check(lib.vbg_crf_nll_bwd(P(em), P(tags), P(doc_off), doc_off.numel() - 1, P(trans), ntag, start, stop, P(alpha), P(logz), P(gout),
                               P(dem), P(dtrans), _stream()), "vbg_crf_nll_bwd")
     return dem
@@ -1932,12 +2132,25 @@ def crf_viterbi(em, doc_off, trans, start, stop):
     return path, score
 
 
+def _sum_det(x, out, squares):
+    ws = torch.empty((int(lib.vbg_sum_det_ws_elems()),), device=x.device, dtype=f32)
+    check(lib.vbg_sum_det(P(x), x.numel(), int(squares), P(out), P(ws), _stream()), "vbg_sum_det")
+    _seen("det:sumsq" if squares else "det:sum")
+    return out
+
+
 def sum_f32(x, out):
+    if _DET[0]:
+        return _sum_det(x, out, False)
+    _seen("fatomic:sum")
     check(lib.vbg_sum_f32(P(x), x.numel(), P(out), _stream()), "vbg_sum_f32")
     return out
 
 
 def sumsq(x, out):
+    if _DET[0]:
+        return _sum_det(x, out, True)
+    _seen("fatomic:sumsq")
     check(lib.vbg_sumsq(P(x), x.numel(), P(out), _stream()), "vbg_sumsq")
     return out
 

@@ -1,5 +1,5 @@
 """The one-call encoder layer (include/vbg.h vbg_bert_layer_fwd, csrc/encoder.hip) launches the same seven kernels with the same
-descriptors as the per-launch path of vbg/functions.py BertLayerFn.forward: results must be BIT-identical in every form the layer runs
+descriptors as the per-launch path, vbg/ops.py bert_layer_launches: results must be BIT-identical in every form the layer runs
 (three bf16 planes / fp16 pairs / the one-product forms of an autocast region; with and without dropout; training and inference), and
 the entry must actually be the path taken.  Needs a real MI355X."""
 import os
@@ -147,3 +147,100 @@ def test_layer_entry_rejects_a_descriptor_without_its_operands():
     d.ntok, d.hidden, d.inter, d.heads = 128, 768, 3072, 12
     assert lib.vbg_bert_layer_fwd(C.byref(d), None) == -1          # argument error, nothing launched
     assert lib.vbg_bert_layer_fwd(None, None) == -1
+
+
+# ---- every route of BertLayerFn against HF BertModel (fp32, CPU) ----------------------------------------------------------------------
+# dense: intermediate size not a multiple of 32; planes_unfused: head width 128 (the LayerNorm kernels take hidden sizes that are multiples
+# of 256, so the hidden size cannot select the dense route); the three fused-attention routes run the homed full-net fixture
+# (route 3 with the pair form off, or with the pair forward and the bf16 backward: mixed; route 4 all-pair)
+ROUTES = ["dense", "planes_unfused", "planes_fused", "planes_fused_mixed", "pair"]
+NT = 40                 # tokens per document (one window); two documents
+
+
+def _route_tags_ok(route, grad, log):
+    fam = {k for k in log if k.startswith(("gemm:", "plane_gemm:", "attn:"))}
+    if route == "dense":
+        return bool(fam) and all(k.startswith("gemm:") for k in fam)
+    if route == "planes_unfused":
+        return any(k.startswith("plane_gemm:") for k in fam) and not any(k.startswith("attn:") for k in fam)
+    pair_fwd = route != "planes_fused"
+    attn = "attn:pair" if (route == "pair" or (pair_fwd and not grad)) else "attn:bf16x3"
+    want = {attn, "plane_gemm:pair" if pair_fwd else "plane_gemm:bf16x3"}
+    if grad:
+        want.add("plane_gemm:grouped_pair" if route == "pair" else "plane_gemm:grouped_bf16x3")
+    grouped = {k for k in fam if k.startswith("plane_gemm:grouped_")}
+    return want <= fam and grouped <= want and {k for k in fam if k.startswith("attn:")} == {attn}
+
+
+def _route_model(tmp_path, route, grad, dev):
+    """(HF BertModel on the device inside a BERTgridGenerator, optimizer or None)"""
+    from transformers import BertConfig, BertModel
+    from model.BERTgrid_generator import BERTgridGenerator
+    from vbg.optim import FusedAdamW, split_parameters
+    if route in ("dense", "planes_unfused"):
+        hidden, inter = 256, (1000 if route == "dense" else 1024)
+        torch.manual_seed(0)
+        hf = BertModel(BertConfig(vocab_size=1200, hidden_size=hidden, num_attention_heads=2, intermediate_size=inter, num_hidden_layers=LAYERS,
+                                  hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0))
+        return BERTgridGenerator(bert_model=hf, grid_mode="mean", stride=8).to(dev), None
+    net = _net(tmp_path, 0.0).to(dev)
+    opt = FusedAdamW(split_parameters(net)[1], dev, lr=0.0) if grad else None          # homed: every layer gradient sunk, Q/K/V stacked
+    return net.BERTgrid_generator, opt
+
+
+@pytest.mark.parametrize("grad", [True, False])
+@pytest.mark.parametrize("route", ROUTES)
+def test_every_layer_route_vs_hf_bert(tmp_path, route, grad):
+    from transformers import BertModel
+    from vbg import ops
+    dev = torch.device("cuda")
+    gen, opt = _route_model(tmp_path, route, grad, dev)
+    gen.train(grad)
+    g = torch.Generator().manual_seed(3)
+    corpus = torch.randint(1000, 1200, (2, NT), generator=g)
+    mask = torch.ones_like(corpus)
+    segs = tuple(torch.arange(NT, dtype=torch.int32) for _ in range(2))          # one segment per token: the mean is the token state
+    R = torch.randn(2 * NT, gen.model.config.hidden_size, generator=g)
+    was_bwd = ops._PAIR_BWD[0]
+    ops.set_pair(route != "planes_fused", force=route in ("planes_fused_mixed", "pair"))
+    ops._PAIR_BWD[0] = route != "planes_fused_mixed"
+    try:
+        if opt is not None:
+            opt.zero_grad()
+        log = ops.dispatch_log(True)
+        with torch.set_grad_enabled(grad):
+            got = torch.cat(gen.BERT_embedding(corpus.to(dev), mask.to(dev), tuple(s.to(dev) for s in segs)), 0)
+            if grad:
+                (got * R.to(dev)).sum().backward()
+        torch.cuda.synchronize()
+        ops.dispatch_log(False)
+    finally:
+        ops.dispatch_log(False); ops.set_pair(True, force=False); ops._PAIR_BWD[0] = was_bwd
+    assert _route_tags_ok(route, grad, log), (route, grad, log)
+
+    ref = BertModel(gen.model.config)
+    ref.load_state_dict({k: v.detach().cpu() for k, v in gen.model.state_dict().items()}, strict=False)
+    ref.train(False)
+    ids = torch.cat([torch.full((2, 1), 101), corpus, torch.full((2, 1), 102)], 1)
+    with torch.set_grad_enabled(grad):
+        want = ref(input_ids=ids, attention_mask=torch.ones_like(ids), token_type_ids=torch.zeros_like(ids)).last_hidden_state[:, 1:-1]
+        want = want.reshape(2 * NT, -1)
+        if grad:
+            (want * R).sum().backward()
+    err = float((got.detach().cpu() - want.detach()).abs().max())
+    print(f"{route} grad={grad}: output max abs err {err:.3e}")
+    assert torch.allclose(got.detach().cpu(), want.detach(), rtol=2e-4, atol=2e-5), err
+    if not grad:
+        return
+    worst, bad = 0.0, []
+    mine = dict(gen.model.named_parameters())
+    for name, p in ref.named_parameters():
+        if p.grad is None or name.endswith("key.bias"):          # (key.bias: an analytically zero gradient, rounding noise on both sides)
+            continue
+        a, b = mine[name].grad.detach().cpu().double(), p.grad.double()
+        rel = float((a - b).norm() / (b.norm() + 1e-30))
+        worst = max(worst, rel)
+        if rel > 1e-3:
+            bad.append((name, rel))
+    print(f"{route}: worst parameter gradient rel L2 err {worst:.3e}")
+    assert not bad, bad

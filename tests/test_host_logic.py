@@ -104,7 +104,7 @@ def test_dispatch_predicates():
         ops.set_pair(True, force=False)
     ops.set_pair(False)
     try:
-        assert not ops.pair_enabled() and not ops.pair_bwd_enabled()
+        assert not ops.pair_enabled()           # (and with it the pair backward: test_layer_route_table)
     finally:
         ops.set_pair(True)
     # an autocast region keeps the fast paths (their one-product forms) unless VBG_AMP_FAST=0 / set_amp_fast(False) hands every product
@@ -120,6 +120,70 @@ def test_dispatch_predicates():
         finally:
             ops.set_amp_fast(True)
     assert not ops.amp_enabled() and ops.pair_enabled()
+
+
+BERT_BASE = (768, 3072, 64, 512)          # hidden, intermediate, head width, longest window
+# (switches, _layer_route(hidden, inter, dh, maxlen, ntok, grad, qkv_fused, sunk, carrier), the route fields expected; pair_bwd_enabled:
+# what ops.pair_bwd_enabled() says under the switches)
+ROUTE_TABLE = [
+    # route 4, all-pair: batch 8 at cfg2, homed parameters; the layers above get the pair planes alone
+    ({}, BERT_BASE + (4128, True, True, True, None),
+     dict(planes=True, flash=True, pair=True, pair_bwd=True, one_qkv=True, pair_qkv=True, split_xq=True, px=False, attn_pair=True,
+          ao_pair=False, keep3=False, entry=True, pair_bwd_enabled=True)),
+    ({}, BERT_BASE + (4128, True, True, True, "pair"), dict(pair_bwd=True, pair_qkv=True, split_xq=False, px=False)),
+    ({"amp": True}, BERT_BASE + (4128, True, True, True, None), dict(pair_bwd=True, ao_pair=True)),
+    # route 3, mixed: pair forward, bf16 backward -- VBG_PAIR_BWD=0, or parameters not in flat storage
+    ({"pair_bwd": False}, BERT_BASE + (4128, True, True, True, "bf16+pair"),
+     dict(flash=True, pair=True, pair_bwd=False, pair_qkv=True, split_xq=False, px=True, attn_pair=False, keep3=True, pair_bwd_enabled=False)),
+    ({}, BERT_BASE + (4128, True, True, False, None), dict(flash=True, pair=True, pair_bwd=False, pair_qkv=False, px=True, keep3=True)),
+    # route 3: the pair form off
+    ({"pair": False}, BERT_BASE + (4128, True, True, True, "bf16"),
+     dict(planes=True, flash=True, pair=False, pair_bwd=False, pair_qkv=False, px=True, attn_pair=False, keep3=True, entry=True,
+          pair_bwd_enabled=False)),
+    # a single document is below the pair form's tiles ... unless there is nothing to differentiate (stacked planes cached on the weights)
+    ({}, BERT_BASE + (516, True, True, True, None), dict(flash=True, pair=False, pair_bwd=False, px=True)),
+    ({}, BERT_BASE + (516, False, False, False, None),
+     dict(pair=True, pair_bwd=False, one_qkv=True, pair_qkv=True, split_xq=True, px=False, attn_pair=True, keep3=False, entry=True)),
+    # parameters not back to back in training: one product per projection, per launch
+    ({}, BERT_BASE + (4128, True, False, False, "bf16+pair"), dict(pair=True, one_qkv=False, pair_qkv=False, px=True, entry=False)),
+    # route 2: head width other than 64, or windows longer than 512
+    ({}, (768, 3072, 128, 512, 4128, True, True, True, None), dict(planes=True, flash=False, pair_bwd=False, attn_pair=False, entry=False)),
+    ({}, (768, 3072, 64, 600, 4128, True, True, True, None), dict(planes=True, flash=False, pair_bwd=False, entry=False)),
+    # route 1: an intermediate size that is not a multiple of 32, fp32 precision, or autocast with the fast forms off
+    ({}, (256, 1000, 64, 512, 4128, True, True, True, None), dict(planes=False, flash=False, pair=False, pair_bwd=False, px=False, entry=False)),
+    ({"precision": "fp32"}, BERT_BASE + (4128, True, True, True, None), dict(planes=False, flash=False, pair=False, pair_bwd=False)),
+    ({"amp": True, "amp_fast": False}, BERT_BASE + (4128, True, True, True, None), dict(planes=False, pair=False, pair_bwd_enabled=False)),
+    # the measurement hooks time single launches
+    ({"entry": False}, BERT_BASE + (4128, True, True, True, None), dict(pair_bwd=True, entry=False)),
+]
+
+
+@pytest.mark.parametrize("switches,args,want", ROUTE_TABLE)
+def test_layer_route_table(switches, args, want):
+    from vbg import functions as Fn, ops
+    cells = (ops._PAIR, ops._PAIR_BWD, ops._AMP, ops._AMP_FAST, ops._SPLIT3, ops._LAYER_ENTRY)
+    saved = [c[0] for c in cells]
+    try:
+        ops._PAIR[0], ops._PAIR_BWD[0] = switches.get("pair", True), switches.get("pair_bwd", True)
+        ops._AMP[0], ops._AMP_FAST[0] = switches.get("amp", False), switches.get("amp_fast", True)
+        ops._SPLIT3[0], ops._LAYER_ENTRY[0] = switches.get("precision", "split") == "split", switches.get("entry", True)
+        r = Fn._layer_route(*args)
+        got = dict(r._asdict(), pair_bwd_enabled=ops.pair_bwd_enabled())
+        assert {k: got[k] for k in want} == want, (switches, args)
+        assert r.grad == args[5] and r == Fn._layer_route(*args)          # (pure: the same inputs, the same record)
+    finally:
+        for c, v in zip(cells, saved):
+            c[0] = v
+
+
+def test_layer_route_refuses_pair_planes_without_the_pair_form():
+    from vbg import functions as Fn, ops
+    ops.set_pair(False)
+    try:
+        with pytest.raises(AssertionError):
+            Fn._layer_route(*BERT_BASE, 4128, True, True, True, "pair")
+    finally:
+        ops.set_pair(True)
 
 
 def test_reducer_refuses_a_subgroup_without_a_syncbn_group():

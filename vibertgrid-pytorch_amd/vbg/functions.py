@@ -3,11 +3,14 @@
 
 Layout conventions: activations NHWC fp32 contiguous; conv weights are the reference's OIHW parameters
 held in channels_last memory, i.e. physically [Cout, kh, kw, Cin] (`ohwi()` is a free view)."""
+from types import SimpleNamespace
+from typing import NamedTuple
+
 import torch
 import torch.distributed as dist
 
 from . import ops
-from .lib import ATTN_DKV, ATTN_DQ, ATTN_FWD, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_DENSE_K, OP_DENSE_R
+from .lib import ATTN_DKV, ATTN_DQ, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_DENSE_K, OP_DENSE_R
 
 f32 = torch.float32
 
@@ -649,6 +652,109 @@ class AttnMeta:
                  "mask_pool")
 
 
+class _LayerRoute(NamedTuple):
+    """How one encoder layer runs (_layer_route): BertLayerFn.forward decides it once, stores it on ctx, and backward dispatches on it."""
+    planes: bool        # products on pre-split planes (csrc/gemm_planes.hip); False: route 1, the generic GEMMs
+    flash: bool         # fused attention (csrc/attn.hip); False: grouped score / P V products and the row softmax
+    pair: bool          # forward QKV / FFN products on two fp16 pieces per operand (csrc/gemm_planes.hip FORM 1)
+    pair_bwd: bool      # the all-pair backward (route 4)
+    one_qkv: bool       # one product over the stacked Q/K/V projections, else one per projection
+    pair_qkv: bool      # ... on the fp16-pair planes of x
+    split_xq: bool      # those pair planes are split here (the layer below did not hand them on)
+    px: bool            # the bf16 planes of x are needed: the QKV product's operand without the pair form, and its weight gradient's
+    attn_pair: bool     # q / k / v leave the projection as fp16-pair planes, the attention runs the pair form
+    ao_pair: bool       # the attention-output projection runs the pair form (autocast region, all-pair path)
+    keep3: bool         # the bf16 planes of x1 / gelu(h) / y are written: operands of the six-product backward
+    entry: bool         # the forward leaves from ONE library call (ops.bert_layer_fwd), else ops.bert_layer_launches
+    grad: bool
+
+    @property
+    def saved(self):
+        return ("pair" if self.pair_bwd else "fused" if self.flash else "unfused") if self.planes else "dense"
+
+
+def _layer_route(hid, inter, dh, maxlen, ntok, grad, qkv_fused, sunk, carrier) -> _LayerRoute:
+    """qkv_fused: the Q/K/V weights and biases are stored back to back; sunk: every weight / bias gradient of the layer goes into the flat
+    buffers; carrier: what came with x from the layer below -- None, "bf16" (its bf16 planes), "bf16+pair" (and its fp16-pair planes) or
+    "pair" (the fp16-pair planes alone: the layer below ran the all-pair path)."""
+    planes = ops.planes_enabled() and hid % 32 == 0 and inter % 32 == 0
+    flash = ops.flash_ok(hid, inter, dh, maxlen)
+    # forward products whose operands are LayerNorm / GELU outputs and weights run on two fp16 pieces per operand once the problem fills
+    # the 8-wave tiles (round 6: or when there is nothing to differentiate -- inference, validation: the form runs on the 64 x 64 tile)
+    pair = planes and ops.pair_enabled() and (ops.pair_tile(ntok, hid) != 0 or not grad)
+    assert carrier != "pair" or pair, "pair planes handed to a layer that does not run the pair form"
+    # all-pair path: the backward products run on two fp16 pieces as well (needs every weight / bias gradient of the layer sunk into the
+    # flat buffers, the stacked Q/K/V layout and the fused attention); the activations saved for backward are pair planes
+    pair_bwd = pair and ops.pair_bwd_enabled() and qkv_fused and flash and grad and sunk
+    split_xq = (pair_bwd or (pair and not grad)) and carrier not in ("pair", "bf16+pair")
+    # parameters NOT stored back to back and nothing to differentiate: the stacked planes of the three projections are cached on the
+    # weights (round 6) -- one Q/K/V product as in training
+    one_qkv = qkv_fused or (planes and not grad)
+    pair_qkv = one_qkv and (split_xq or (pair and carrier in ("pair", "bf16+pair")))
+    return _LayerRoute(planes=planes, flash=flash, pair=pair, pair_bwd=pair_bwd, one_qkv=one_qkv, pair_qkv=pair_qkv, split_xq=split_xq,
+                       px=planes and not pair_bwd and not (pair_qkv and not grad), attn_pair=flash and pair_qkv and (pair_bwd or not grad),
+                       ao_pair=pair_bwd and ops.amp_one_product(), keep3=not pair_bwd and not (pair and not grad),
+                       entry=flash and one_qkv and ops.layer_entry_ok(), grad=grad)
+
+
+# what forward saves for backward, per _LayerRoute.saved (planes are saved as their buffers)
+_SAVED_ALL = ("wq", "wk", "wv", "wo", "g1", "wi", "wo2", "g2", "xh1", "rs1", "h", "xh2", "rs2")
+_SAVED = {"dense": _SAVED_ALL + ("x", "qkv", "P", "ctxv", "x1", "g"),
+          "unfused": _SAVED_ALL + ("qkv", "P", "px", "pctx", "px1", "pg"),
+          "fused": _SAVED_ALL + ("pqkv", "ctxv", "px", "pctx", "px1", "pg", "lse", "kbar"),
+          "pair": _SAVED_ALL + ("pqkv", "ctxv", "xq", "px1q", "pgq", "lse", "kbar", "pctxq")}
+
+
+def _save(ctx, **t):
+    ctx.save_for_backward(*(t[n].buf if isinstance(t[n], ops.Planes) else t[n] for n in _SAVED[ctx.route.saved]))
+
+
+def _grads(dx, qkv=(None,) * 6, dwo=None, dbo=None, dg1=None, db1=None, dwi=None, dbi=None, dwo2=None, dbo2=None, dg2=None, db2=None):
+    """the 23 gradient slots of BertLayerFn.forward's inputs; qkv: (dq, dbq, dk, dbk, dv, dbv)"""
+    return (dx, None, *qkv, dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2, None, None, None, None, None)
+
+
+def _qkv_sunk(ctx, wq, wk, wv):
+    """(gradient destinations of the Q/K/V weights and biases, whether ONE stacked product serves all three: weights and sunk
+    gradients back to back)"""
+    gq = [wgrad_dest(t) for t in ctx.w_refs[:3] + ctx.b_refs[:3]]
+    return gq, (_back_to_back(wq, wk, wv) and all(t is not None for t in gq) and _back_to_back(*gq[:3]) and _back_to_back(*gq[3:]))
+
+
+def _qkv_tail(ctx, sunk, dqkv, wgrad, dgrad=None):
+    """the Q/K/V parameter gradients once d(qkv) [ntok, 3*hidden] is known.  sunk: the stacked products wrote them, they are only marked
+    done.  Else per projection j: wgrad(j, weight, d(qkv) block) -> weight gradient, the bias column sums, then dgrad(d(qkv) block, j)
+    when the data gradient is still to add.  -> (dq, dbq, dk, dbk, dv, dbv)"""
+    refs = ctx.w_refs[:3] + ctx.b_refs[:3]
+    if sunk:
+        for t in refs:
+            wgrad_done(t)
+        return (None,) * 6
+    hid = dqkv.shape[1] // 3
+    out = []
+    for j in range(3):
+        dj = dqkv[:, j * hid:(j + 1) * hid]
+        out += [wgrad(j, refs[j], dj), _bias_grad(refs[3 + j], dj)]
+        if dgrad is not None:
+            dgrad(dj, j)
+    return out
+
+
+def _ln_bwd_planes(dy, xhat, rstd, gamma, p, seed, sid, rg, rb, rbias):
+    """LayerNorm (+ dropout, residual) backward of the plane path -> (planes of the gradient of the product in front, dx, dgamma, dbeta,
+    that product's bias gradient).  A sunk bias gradient: the gradient leaves the kernel as planes, its column sums as the bias gradient"""
+    dg, db, sunk = _affine_dest(rg, rb)
+    dst = wgrad_dest(rbias)
+    if dst is not None:
+        pd, dx = ops.dropout_add_ln_bwd_planes(dy, xhat, rstd, gamma, p, seed, sid, dg, db, dst)
+        wgrad_done(rbias)
+        return (pd, dx) + _affine_done(rg, rb, dg, db, sunk) + (None,)
+    d, dx = ops.dropout_add_ln_bwd(dy, xhat, rstd, gamma, p, seed, sid, dg, db)
+    dg, db = _affine_done(rg, rb, dg, db, sunk)
+    pd, dbias = _split_with_bias_grad(rbias, d)
+    return pd, dx, dg, db, dbias
+
+
 class BertLayerFn(torch.autograd.Function):
     """One transformer encoder layer over packed tokens [ntok, hidden] (HF BertLayer: self-attention,
     out-proj + dropout + residual LN, FFN(GELU erf) + dropout + residual LN)."""
@@ -659,211 +765,126 @@ class BertLayerFn(torch.autograd.Function):
         or None): the LayerNorm that ends the layer splits its output for the next layer's first product."""
         x = _c(x)
         ntok, hid = x.shape
-        H, dh = meta.heads, meta.dh
+        inter = wi.shape[0]
         dev = x.device
         ctx.side_ok = SIDE_OK[0]            # (this forward runs on the encoder's side stream: the graph holds the node that joins the streams)
+        grad = any(ctx.needs_input_grad)
         fused_qkv = _back_to_back(wq, wk, wv) and _back_to_back(bq, bk, bv)
-        planes = ops.planes_enabled() and hid % 32 == 0 and wi.shape[0] % 32 == 0
-        flash = ops.flash_ok(hid, wi.shape[0], dh, meta.maxlen)
-        px = pctx = px1 = pg = pqkv = qkv = P = lse = masks = kbar = None
-        if not flash:
-            qkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
-        # forward products whose operands are LayerNorm / GELU outputs and weights run on two fp16 pieces per operand (three piece
-        # products, csrc/gemm_planes.hip FORM 1) once the problem fills the 8-wave tiles; the pair planes of x arrive as an attribute of
-        # the previous layer's bf16 planes (written by its closing LayerNorm)
-        # (round 6: nothing to differentiate -- inference, validation -- and a problem below the 8-wave tiles: the form runs on the 64 x 64 tile,
-        #  half the matrix-core work of the six-product form that single documents used to take)
-        nograd = not any(ctx.needs_input_grad)
-        pair = planes and ops.pair_enabled() and (ops.pair_tile(ntok, hid) != 0 or nograd)
-        ptile = lambda n, wide=False: ops.pair_tile(ntok, n, wide) or 64004          # (four LDS stages: the weights of a lone document come from HBM)
-        carrier_is_pair = xpl is not None and xpl.shape[0] == 2          # (the previous layer ran the all-pair path: xpl ARE the pair planes)
-        xq = (ops.Planes(xpl, ntok, hid, xpl.shape[2]) if carrier_is_pair else getattr(xpl, "_vbg_pair", None)) if (pair and xpl is not None) else None
-        # all-pair path: the backward products run on two fp16 pieces as well (needs every weight / bias gradient of the layer sunk into
-        # the flat buffers, the stacked Q/K/V layout and the fused attention), and so does the attention-output projection; the
-        # activations saved for backward are pair planes, no bf16 planes of x1 / gelu(h) / y / ctx are written at all
-        # (pair_bwd implies flash -- pair implies the plane shapes --, one_qkv and, below, xq: its q / k / v are always pair planes)
-        pair_bwd = (pair and ops.pair_bwd_enabled() and fused_qkv and dh == 64 and meta.maxlen <= 512
-                    and any(ctx.needs_input_grad)
-                    and all(sinks(t) for t in (wq, wk, wv, bq, bk, bv, wo, bo, wi, bi, wo2, bo2)))
-        assert not carrier_is_pair or pair, "pair planes handed to a layer that does not run the pair form"
-        if (pair_bwd or (pair and nograd)) and xq is None:
-            xq = ops.split_planes_pair(x)
-        # q, k, v leave the projection as planes only (the fused attention kernels' operands): fp16-pair planes when the projection runs
-        # the pair form and the backward that follows is the all-pair one (round 5: the attention then runs three fp16 piece products per
-        # product, csrc/attn.hip FORM 1), three bf16 planes otherwise
-        # parameters NOT stored back to back and nothing to differentiate (inference, validation): the stacked planes of the three
-        # projections are cached on the weights (round 6) -- one Q/K/V product as in training instead of three
-        one_qkv = fused_qkv or (planes and nograd)
-        attn_pair = flash and pair and one_qkv and xq is not None and (pair_bwd or nograd)
-        # round 6: the layer's seven launches leave from ONE library call (csrc/encoder.hip) -- same descriptors, a third of the host time
-        fast = planes and flash and one_qkv and ops.layer_entry_ok()
-        if flash:
-            pqkv = ops.pair_empty(ntok, 3 * hid, dev) if attn_pair else ops.planes_empty(ntok, 3 * hid, dev)
-        if planes:                 # operands split into bf16 planes once (csrc/gemm_planes.hip), weights once per optimizer step
-            if not pair_bwd and not (one_qkv and xq is not None and not any(ctx.needs_input_grad)):
-                # (the bf16 planes of x: the QKV product's operand without the pair form, and its weight gradient's)
-                px = ops.Planes(xpl, ntok, hid, xpl.shape[2]) if (xpl is not None and not carrier_is_pair) else ops.split_planes(x)
-            if one_qkv:
-                if fused_qkv:
-                    wqkv_pl, bqkv_t = ops.weight_planes(wq, view=_stack3(wq), also=(wk, wv), pair=xq is not None), _stack3(bq)
-                else:
-                    wqkv_pl, bqkv_t = ops.stacked_qkv(wq, wk, wv, bq, bk, bv, pair=xq is not None)
-                tile_qkv = ptile(3 * hid) if xq is not None else ops._dense_tile(ntok, 3 * hid)
-            if fast:
-                pass
-            elif one_qkv and xq is not None:
-                ops.plane_gemm(xq, wqkv_pl, qkv, bias=bqkv_t,
-                               out_planes=None if attn_pair else pqkv, out_pair=pqkv if attn_pair else None, tile=tile_qkv, form=1)
-            elif one_qkv:
-                ops.plane_gemm(px, wqkv_pl, qkv, bias=bqkv_t, out_planes=pqkv, tile=tile_qkv)
-            else:              # parameters not laid out back to back (no flat buffers): one product per projection, same kernel
-                for j, (w, b) in enumerate(((wq, bq), (wk, bk), (wv, bv))):
-                    ops.plane_gemm(px, ops.weight_planes(w), None if flash else qkv[:, j * hid:(j + 1) * hid], bias=b,
-                                   out_planes=pqkv.col_block(j * hid, hid) if flash else None, tile=ops._dense_tile(ntok, hid))
-        elif fused_qkv:            # one [ntok,hid] x [3*hid,hid]^T GEMM over the stacked projections
-            ops.linear_fwd(x, _stack3(wq), _stack3(bq), out=qkv)
-        else:
-            for j, (w, b) in enumerate(((wq, bq), (wk, bk), (wv, bv))):
-                ops.gemm_raw(ntok, hid, hid, x, hid, OP_DENSE_K, w, hid, OP_DENSE_K, qkv, 3 * hid, bias=b, c_ptr_off=j * hid)
+        sunk = grad and all(sinks(t) for t in (wq, wk, wv, bq, bk, bv, wo, bo, wi, bi, wo2, bo2))
+        # (the pair planes of x arrive as an attribute of the previous layer's bf16 planes, or alone after an all-pair layer)
+        carrier = None if xpl is None else "pair" if xpl.shape[0] == 2 else "bf16+pair" if hasattr(xpl, "_vbg_pair") else "bf16"
+        r = _layer_route(hid, inter, meta.dh, meta.maxlen, ntok, grad, fused_qkv, sunk, carrier)
         sid = layer * 8
+        ctx.route, ctx.meta, ctx.cfg = r, meta, (eps, p, seed, sid)
+        ctx.w_refs = (wq, wk, wv, wo, wi, wo2)
+        ctx.b_refs = (bq, bk, bv, bo, bi, bo2, g1, b1, g2, b2)
         ctxv = torch.empty((ntok, hid), device=dev, dtype=f32)
-        if flash:
-            # fused attention (csrc/attn.hip): scores, softmax, dropout and P V in one pass, nothing of size L x L is stored
+        qkv = P = None
+        if not r.flash:
+            qkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
+            P = torch.empty((meta.s_elems,), device=dev, dtype=f32)
+        if not r.planes:
+            if fused_qkv:            # one [ntok,hid] x [3*hid,hid]^T GEMM over the stacked projections
+                ops.linear_fwd(x, _stack3(wq), _stack3(bq), out=qkv)
+            else:
+                for j, (w, b) in enumerate(((wq, bq), (wk, bk), (wv, bv))):
+                    ops.gemm_raw(ntok, hid, hid, x, hid, OP_DENSE_K, w, hid, OP_DENSE_K, qkv, 3 * hid, bias=b, c_ptr_off=j * hid)
+            ops.attn_unfused_fwd(meta, qkv, P, ctxv, p, seed, sid)
+            ao = ops.linear_fwd(ctxv, wo, bo)
+            x1, xh1, rs1 = ops.dropout_add_ln_fwd(ao, x, g1, b1, eps, p, seed, sid + 1)
+            h, g = ops.linear_fwd(x1, wi, bi, EPI_GELU_DUAL)
+            fo = ops.linear_fwd(g, wo2, bo2)
+            y, xh2, rs2 = ops.dropout_add_ln_fwd(fo, x1, g2, b2, eps, p, seed, sid + 2)
+            if grad:
+                _save(ctx, x=x, wq=wq, wk=wk, wv=wv, wo=wo, g1=g1, wi=wi, wo2=wo2, g2=g2, qkv=qkv, P=P, ctxv=ctxv, xh1=xh1, rs1=rs1, x1=x1,
+                      h=h, g=g, xh2=xh2, rs2=rs2)
+            return y, None
+        # operands split into planes once (csrc/gemm_planes.hip), weights once per optimizer step
+        ptile = lambda n, wide=False: ops.pair_tile(ntok, n, wide) or 64004          # (four LDS stages: the weights of a lone document come from HBM)
+        carried = ops.Planes(xpl, ntok, hid, xpl.shape[2]) if xpl is not None else None
+        xq = (ops.split_planes_pair(x) if r.split_xq else carried if carrier == "pair" else xpl._vbg_pair) if r.pair_qkv else None
+        px = (carried if carrier in ("bf16", "bf16+pair") else ops.split_planes(x)) if r.px else None
+        if not r.one_qkv:          # parameters not laid out back to back (no flat buffers): one product per projection, same kernel
+            wqkv, bqkv, tile_qkv = tuple(ops.weight_planes(w) for w in (wq, wk, wv)), (bq, bk, bv), ops._dense_tile(ntok, hid)
+        else:
+            if fused_qkv:
+                wqkv, bqkv = ops.weight_planes(wq, view=_stack3(wq), also=(wk, wv), pair=r.pair_qkv), _stack3(bq)
+            else:
+                wqkv, bqkv = ops.stacked_qkv(wq, wk, wv, bq, bk, bv, pair=r.pair_qkv)
+            tile_qkv = ptile(3 * hid) if r.pair_qkv else ops._dense_tile(ntok, 3 * hid)
+        pqkv = lse = masks = kbar = pctxq = None
+        if r.flash:
+            # q, k, v leave the projection as planes only (the fused attention kernels' operands): fp16-pair planes when the attention
+            # runs the pair form (csrc/attn.hip FORM 1), three bf16 planes otherwise.  Nothing of size L x L is stored.
+            pqkv = (ops.pair_empty if r.attn_pair else ops.planes_empty)(ntok, 3 * hid, dev)
             # row statistics (m, 1 / l) and, in backward, delta: zero in the padding rows; one zeroed pool per step for all layers
             pool = getattr(meta, "stat_pool", None)
-            st = pool[layer] if pool is not None and layer < pool.shape[0] else torch.zeros((3, H, meta.ntok_pad), device=dev, dtype=f32)
+            st = pool[layer] if pool is not None and layer < pool.shape[0] else torch.zeros((3, meta.heads, meta.ntok_pad), device=dev, dtype=f32)
             lse = st[:2]
             ctx.delta_buf = st[2]
             # (the keeps of every layer of the step were drawn by ONE launch in front of the encoder when the generator could: mask_pool)
             mpool = getattr(meta, "mask_pool", None)
             masks = (mpool[layer] if (mpool is not None and layer < len(mpool)) else ops.attn_mask(meta, p, seed, sid + 0)) if p > 0 else None
-            kbar = torch.empty((ntok, hid), device=dev, dtype=f32) if any(ctx.needs_input_grad) else None
-            # (all-pair backward: O also as fp16-pair planes -- the B operand of the output projection's weight gradient, saved instead of
-            #  the split pass the backward used to run over the fp32 O)
-            pctxq = ops.pair_empty(ntok, hid, dev) if (pair_bwd and any(ctx.needs_input_grad)) else None
-            # (autocast region: the output projection multiplies the hi plane of those, no bf16 planes of O are written)
-            amp_ao = pctxq is not None and ops.amp_one_product()
-            pctx = None if amp_ao else ops.planes_empty(ntok, hid, dev)
-            if not fast:
-                ops.attn(meta, ATTN_FWD, pqkv, None, ctxv, lse, None, masks, 1.0 / (dh ** 0.5), p, kbar=kbar, out_planes=pctx, out_pair=pctxq)
+            kbar = torch.empty((ntok, hid), device=dev, dtype=f32) if grad else None
+            # (all-pair backward: O also as fp16-pair planes -- the B operand of the output projection's weight gradient)
+            pctxq = ops.pair_empty(ntok, hid, dev) if r.pair_bwd else None
+        # (the attention-output projection stays on the six-product form, its operand's bf16 planes come from the attention kernel:
+        #  measured at full scale, moving it to the pair form as well raised the gradient error of the ill-conditioned trunk
+        #  convolutions from 6.3e-4 to 1.0e-3 of the reference -- the forward feeds everything; the backward products do not.
+        #  An autocast region multiplies the hi plane of the pair planes of O: no bf16 planes of O are written)
+        pctx = None if r.ao_pair else ops.planes_empty(ntok, hid, dev)
+        if r.ao_pair:
+            wo_pl, tile_ao = ops.weight_planes(wo, pair=True), ops.pair_tile(ntok, hid) or 128129
         else:
-            # scores -> probabilities (in place), grouped over (sequence, head)
-            P = torch.empty((meta.s_elems,), device=dev, dtype=f32)
-            ops.gemm_raw(0, 0, 0, qkv, 3 * hid, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_K, P, meta.ld, grp=meta.t_qk, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, meta.maxlen), b_ptr_off=hid, bk=16 if dh <= 128 else 0, tile=64064 if dh <= 128 else 0)
-            ops.softmax_fwd(P, meta.soff, meta.lens, meta.ldp, meta.ngroups, H, meta.maxlen, 1.0 / (dh ** 0.5), p, seed, sid + 0)
-            ops.gemm_raw(0, 0, 0, P, meta.ld, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_R, ctxv, hid, grp=meta.t_pv, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, dh), b_ptr_off=2 * hid, a_relu_scale=1.0 / (1.0 - p))
-        py = None
-        if planes:
-            # (the attention-output projection stays on the six-product form, its operand's bf16 planes come from the attention kernel:
-            #  measured at full scale, moving it to the pair form as well raised the gradient error of the ill-conditioned trunk
-            #  convolutions from 6.3e-4 to 1.0e-3 of the reference -- the forward feeds everything; the backward products do not)
-            ao = torch.empty((ntok, hid), device=dev, dtype=f32)
-            ao_pair = bool(flash and amp_ao)
-            if ao_pair:
-                wo_pl, tile_ao = ops.weight_planes(wo, pair=True), ops.pair_tile(ntok, hid) or 128129
-            else:
-                if pctx is None:
-                    pctx = ops.split_planes(ctxv)
-                wo_pl, tile_ao = ops.weight_planes(wo), ops._dense_tile(ntok, hid)
-            # (the bf16 planes of x1 / gelu(h) / y are operands of the BACKWARD's six-product form: not written when that backward runs the
-            #  pair form, nor when there is no backward at all and the forward reads the pair planes)
-            keep3 = not pair_bwd and not (pair and nograd)
-            px1 = ops.planes_empty(ntok, hid, dev) if keep3 else None
-            px1q = ops.pair_empty(ntok, hid, dev) if pair else None
-            inter = wi.shape[0]
-            h = torch.empty((ntok, inter), device=dev, dtype=f32)
-            # gelu(h) leaves the FFN1 epilogue as planes only (the A operand of FFN2 and, untransposed, of its weight gradient)
-            pg = ops.planes_empty(ntok, inter, dev) if keep3 else None
-            pgq = ops.pair_empty(ntok, inter, dev) if pair else None
-            fo = torch.empty((ntok, hid), device=dev, dtype=f32)
-            wi_pl, wo2_pl = ops.weight_planes(wi, pair=pair), ops.weight_planes(wo2, pair=pair)
-            if pair:
-                tile_f1, tile_f2 = ptile(inter, True), ptile(hid)
-            else:
-                tile_f1, tile_f2 = ops._dense_tile(ntok, inter, True), ops._dense_tile(ntok, hid)
-            if fast:
-                x1, xh1, y, xh2 = (torch.empty_like(x) for _ in range(4))
-                rs1, rs2 = (torch.empty((ntok,), device=dev, dtype=f32) for _ in range(2))
-                py = ops.planes_empty(ntok, hid, dev) if keep3 else None
-                pyq = ops.pair_empty(ntok, hid, dev) if pair else None
-                ops.bert_layer_fwd(meta, eps=eps, p=p, seed=seed, sid=sid, x=x, xa=xq if xq is not None else px, pair_qkv=xq is not None,
-                                   wqkv=wqkv_pl, bqkv=bqkv_t, tile_qkv=tile_qkv, pqkv=pqkv, attn_pair=attn_pair, ctxv=ctxv, lse=lse, kbar=kbar,
-                                   pctx=pctx, pctxq=pctxq, masks=masks, scale=1.0 / (dh ** 0.5), wo=wo_pl, bo=bo, ao_pair=ao_pair, tile_ao=tile_ao,
-                                   ao=ao, g1=g1, b1=b1, x1=x1, xh1=xh1, rs1=rs1, px1=px1, px1q=px1q, wi=wi_pl, bi=bi, wo2=wo2_pl, bo2=bo2,
-                                   pair_ffn=pair, tile_ffn1=tile_f1, tile_ffn2=tile_f2, h=h, pg=pg, pgq=pgq, fo=fo, g2=g2, b2=b2, y=y, xh2=xh2,
-                                   rs2=rs2, py=py, pyq=pyq)
-            else:
-                ops.plane_gemm(pctxq if ao_pair else pctx, wo_pl, ao, bias=bo, tile=tile_ao, form=1 if ao_pair else 0)
-                x1, xh1, rs1 = ops.dropout_add_ln_fwd(ao, x, g1, b1, eps, p, seed, sid + 1, out_planes=px1, out_pair=px1q)
-                if pair:
-                    ops.plane_gemm(px1q, wi_pl, h, bias=bi, epi=EPI_GELU_DUAL, out_planes=pg, out_pair=pgq, tile=tile_f1, form=1)
-                    ops.plane_gemm(pgq, wo2_pl, fo, bias=bo2, tile=tile_f2, form=1)
-                else:
-                    ops.plane_gemm(px1, wi_pl, h, bias=bi, epi=EPI_GELU_DUAL, out_planes=pg, tile=tile_f1)
-                    ops.plane_gemm(pg, wo2_pl, fo, bias=bo2, tile=tile_f2)
-            if pair and not pair_bwd:
-                pgq = px1q = None
-            g = None
-        else:
-            ao = ops.linear_fwd(ctxv, wo, bo)
-            x1, xh1, rs1 = ops.dropout_add_ln_fwd(ao, x, g1, b1, eps, p, seed, sid + 1)
-            h, g = ops.linear_fwd(x1, wi, bi, EPI_GELU_DUAL)
-            fo = ops.linear_fwd(g, wo2, bo2)
-        if not fast:
-            pyq = None
-            if planes:
-                py = ops.planes_empty(ntok, hid, dev) if keep3 else None
-                pyq = ops.pair_empty(ntok, hid, dev) if pair else None
-            y, xh2, rs2 = ops.dropout_add_ln_fwd(fo, x1, g2, b2, eps, p, seed, sid + 2, out_planes=py, out_pair=pyq)
-        ctx.meta, ctx.cfg = meta, (eps, p, seed, sid)
-        ctx.planes, ctx.flash, ctx.pair_bwd = planes, flash, pair_bwd
-        ctx.w_refs = (wq, wk, wv, wo, wi, wo2)
-        ctx.b_refs = (bq, bk, bv, bo, bi, bo2, g1, b1, g2, b2)
-        if not any(ctx.needs_input_grad):
-            pass                                   # (nothing is differentiated -- inference, validation: nothing to keep)
-        elif planes:
+            wo_pl, tile_ao = ops.weight_planes(wo), ops._dense_tile(ntok, hid)
+        pair, keep3 = r.pair, r.keep3
+        tile_f1, tile_f2 = (ptile(inter, True), ptile(hid)) if pair else (ops._dense_tile(ntok, inter, True), ops._dense_tile(ntok, hid))
+        empty = lambda n: torch.empty((ntok, n), device=dev, dtype=f32)
+        planes_of = lambda n, on: ops.planes_empty(ntok, n, dev) if on else None
+        pair_of = lambda n: ops.pair_empty(ntok, n, dev) if pair else None
+        # gelu(h) leaves the FFN1 epilogue as planes only (the A operand of FFN2 and, untransposed, of its weight gradient)
+        kw = dict(eps=eps, p=p, seed=seed, sid=sid, x=x, xa=xq if r.pair_qkv else px, pair_qkv=r.pair_qkv, wqkv=wqkv, bqkv=bqkv,
+                  tile_qkv=tile_qkv, pqkv=pqkv, attn_pair=r.attn_pair, ctxv=ctxv, lse=lse, kbar=kbar, pctx=pctx, pctxq=pctxq, masks=masks,
+                  scale=1.0 / (meta.dh ** 0.5), wo=wo_pl, bo=bo, ao_pair=r.ao_pair, tile_ao=tile_ao, ao=empty(hid), g1=g1, b1=b1, x1=empty(hid),
+                  xh1=empty(hid), rs1=torch.empty((ntok,), device=dev, dtype=f32), px1=planes_of(hid, keep3), px1q=pair_of(hid),
+                  wi=ops.weight_planes(wi, pair=pair), bi=bi, wo2=ops.weight_planes(wo2, pair=pair), bo2=bo2, pair_ffn=pair, tile_ffn1=tile_f1,
+                  tile_ffn2=tile_f2, h=empty(inter), pg=planes_of(inter, keep3), pgq=pair_of(inter), fo=empty(hid), g2=g2, b2=b2, y=empty(hid),
+                  xh2=empty(hid), rs2=torch.empty((ntok,), device=dev, dtype=f32), py=planes_of(hid, keep3), pyq=pair_of(hid), qkv=qkv, P=P)
+        (ops.bert_layer_fwd if r.entry else ops.bert_layer_launches)(meta, **kw)
+        if grad:
             # backward needs the activations only as GEMM operands: their planes stand in for x / ctx / x1 / gelu(h)
-            ctx.pl_shape = (ntok, hid, wi.shape[0])
-            if pair_bwd:
-                ctx.masks = masks
-                ctx.save_for_backward(wq, wk, wv, wo, g1, wi, wo2, g2, pqkv.buf, ctxv, xh1, rs1, h, xh2, rs2, xq.buf, px1q.buf, pgq.buf, lse, kbar,
-                                      None if pctxq is None else pctxq.buf)
-            elif flash:
-                ctx.masks = masks
-                ctx.save_for_backward(wq, wk, wv, wo, g1, wi, wo2, g2, pqkv.buf, ctxv, xh1, rs1, h, xh2, rs2, px.buf, pctx.buf, px1.buf, pg.buf, lse, kbar)
-            else:
-                ctx.save_for_backward(wq, wk, wv, wo, g1, wi, wo2, g2, qkv, P, xh1, rs1, h, xh2, rs2, px.buf, pctx.buf, px1.buf, pg.buf)
-        else:
-            ctx.save_for_backward(x, wq, wk, wv, wo, g1, wi, wo2, g2, qkv, P, ctxv, xh1, rs1, x1, h, g, xh2, rs2)
-        if py is None and pyq is not None:            # all-pair path: the pair planes themselves travel to the next layer
-            ctx.mark_non_differentiable(pyq.buf)
-            ctx.set_materialize_grads(False)
-            return y, pyq.buf
-        if py is None:
-            return y, None
-        ctx.mark_non_differentiable(py.buf)
+            ctx.masks = masks
+            _save(ctx, wq=wq, wk=wk, wv=wv, wo=wo, g1=g1, wi=wi, wo2=wo2, g2=g2, qkv=qkv, P=P, pqkv=pqkv, ctxv=ctxv, xq=xq, px=px, pctx=pctx,
+                  pctxq=pctxq, lse=lse, kbar=kbar, **{k: kw[k] for k in ("xh1", "rs1", "h", "xh2", "rs2", "px1", "pg", "px1q", "pgq")})
+        y, py, pyq = kw["y"], kw["py"], kw["pyq"]
+        out = py if py is not None else pyq          # (all-pair path: the pair planes themselves travel to the next layer)
+        ctx.mark_non_differentiable(out.buf)
         ctx.set_materialize_grads(False)       # (no zero tensor for the planes output's gradient slot: 19 MB fill per layer)
-        if pyq is not None:
+        if py is not None and pyq is not None:
             py.buf._vbg_pair = pyq             # (travels on the tensor object to the next layer's first product)
-        return y, py.buf
+        return y, out.buf
 
     @staticmethod
-    def _backward_pair(ctx, dy):
+    def backward(ctx, dy, _dplanes=None):
+        r = ctx.route
+        s = SimpleNamespace(**dict(zip(_SAVED[r.saved], ctx.saved_tensors)))
+        if r.pair_bwd:
+            return BertLayerFn._backward_pair(ctx, s, dy)
+        return (BertLayerFn._backward_planes if r.planes else BertLayerFn._backward_dense)(ctx, s, dy)
+
+    @staticmethod
+    def _backward_pair(ctx, s, dy):
         """backward of the all-pair path: every product on two fp16 pieces.  A gradient operand is split by a pass of its own once its
         largest magnitude is known (LayerNorm backward -> fp32 -> vbg_amax -> scaled split with the bias column sums; the GELU-gradient
         product reports the maximum of what it stores), scaled by the power of two of that maximum; products scale back (exact)."""
-        (wq, wk, wv, wo, g1, wi, wo2, g2, bqkv, ctxv, xh1, rs1, h, xh2, rs2, bx, bx1, bg, lse, kbar, bctxq) = ctx.saved_tensors
         meta = ctx.meta
         eps, p, seed, sid = ctx.cfg
-        ntok, hid, inter = ctx.pl_shape
-        H, dh = meta.heads, meta.dh
-        dev = h.device
+        (ntok, inter), hid = s.h.shape, s.xh1.shape[1]
+        dev = s.h.device
         mk = lambda buf, cols: ops.Planes(buf, ntok, cols, buf.shape[2])
-        qx, qx1, qg = mk(bx, hid), mk(bx1, hid), mk(bg, inter)
+        qx, qx1, qg = mk(s.xq, hid), mk(s.px1q, hid), mk(s.pgq, inter)
         # (the attention output as the B operand of the output projection's weight gradient: pair planes written by the forward kernel)
-        qctx = mk(bctxq, hid) if bctxq is not None else ops.split_planes_pair(ctxv)
+        qctx = mk(s.pctxq, hid) if s.pctxq is not None else ops.split_planes_pair(s.ctxv)
         rbq, rbk, rbv, rbo, rbi, rbo2, rg1, rb1, rg2, rb2 = ctx.b_refs
         rq, rk, rv, ro, ri, ro2 = ctx.w_refs
         tile = lambda n, wide=False: ops.pair_tile(ntok, n, wide)
@@ -879,10 +900,10 @@ class BertLayerFn(torch.autograd.Function):
             if s_dy is None:
                 s_dy = ops.amax(dyc)                  # (the top layer: its output gradient is a sum autograd formed)
             s_dfo_ref = ops.amax_slot(dev)
-            qdfo, dx1 = ops.dropout_add_ln_bwd_pair(dyc, xh2, rs2, g2, p, seed, sid + 2, dg2, db2, wgrad_dest(rbo2), s_dy, s_dfo, s_dfo_ref)
+            qdfo, dx1 = ops.dropout_add_ln_bwd_pair(dyc, s.xh2, s.rs2, s.g2, p, seed, sid + 2, dg2, db2, wgrad_dest(rbo2), s_dy, s_dfo, s_dfo_ref)
         else:
             s_dfo_ref = s_dfo
-            dfo, dx1 = ops.dropout_add_ln_bwd(dyc, xh2, rs2, g2, p, seed, sid + 2, dg2, db2, dx_amax=s_dfo)
+            dfo, dx1 = ops.dropout_add_ln_bwd(dyc, s.xh2, s.rs2, s.g2, p, seed, sid + 2, dg2, db2, dx_amax=s_dfo)
             qdfo = ops.split_planes_pair(dfo, amax_slot_=s_dfo, colsum_out=wgrad_dest(rbo2))
             del dfo
         dg2, db2 = _affine_done(rg2, rb2, dg2, db2, sunk2)
@@ -892,44 +913,44 @@ class BertLayerFn(torch.autograd.Function):
         #      of a measured maximum, so it needs no fp32 round trip and no split pass; s_dh receives the bound (the consumers' scale)
         s_dh = ops.amax_slot(dev)
         qdh = ops.pair_empty(ntok, inter, dev)
-        ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=wo2, pair=True), None, epi=EPI_MUL_GELU_GRAD, C2=h, tile=tile(inter, True), form=1,
-                       a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=wo2), q_mul=1.13 * 1.01, q_ref_out=s_dh,
+        ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=s.wo2, pair=True), None, epi=EPI_MUL_GELU_GRAD, C2=s.h, tile=tile(inter, True), form=1,
+                       a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=s.wo2), q_mul=1.13 * 1.01, q_ref_out=s_dh,
                        colsum_out=wgrad_dest(rbi))
         wgrad_done(rbi)
         s_dx1 = ops.amax_slot(dev) if bound else None           # (max |dx1| rides on the product that completes it: LayerNorm 1's bound)
-        ops.plane_gemm(qdh, ops.weight_planes(ri, True, view=wi, pair=True), dx1, accumulate=True, tile=tile(hid), form=1, a_amax=s_dh, c_amax=s_dx1)
+        ops.plane_gemm(qdh, ops.weight_planes(ri, True, view=s.wi, pair=True), dx1, accumulate=True, tile=tile(hid), form=1, a_amax=s_dh, c_amax=s_dx1)
         # ---- LayerNorm 1 backward -> dao (pair planes by the same bound, or fp32 + split)
         dg1, db1, sunk1 = _affine_dest(rg1, rb1)
         s_dao = ops.amax_slot(dev)
         if bound and sunk1:
             s_dao_ref = ops.amax_slot(dev)
-            qdao, dx = ops.dropout_add_ln_bwd_pair(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1, wgrad_dest(rbo), s_dx1, s_dao, s_dao_ref)
+            qdao, dx = ops.dropout_add_ln_bwd_pair(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1, wgrad_dest(rbo), s_dx1, s_dao, s_dao_ref)
         else:
             s_dao_ref = s_dao
-            dao, dx = ops.dropout_add_ln_bwd(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1, dx_amax=s_dao)
+            dao, dx = ops.dropout_add_ln_bwd(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1, dx_amax=s_dao)
             qdao = ops.split_planes_pair(dao, amax_slot_=s_dao, colsum_out=wgrad_dest(rbo))
             del dao
         dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
         wgrad_done(rbo)
         # ---- d(context), the dO operand of the fused attention backward: fp16-pair planes like the forward's q / k / v planes, scaled by a
         #      bound (max |dao| x the largest column L1 norm of W_o; the attention kernels read the scale from s_dctx)
-        assert bqkv.shape[0] == 2, "the all-pair backward's q / k / v are fp16-pair planes"
-        pqkv = ops.Planes(bqkv, ntok, 3 * hid, bqkv.shape[2])
+        assert s.pqkv.shape[0] == 2, "the all-pair backward's q / k / v are fp16-pair planes"
+        pqkv = mk(s.pqkv, 3 * hid)
         pdctx = ops.pair_empty(ntok, hid, dev)
         s_dctx = ops.amax_slot(dev)
-        ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=wo, pair=True), None, tile=tile(hid), form=1, a_amax=s_dao_ref, out_pair=pdctx,
-                       q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=wo), q_mul=1.01, q_ref_out=s_dctx)
+        ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=s.wo, pair=True), None, tile=tile(hid), form=1, a_amax=s_dao_ref, out_pair=pdctx,
+                       q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=s.wo), q_mul=1.01, q_ref_out=s_dctx)
         delta = ctx.delta_buf
         dqkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
-        sc = 1.0 / (dh ** 0.5)
+        sc = 1.0 / (meta.dh ** 0.5)
         s_dqkv = ops.amax_slot(dev)                   # (the largest magnitude of d(qkv) rides on the two kernels that write it)
-        ops.attn(meta, ATTN_DQ, pqkv, pdctx, dqkv, lse, delta, ctx.masks, sc, p, kbar=kbar, o=ctxv, out_amax=s_dqkv, do_amax=s_dctx)
-        ops.attn(meta, ATTN_DKV, pqkv, pdctx, dqkv, lse, delta, ctx.masks, sc, p, out_amax=s_dqkv, do_amax=s_dctx)
+        ops.attn(meta, ATTN_DQ, pqkv, pdctx, dqkv, s.lse, delta, ctx.masks, sc, p, kbar=s.kbar, o=s.ctxv, out_amax=s_dqkv, do_amax=s_dctx)
+        ops.attn(meta, ATTN_DKV, pqkv, pdctx, dqkv, s.lse, delta, ctx.masks, sc, p, out_amax=s_dqkv, do_amax=s_dctx)
         gq = [wgrad_dest(t) for t in (rq, rk, rv, rbq, rbk, rbv)]
         qdqkv = ops.split_planes_pair(dqkv, amax_slot_=s_dqkv, colsum_out=_stack3(gq[3]))
         del dqkv
         s_dx = ops.amax_slot(dev) if bound else None            # (max |dx| for the layer below: its LayerNorm 2 bound)
-        ops.plane_gemm(qdqkv, ops.weight_planes(rq, True, view=_stack3(wq), also=(rk, rv), pair=True), dx, accumulate=True, tile=tile(hid), form=1,
+        ops.plane_gemm(qdqkv, ops.weight_planes(rq, True, view=_stack3(s.wq), also=(rk, rv), pair=True), dx, accumulate=True, tile=tile(hid), form=1,
                        a_amax=s_dqkv, c_amax=s_dx)
         if s_dx is not None:
             dx._vbg_amax = (s_dx, dx._version)
@@ -939,185 +960,113 @@ class BertLayerFn(torch.autograd.Function):
         ops.plane_gemm_grouped(jobs, trans=True, accumulate=True, form=1, a_amax=scales)
         for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
             wgrad_done(t)
-        return (dx, None, None, None, None, None, None, None, None, None, dg1, db1, None, None, None, None, dg2, db2, None, None, None, None, None)
+        return _grads(dx, dg1=dg1, db1=db1, dg2=dg2, db2=db2)
 
     @staticmethod
-    def _backward_planes(ctx, dy):
+    def _backward_planes(ctx, s, dy):
         """backward of the plane path: every dy is split once (the A operand of its data-gradient product) and the four weight
         gradients of the layer run as ONE grouped TN launch from the untransposed planes of dy and of the saved activations"""
-        flash = ctx.flash
-        if flash:
-            (wq, wk, wv, wo, g1, wi, wo2, g2, bqkv, ctxv, xh1, rs1, h, xh2, rs2, bx, bctx, bx1, bg, lse, kbar) = ctx.saved_tensors
-        else:
-            (wq, wk, wv, wo, g1, wi, wo2, g2, qkv, P, xh1, rs1, h, xh2, rs2, bx, bctx, bx1, bg) = ctx.saved_tensors
+        flash = ctx.route.flash
         meta = ctx.meta
         eps, p, seed, sid = ctx.cfg
-        ntok, hid, inter = ctx.pl_shape
-        H, dh = meta.heads, meta.dh
-        dev = h.device
+        (ntok, inter), hid = s.h.shape, s.xh1.shape[1]
+        dev = s.h.device
         mk = lambda buf, cols: ops.Planes(buf, ntok, cols, buf.shape[2])
-        px, pctx, px1, pg = mk(bx, hid), mk(bctx, hid), mk(bx1, hid), mk(bg, inter)
+        px, pctx, px1, pg = mk(s.px, hid), mk(s.pctx, hid), mk(s.px1, hid), mk(s.pg, inter)
         rbq, rbk, rbv, rbo, rbi, rbo2, rg1, rb1, rg2, rb2 = ctx.b_refs
         rq, rk, rv, ro, ri, ro2 = ctx.w_refs
-        dg2, db2, sunk2 = _affine_dest(rg2, rb2)
-        dst = wgrad_dest(rbo2)
-        if dst is not None and hid % 32 == 0:     # dx leaves the LayerNorm backward as planes, its column sums as the bias gradient
-            pdfo, dx1 = ops.dropout_add_ln_bwd_planes(_c(dy), xh2, rs2, g2, p, seed, sid + 2, dg2, db2, dst)
-            wgrad_done(rbo2)
-            dbo2 = None
-            dg2, db2 = _affine_done(rg2, rb2, dg2, db2, sunk2)
-        else:
-            dfo, dx1 = ops.dropout_add_ln_bwd(_c(dy), xh2, rs2, g2, p, seed, sid + 2, dg2, db2)
-            dg2, db2 = _affine_done(rg2, rb2, dg2, db2, sunk2)
-            pdfo, dbo2 = _split_with_bias_grad(rbo2, dfo)
+        pdfo, dx1, dg2, db2, dbo2 = _ln_bwd_planes(_c(dy), s.xh2, s.rs2, s.g2, p, seed, sid + 2, rg2, rb2, rbo2)
         # dL/dh = (dfo Wo2) o gelu'(h): the GELU backward rides in the product's epilogue
         dst_bi = wgrad_dest(rbi)
         if dst_bi is not None:
             # ... and dL/dh leaves as planes only (it is only ever a plane operand), its column sums go into the bias gradient
             pdh = ops.planes_empty(ntok, inter, dev)
-            ops.plane_gemm(pdfo, ops.weight_planes(ro2, True, view=wo2), None, epi=EPI_MUL_GELU_GRAD, C2=h, out_planes=pdh, colsum_out=dst_bi,
+            ops.plane_gemm(pdfo, ops.weight_planes(ro2, True, view=s.wo2), None, epi=EPI_MUL_GELU_GRAD, C2=s.h, out_planes=pdh, colsum_out=dst_bi,
                            tile=ops._dense_tile(ntok, inter, True))
             wgrad_done(rbi)
             dbi = None
         else:
-            dh_ = ops.plane_gemm(pdfo, ops.weight_planes(ro2, True, view=wo2), torch.empty_like(h), epi=EPI_MUL_GELU_GRAD, C2=h,
+            dh_ = ops.plane_gemm(pdfo, ops.weight_planes(ro2, True, view=s.wo2), torch.empty_like(s.h), epi=EPI_MUL_GELU_GRAD, C2=s.h,
                                  tile=ops._dense_tile(ntok, inter, True))
             pdh, dbi = _split_with_bias_grad(rbi, dh_)
-        ops.plane_gemm(pdh, ops.weight_planes(ri, True, view=wi), dx1, accumulate=True, tile=ops._dense_tile(ntok, hid))
-        dg1, db1, sunk1 = _affine_dest(rg1, rb1)
-        dst = wgrad_dest(rbo)
-        if dst is not None and hid % 32 == 0:
-            pdao, dx = ops.dropout_add_ln_bwd_planes(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1, dst)
-            wgrad_done(rbo)
-            dbo = None
-            dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
-        else:
-            dao, dx = ops.dropout_add_ln_bwd(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1)
-            dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
-            pdao, dbo = _split_with_bias_grad(rbo, dao)
+        ops.plane_gemm(pdh, ops.weight_planes(ri, True, view=s.wi), dx1, accumulate=True, tile=ops._dense_tile(ntok, hid))
+        pdao, dx, dg1, db1, dbo = _ln_bwd_planes(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, rg1, rb1, rbo)
         pdctx = ops.planes_empty(ntok, hid, dev) if flash else None
-        dctx = ops.plane_gemm(pdao, ops.weight_planes(ro, True, view=wo), torch.empty((ntok, hid), device=dev, dtype=f32), out_planes=pdctx,
+        dctx = ops.plane_gemm(pdao, ops.weight_planes(ro, True, view=s.wo), torch.empty((ntok, hid), device=dev, dtype=f32), out_planes=pdctx,
                               tile=ops._dense_tile(ntok, hid))
         if flash:
             # fused attention backward: delta = rowsum(dO o O), then dQ (queries stationary) and dK / dV (keys stationary), each
             # recomputing its score tile from the q / k / v planes and the saved log-sum-exp
-            pqkv = ops.Planes(bqkv, ntok, 3 * hid, bqkv.shape[2])
+            pqkv = mk(s.pqkv, 3 * hid)
             delta = ctx.delta_buf                      # zero in the padding rows; the DQ pass fills it
             dqkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
-            sc = 1.0 / (dh ** 0.5)
-            ops.attn(meta, ATTN_DQ, pqkv, pdctx, dqkv, lse, delta, ctx.masks, sc, p, kbar=kbar, o=ctxv)
-            ops.attn(meta, ATTN_DKV, pqkv, pdctx, dqkv, lse, delta, ctx.masks, sc, p)
+            sc = 1.0 / (meta.dh ** 0.5)
+            ops.attn(meta, ATTN_DQ, pqkv, pdctx, dqkv, s.lse, delta, ctx.masks, sc, p, kbar=s.kbar, o=s.ctxv)
+            ops.attn(meta, ATTN_DKV, pqkv, pdctx, dqkv, s.lse, delta, ctx.masks, sc, p)
         else:
-            dP = torch.empty_like(P)
-            ops.gemm_raw(0, 0, 0, dctx, hid, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_K, dP, meta.ld, grp=meta.t_dp, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, meta.maxlen), b_ptr_off=2 * hid, bk=16 if dh <= 128 else 0, tile=64064 if dh <= 128 else 0)
-            dqkv = torch.empty_like(qkv)
-            ops.gemm_raw(0, 0, 0, P, meta.ld, OP_DENSE_R, dctx, hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dv, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, dh), c_ptr_off=2 * hid, a_relu_scale=1.0 / (1.0 - p))
-            ops.softmax_bwd(P, dP, meta.soff, meta.lens, meta.ldp, meta.ngroups, H, meta.maxlen, 1.0 / (dh ** 0.5), p)
-            ops.gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dq, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, dh), b_ptr_off=hid)
-            ops.gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_R, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dk, ngroups=meta.ngroups,
-                         grp_max=(meta.maxlen, dh), c_ptr_off=hid)
-        stacked = _back_to_back(wq, wk, wv)
-        gq = [wgrad_dest(t) for t in (rq, rk, rv, rbq, rbk, rbv)]
-        qkv_sunk = stacked and all(t is not None for t in gq) and _back_to_back(*gq[:3]) and _back_to_back(*gq[3:])
+            dqkv = ops.attn_unfused_bwd(meta, s.qkv, s.P, dctx, p)
+        gq, qkv_sunk = _qkv_sunk(ctx, s.wq, s.wk, s.wv)
         pdqkv = ops.split_planes(dqkv, colsum_out=_stack3(gq[3]) if qkv_sunk else None)
-        if stacked:
-            ops.plane_gemm(pdqkv, ops.weight_planes(rq, True, view=_stack3(wq), also=(rk, rv)), dx, accumulate=True, tile=ops._dense_tile(ntok, hid))
+        if _back_to_back(s.wq, s.wk, s.wv):
+            ops.plane_gemm(pdqkv, ops.weight_planes(rq, True, view=_stack3(s.wq), also=(rk, rv)), dx, accumulate=True, tile=ops._dense_tile(ntok, hid))
         else:
-            for j, (w, wr) in enumerate(((wq, rq), (wk, rk), (wv, rv))):
+            for j, (w, wr) in enumerate(((s.wq, rq), (s.wk, rk), (s.wv, rv))):
                 ops.plane_gemm(pdqkv.col_block(j * hid, hid), ops.weight_planes(wr, True, view=w), dx, accumulate=True, tile=ops._dense_tile(ntok, hid))
         # ---- the four weight gradients: one grouped TN launch (432 tiles at bert-base: two rounds on 256 CUs instead of four
         #      launches of 36-144 tiles each) ------------------------------------------------------------------------------
         dw_qkv = _stack3(gq[0]) if qkv_sunk else torch.zeros((3 * hid, hid), device=dev, dtype=f32)
-        dests, fresh = [], []
-        for wp in (ro2, ri, ro):
-            d_ = wgrad_dest(wp)
-            fresh.append(d_ is None)
-            dests.append(d_ if d_ is not None else torch.zeros_like(wp))
-        jobs = [(pdfo, pg, dests[0]), (pdh, px1, dests[1]), (pdao, pctx, dests[2]), (pdqkv, px, dw_qkv)]
-        ops.plane_gemm_grouped(jobs, trans=True, accumulate=True)
+        dests = [wgrad_dest(wp) for wp in (ro2, ri, ro)]
+        fresh = [d_ is None for d_ in dests]
+        dests = [torch.zeros_like(wp) if fr else d_ for wp, d_, fr in zip((ro2, ri, ro), dests, fresh)]
+        ops.plane_gemm_grouped([(pdfo, pg, dests[0]), (pdh, px1, dests[1]), (pdao, pctx, dests[2]), (pdqkv, px, dw_qkv)], trans=True, accumulate=True)
         for wp, fr in zip((ro2, ri, ro), fresh):
             if not fr:
                 wgrad_done(wp)
-        dwo2, dwi, dwo = (dests[i] if fresh[i] else None for i in range(3))
-        if qkv_sunk:
-            for t in (rq, rk, rv, rbq, rbk, rbv):
-                wgrad_done(t)
-            return (dx, None, None, None, None, None, None, None, dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2, None, None, None, None, None)
-        dws, dbs = [], []
-        for j, (wr, br) in enumerate(((rq, rbq), (rk, rbk), (rv, rbv))):
+        dwo2, dwi, dwo = (d_ if fr else None for d_, fr in zip(dests, fresh))
+
+        def wgrad(j, wr, _):
             dj = dw_qkv[j * hid:(j + 1) * hid]
             dst = wgrad_dest(wr)
-            if dst is not None:            # sunk but not stacked: add the block into the parameter's own gradient view
-                dst.add_(dj)
-                wgrad_done(wr)
-                dj = None
-            dws.append(dj)
-            dbs.append(_bias_grad(br, dqkv[:, j * hid:(j + 1) * hid]))
-        return (dx, None, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2,
-                dg2, db2, None, None, None, None, None)
+            if dst is None:
+                return dj
+            dst.add_(dj)                   # sunk but not stacked: add the block into the parameter's own gradient view
+            wgrad_done(wr)
+        return _grads(dx, _qkv_tail(ctx, qkv_sunk, dqkv, wgrad), dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2)
 
     @staticmethod
-    def backward(ctx, dy, _dplanes=None):
-        if ctx.planes:
-            return BertLayerFn._backward_pair(ctx, dy) if ctx.pair_bwd else BertLayerFn._backward_planes(ctx, dy)
-        (x, wq, wk, wv, wo, g1, wi, wo2, g2, qkv, P, ctxv, xh1, rs1, x1, h, g, xh2, rs2) = ctx.saved_tensors
+    def _backward_dense(ctx, s, dy):
         meta = ctx.meta
         eps, p, seed, sid = ctx.cfg
-        ntok, hid = x.shape
-        H, dh = meta.heads, meta.dh
-        dev = x.device
         rbq, rbk, rbv, rbo, rbi, rbo2, rg1, rb1, rg2, rb2 = ctx.b_refs
+        rq, rk, rv, ro, ri, ro2 = ctx.w_refs
         dg2, db2, sunk2 = _affine_dest(rg2, rb2)
-        dfo, dx1 = ops.dropout_add_ln_bwd(_c(dy), xh2, rs2, g2, p, seed, sid + 2, dg2, db2)
+        dfo, dx1 = ops.dropout_add_ln_bwd(_c(dy), s.xh2, s.rs2, s.g2, p, seed, sid + 2, dg2, db2)
         dg2, db2 = _affine_done(rg2, rb2, dg2, db2, sunk2)
         # FFN
-        rq, rk, rv, ro, ri, ro2 = ctx.w_refs
-        dwo2 = _linear_wgrad(ro2, dfo, g)
+        dwo2 = _linear_wgrad(ro2, dfo, s.g)
         dbo2 = _bias_grad(rbo2, dfo)
-        dh_ = ops.linear_dgrad(dfo, wo2)
-        ops.gelu_bwd_(h, dh_)
-        dwi = _linear_wgrad(ri, dh_, x1)
+        dh_ = ops.linear_dgrad(dfo, s.wo2)
+        ops.gelu_bwd_(s.h, dh_)
+        dwi = _linear_wgrad(ri, dh_, s.x1)
         dbi = _bias_grad(rbi, dh_)
-        ops.linear_dgrad(dh_, wi, out=dx1, accumulate=True)
+        ops.linear_dgrad(dh_, s.wi, out=dx1, accumulate=True)
         # LN1
         dg1, db1, sunk1 = _affine_dest(rg1, rb1)
-        dao, dx = ops.dropout_add_ln_bwd(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1)
+        dao, dx = ops.dropout_add_ln_bwd(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1)
         dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
-        dwo = _linear_wgrad(ro, dao, ctxv)
+        dwo = _linear_wgrad(ro, dao, s.ctxv)
         dbo = _bias_grad(rbo, dao)
-        dctx = ops.linear_dgrad(dao, wo)
-        # attention backward (grouped GEMMs + row softmax backward)
-        dP = torch.empty_like(P)
-        ops.gemm_raw(0, 0, 0, dctx, hid, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_K, dP, meta.ld, grp=meta.t_dp, ngroups=meta.ngroups,
-                     grp_max=(meta.maxlen, meta.maxlen), b_ptr_off=2 * hid, bk=16 if dh <= 128 else 0, tile=64064 if dh <= 128 else 0)
-        dqkv = torch.empty_like(qkv)
-        ops.gemm_raw(0, 0, 0, P, meta.ld, OP_DENSE_R, dctx, hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dv, ngroups=meta.ngroups,
-                     grp_max=(meta.maxlen, dh), c_ptr_off=2 * hid, a_relu_scale=1.0 / (1.0 - p))
-        ops.softmax_bwd(P, dP, meta.soff, meta.lens, meta.ldp, meta.ngroups, H, meta.maxlen, 1.0 / (dh ** 0.5), p)
-        ops.gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dq, ngroups=meta.ngroups,
-                     grp_max=(meta.maxlen, dh), b_ptr_off=hid)
-        ops.gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_R, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dk, ngroups=meta.ngroups,
-                     grp_max=(meta.maxlen, dh), c_ptr_off=hid)
+        dctx = ops.linear_dgrad(dao, s.wo)
+        dqkv = ops.attn_unfused_bwd(meta, s.qkv, s.P, dctx, p)
         # QKV projections
-        gq = [wgrad_dest(t) for t in (rq, rk, rv, rbq, rbk, rbv)]
-        if (all(t is not None for t in gq) and _back_to_back(wq, wk, wv) and _back_to_back(*gq[:3]) and _back_to_back(*gq[3:])):
-            ops.linear_wgrad(dqkv, x, _stack3(gq[0]), accumulate=True)
+        gq, qkv_sunk = _qkv_sunk(ctx, s.wq, s.wk, s.wv)
+        if qkv_sunk:
+            ops.linear_wgrad(dqkv, s.x, _stack3(gq[0]), accumulate=True)
             ops.colsum(dqkv, out=_stack3(gq[3]), accumulate=True)
-            ops.linear_dgrad(dqkv, _stack3(wq), out=dx, accumulate=True)
-            for t in (rq, rk, rv, rbq, rbk, rbv):
-                wgrad_done(t)
-            return (dx, None, None, None, None, None, None, None, dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2, None, None, None, None, None)
-        dws, dbs = [], []
-        for j, (w, wr, br) in enumerate(((wq, rq, rbq), (wk, rk, rbk), (wv, rv, rbv))):
-            dj = dqkv[:, j * hid:(j + 1) * hid]
-            dws.append(_linear_wgrad(wr, dj, x))
-            dbs.append(_bias_grad(br, dj))
-            ops.linear_dgrad(dj, w, out=dx, accumulate=True)
-        return (dx, None, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2,
-                dg2, db2, None, None, None, None, None)
+            ops.linear_dgrad(dqkv, _stack3(s.wq), out=dx, accumulate=True)
+        qkv = _qkv_tail(ctx, qkv_sunk, dqkv, lambda j, wr, dj: _linear_wgrad(wr, dj, s.x),
+                        lambda dj, j: ops.linear_dgrad(dj, (s.wq, s.wk, s.wv)[j], out=dx, accumulate=True))
+        return _grads(dx, qkv, dwo, dbo, dg1, db1, dwi, dbi, dwo2, dbo2, dg2, db2)
 
 
 class StepRootFn(torch.autograd.Function):

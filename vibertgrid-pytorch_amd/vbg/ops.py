@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from .lib import (EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
+from .lib import (ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
                   AttnDesc, BertLayerFwdDesc, GemmDesc, PlaneGemmDesc, check, lib)
 
 f32 = torch.float32
@@ -302,7 +302,7 @@ def set_pair(on: bool, force: bool = False):
 
 
 def pair_enabled() -> bool:
-    return _PAIR[0] and _PLANES[0] and _SPLIT3[0] and not _amp_generic()
+    return _PAIR[0] and planes_enabled()
 
 
 _PAIR_BWD = [os.environ.get("VBG_PAIR_BWD", "1") != "0"]
@@ -459,17 +459,12 @@ def plane_gemm_grouped(problems, *, trans=True, accumulate=True, tile=0, alpha=1
     check(lib.vbg_plane_gemm(C.byref(d), _stream()), "vbg_plane_gemm (grouped)")
 
 
-_PLANES = [True]
 _W_EPOCH = [0]
 
 
-def set_planes(on: bool):
-    """dense linear products from pre-split bf16 planes (csrc/gemm_planes.hip) instead of the in-kernel split of vbg_gemm"""
-    _PLANES[0] = bool(on)
-
-
 def planes_enabled() -> bool:
-    return _PLANES[0] and _SPLIT3[0] and not _amp_generic()
+    """dense linear products from pre-split bf16 planes (csrc/gemm_planes.hip) instead of the in-kernel split of vbg_gemm"""
+    return _SPLIT3[0] and not _amp_generic()
 
 
 def flash_ok(hidden: int, inter: int, dh: int, maxlen: int) -> bool:
@@ -1386,13 +1381,11 @@ def embed_ln_bwd(dout, xhat, rstd, ids, pos_ids, gamma, p, seed, sid, dword, dpo
                                P(dpos), P(dtype0), P(dgamma), P(dbeta), _stream()), "vbg_embed_ln_bwd")
 
 
-def dropout_add_ln_fwd(x, res, gamma, beta, eps, p, seed, sid, out_planes=None, out_pair=None):
+def dropout_add_ln_fwd(x, res, gamma, beta, eps, p, seed, sid, out_planes=None, out_pair=None, out=None):
     """out_planes: Planes [rows, hidden] that receive the split of y in the same pass (ld == hidden: no padding columns); out_pair:
-    fp16-pair Planes of y as well (with out_planes)"""
+    fp16-pair Planes of y as well (with out_planes); out: (y, xhat, rstd) to write instead of fresh tensors"""
     rows, hidden = x.shape
-    y = torch.empty_like(x)
-    xhat = torch.empty_like(x)
-    rstd = torch.empty((rows,), device=x.device, dtype=f32)
+    y, xhat, rstd = out if out is not None else (torch.empty_like(x), torch.empty_like(x), torch.empty((rows,), device=x.device, dtype=f32))
     if out_planes is not None or out_pair is not None:
         assert (out_planes is None or (out_planes.ld == hidden and out_planes.rows == rows)) and (out_pair is None or out_pair.ld == hidden)
         check(lib.vbg_dropout_add_ln_fwd_planes(P(x), P(res), rows, hidden, P(gamma), P(beta), eps, p, seed, sid, P(y), P(xhat), P(rstd),
@@ -1477,6 +1470,34 @@ def attn_keep_scale(p):
     """1 / (1 - p') with p' = the 16-bit quantised drop rate the mask kernel realises (thr16 / 65536)"""
     thr = int(lib.vbg_attn_drop_thr16(float(p)))
     return 65536.0 / (65536.0 - thr)
+
+
+def attn_unfused_fwd(meta, qkv, P, ctxv, p, seed, sid):
+    """attention from the fp32 q / k / v columns of qkv [ntok, 3*hidden]: the scores into P (probabilities in place), grouped over
+    (sequence, head), then P V into ctxv"""
+    hid, dh = ctxv.shape[1], meta.dh
+    gemm_raw(0, 0, 0, qkv, 3 * hid, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_K, P, meta.ld, grp=meta.t_qk, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, meta.maxlen), b_ptr_off=hid, bk=16 if dh <= 128 else 0, tile=64064 if dh <= 128 else 0)
+    softmax_fwd(P, meta.soff, meta.lens, meta.ldp, meta.ngroups, meta.heads, meta.maxlen, 1.0 / (dh ** 0.5), p, seed, sid)
+    gemm_raw(0, 0, 0, P, meta.ld, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_R, ctxv, hid, grp=meta.t_pv, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, dh), b_ptr_off=2 * hid, a_relu_scale=1.0 / (1.0 - p))
+
+
+def attn_unfused_bwd(meta, qkv, P, dctx, p):
+    """backward of attn_unfused_fwd: d(qkv) [ntok, 3*hidden] from d(context), four grouped products and the row softmax backward"""
+    hid, dh = dctx.shape[1], meta.dh
+    dP = torch.empty_like(P)
+    gemm_raw(0, 0, 0, dctx, hid, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_K, dP, meta.ld, grp=meta.t_dp, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, meta.maxlen), b_ptr_off=2 * hid, bk=16 if dh <= 128 else 0, tile=64064 if dh <= 128 else 0)
+    dqkv = torch.empty_like(qkv)
+    gemm_raw(0, 0, 0, P, meta.ld, OP_DENSE_R, dctx, hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dv, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, dh), c_ptr_off=2 * hid, a_relu_scale=1.0 / (1.0 - p))
+    softmax_bwd(P, dP, meta.soff, meta.lens, meta.ldp, meta.ngroups, meta.heads, meta.maxlen, 1.0 / (dh ** 0.5), p)
+    gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_K, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dq, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, dh), b_ptr_off=hid)
+    gemm_raw(0, 0, 0, dP, meta.ld, OP_DENSE_R, qkv, 3 * hid, OP_DENSE_R, dqkv, 3 * hid, grp=meta.t_dk, ngroups=meta.ngroups,
+             grp_max=(meta.maxlen, dh), c_ptr_off=hid)
+    return dqkv
 
 
 def attn_mask(meta, p, seed, sid):
@@ -1591,9 +1612,11 @@ def _pref(r, pl):
 
 def bert_layer_fwd(meta, *, eps, p, seed, sid, x, xa, pair_qkv, wqkv, bqkv, tile_qkv, pqkv, attn_pair, ctxv, lse, kbar, pctx, pctxq, masks, scale,
                    wo, bo, ao_pair, tile_ao, ao, g1, b1, x1, xh1, rs1, px1, px1q, wi, bi, wo2, bo2, pair_ffn, tile_ffn1, tile_ffn2, h, pg, pgq, fo,
-                   g2, b2, y, xh2, rs2, py, pyq):
+                   g2, b2, y, xh2, rs2, py, pyq, qkv=None, P=None):
     """Planes arguments may be None where include/vbg.h marks them optional; the flags say which form each product runs (pair: fp16-pair
-    planes, three piece products -- one on the hi planes inside an autocast region -- else three bf16 planes, six)."""
+    planes, three piece products -- one on the hi planes inside an autocast region -- else three bf16 planes, six).  The layer's
+    seven launches leave from ONE library call (csrc/encoder.hip); bert_layer_launches issues them one by one."""
+    assert qkv is None and P is None and not isinstance(wqkv, tuple), "the layer entry runs the fused attention and one Q/K/V product"
     d = BertLayerFwdDesc()
     ntok, hid = x.shape
     inter = h.shape[1]
@@ -1635,6 +1658,32 @@ def bert_layer_fwd(meta, *, eps, p, seed, sid, x, xa, pair_qkv, wqkv, bqkv, tile
         _seen(("attn:onep" if d.form_attn == 2 else "attn:pair") if attn_pair else "attn:bf16x3")
         _seen("bert_layer_fwd:entry")
     check(lib.vbg_bert_layer_fwd(C.byref(d), _stream()), "vbg_bert_layer_fwd")
+
+
+def bert_layer_launches(meta, *, eps, p, seed, sid, x, xa, pair_qkv, wqkv, bqkv, tile_qkv, pqkv, attn_pair, ctxv, lse, kbar, pctx, pctxq, masks,
+                        scale, wo, bo, ao_pair, tile_ao, ao, g1, b1, x1, xh1, rs1, px1, px1q, wi, bi, wo2, bo2, pair_ffn, tile_ffn1, tile_ffn2, h,
+                        pg, pgq, fo, g2, b2, y, xh2, rs2, py, pyq, qkv=None, P=None):
+    """bert_layer_fwd one launch at a time, same kernels and descriptors (the measurement hooks time single launches).  Also runs what
+    the entry does not: one product per projection (wqkv, bqkv: three planes / biases; parameters not stored back to back) and the
+    unfused attention (qkv, P: the fp32 q / k / v and the probabilities; pqkv None; pctx receives the split of the context)"""
+    hid = x.shape[1]
+    if isinstance(wqkv, tuple):
+        for j, (w, b) in enumerate(zip(wqkv, bqkv)):
+            plane_gemm(xa, w, None if qkv is None else qkv[:, j * hid:(j + 1) * hid], bias=b,
+                       out_planes=None if pqkv is None else pqkv.col_block(j * hid, hid), tile=tile_qkv)
+    else:
+        plane_gemm(xa, wqkv, qkv, bias=bqkv, out_planes=None if attn_pair else pqkv, out_pair=pqkv if attn_pair else None, tile=tile_qkv,
+                   form=int(pair_qkv))
+    if pqkv is None:
+        attn_unfused_fwd(meta, qkv, P, ctxv, p, seed, sid)
+        split_planes(ctxv, out=pctx)
+    else:
+        attn(meta, ATTN_FWD, pqkv, None, ctxv, lse, None, masks, scale, p, kbar=kbar, out_planes=pctx, out_pair=pctxq)
+    plane_gemm(pctxq if ao_pair else pctx, wo, ao, bias=bo, tile=tile_ao, form=int(ao_pair))
+    dropout_add_ln_fwd(ao, x, g1, b1, eps, p, seed, sid + 1, out_planes=px1, out_pair=px1q, out=(x1, xh1, rs1))
+    plane_gemm(px1q if pair_ffn else px1, wi, h, bias=bi, epi=EPI_GELU_DUAL, out_planes=pg, out_pair=pgq, tile=tile_ffn1, form=int(pair_ffn))
+    plane_gemm(pgq if pair_ffn else pg, wo2, fo, bias=bo2, tile=tile_ffn2, form=int(pair_ffn))
+    dropout_add_ln_fwd(fo, x1, g2, b2, eps, p, seed, sid + 2, out_planes=py, out_pair=pyq, out=(y, xh2, rs2))
 
 
 def row_softmax(x):

@@ -550,13 +550,20 @@ int vbg_upsample_nhwc_to_nchw(const float* x, int B, int h, int w, int C, int f,
 int vbg_add_inplace(float* a, const float* b, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * a10. RoIAlign  (torchvision.ops.RoIAlign(7, 1/4, sampling_ratio=-1, aligned=False);
+ * a10. RoIAlign  (torchvision.ops.RoIAlign(7 or (h, w), 1/4, sampling_ratio=-1, aligned=False);
  *      model/grid_roi_align.py:37-41, 81).  feat NHWC [B,H,W,C]; boxes int32 image coords.
  * ------------------------------------------------------------------------------------------ */
 int vbg_roi_align_fwd(const float* feat, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi,
                       int out, float scale, float* y /* [nroi,out,out,C] */, void* stream);
 int vbg_roi_align_bwd(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi,
                       int out, float scale, float* dfeat_accum, void* stream);
+/* rectangular bins: torchvision.ops.RoIAlign(output_size=(out_h, out_w)) -- upstream model/grid_roi_align.py:10-19 takes
+ * output_size as an int or (H, W).  y [nroi,out_h,out_w,C].  The int entries above are these with out_h = out_w = out.  Backward:
+ * separable form for out_h * out_w <= 64, out_h <= 8, out_w <= 32 (H, W <= 256), the per-tap atomic kernel otherwise. */
+int vbg_roi_align_hw_fwd(const float* feat, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi,
+                         int out_h, int out_w, float scale, float* y, void* stream);
+int vbg_roi_align_hw_bwd(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi,
+                         int out_h, int out_w, float scale, float* dfeat_accum, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * a13. losses  (pipeline/custom_loss.py:35-101, 127-201)
@@ -638,6 +645,9 @@ int vbg_ce_bwd_rows(const float* logits, long long ld, int ncls, const int* elem
 /* RoIAlign backward, one owner per feature row: RoIs added in RoI order (out <= 8, out * W * 4 <= 48 KB) */
 int vbg_roi_align_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out,
                           float scale, float* dfeat_accum, void* stream);
+/* the same for (out_h, out_w) bins (upstream model/grid_roi_align.py:10-19): 1 <= out_h, out_w <= 32, out_w * W * 4 <= 48 KB of LDS */
+int vbg_roi_align_hw_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out_h,
+                             int out_w, float scale, float* dfeat_accum, void* stream);
 /* BatchNorm reductions: one partials row per row block (ws: vbg_bn_det_ws_rows(M, C) rows of 2C doubles, plain stores), the rows
  * added in block order into slot row 0 of zero_slots (which must be zero) */
 int vbg_bn_det_ws_rows(long long M, int C);

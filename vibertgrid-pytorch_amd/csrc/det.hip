@@ -127,15 +127,15 @@ __global__ void ce_bwd_rows_kernel(const float* __restrict__ logits, long long l
 // ---- RoIAlign backward (torchvision aligned=False geometry, as roi.hip) ----
 struct DetGeo { float y_start, x_start, bin_h, bin_w; int gh, gw; float inv_count; };
 
-__device__ __forceinline__ DetGeo det_geo(const int* box, float scale, int out) {
+__device__ __forceinline__ DetGeo det_geo(const int* box, float scale, int out_h, int out_w) {
     const float x1 = __fmul_rn((float)box[0], scale), y1 = __fmul_rn((float)box[1], scale);
     const float x2 = __fmul_rn((float)box[2], scale), y2 = __fmul_rn((float)box[3], scale);
     const float rw = fmaxf(__fsub_rn(x2, x1), 1.0f), rh = fmaxf(__fsub_rn(y2, y1), 1.0f);
     DetGeo g;
-    g.bin_h = __fdiv_rn(rh, (float)out);
-    g.bin_w = __fdiv_rn(rw, (float)out);
-    g.gh = (int)ceilf(__fdiv_rn(rh, (float)out));
-    g.gw = (int)ceilf(__fdiv_rn(rw, (float)out));
+    g.bin_h = __fdiv_rn(rh, (float)out_h);
+    g.bin_w = __fdiv_rn(rw, (float)out_w);
+    g.gh = (int)ceilf(__fdiv_rn(rh, (float)out_h));
+    g.gw = (int)ceilf(__fdiv_rn(rw, (float)out_w));
     g.y_start = y1; g.x_start = x1;
     g.inv_count = 1.0f / (float)max(g.gh * g.gw, 1);
     return g;
@@ -165,20 +165,23 @@ __device__ __forceinline__ float det_weight(float start, int b, float bin, int g
     return w;
 }
 
-constexpr int DET_ROI_OUT_MAX = 8;
-// block = (channel group, feature row Y, document); dynamic LDS: wx[out][W]
+// out_h, out_w <= 32; wx[out_w][W] must fit DET_ROI_LDS_BYTES
+constexpr int DET_ROI_OUT_MAX = 32;
+constexpr long long DET_ROI_LDS_BYTES = 48 * 1024;
+// block = (channel group, feature row Y, document); dynamic LDS: wx[out_w][W].  tmp[] stays in registers: its column loops are
+// unrolled to DET_ROI_OUT_MAX and guarded by bw < out_w.
 __global__ __launch_bounds__(256) void roi_align_bwd_det_kernel(const float* __restrict__ dy, int H, int W, int C,
                                                                 const int* __restrict__ boxes, const int* __restrict__ box_doc, int nroi,
-                                                                int out, float scale, float* dfeat) {
-    extern __shared__ float wx[];                 // [out][W]
+                                                                int out_h, int out_w, float scale, float* dfeat) {
+    extern __shared__ float wx[];                 // [out_w][W]
     __shared__ float wy[DET_ROI_OUT_MAX];
     const int Y = blockIdx.y, b = blockIdx.z;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     float* frow = dfeat + (((long long)b * H + Y) * W) * C;
     for (int r = 0; r < nroi; ++r) {
         if (box_doc[r] != b) continue;                                   // (uniform)
-        const DetGeo g = det_geo(boxes + 4 * (long long)r, scale, out);
-        const float rh = __fmul_rn(g.bin_h, (float)out), rw = __fmul_rn(g.bin_w, (float)out);
+        const DetGeo g = det_geo(boxes + 4 * (long long)r, scale, out_h, out_w);
+        const float rh = __fmul_rn(g.bin_h, (float)out_h), rw = __fmul_rn(g.bin_w, (float)out_w);
         const int y_lo = min(max((int)floorf(fmaxf(g.y_start, 0.f)), 0), H - 1);
         const int y_hi = min(max((int)floorf(g.y_start + rh) + 2, 0), H - 1);
         if (Y < y_lo || Y > y_hi) continue;                              // (uniform) the RoI's taps cannot reach this row
@@ -186,26 +189,31 @@ __global__ __launch_bounds__(256) void roi_align_bwd_det_kernel(const float* __r
         const int x_hi = min(max((int)floorf(g.x_start + rw) + 2, 0), W - 1);
         const int pw = x_hi - x_lo + 1;
         __syncthreads();                                                 // the previous RoI's tables are no longer read
-        if (threadIdx.x < out) wy[threadIdx.x] = det_weight(g.y_start, threadIdx.x, g.bin_h, g.gh, H, Y) * g.inv_count;
-        for (int i = threadIdx.x; i < out * pw; i += blockDim.x) {
+        if (threadIdx.x < out_h) wy[threadIdx.x] = det_weight(g.y_start, threadIdx.x, g.bin_h, g.gh, H, Y) * g.inv_count;
+        for (int i = threadIdx.x; i < out_w * pw; i += blockDim.x) {
             const int bw = i / pw, X = i - bw * pw;
             wx[bw * W + X] = det_weight(g.x_start, bw, g.bin_w, g.gw, W, x_lo + X);
         }
         __syncthreads();
         bool any = false;
-        for (int bh = 0; bh < out; ++bh) any |= wy[bh] != 0.f;
+        for (int bh = 0; bh < out_h; ++bh) any |= wy[bh] != 0.f;
         if (!any || c >= C) continue;
+        const float* dyr = dy + (long long)r * out_h * out_w * C + c;
         float tmp[DET_ROI_OUT_MAX];
-        for (int bw = 0; bw < out; ++bw) {
+#pragma unroll
+        for (int bw = 0; bw < DET_ROI_OUT_MAX; ++bw) {
             float a = 0.f;
-            for (int bh = 0; bh < out; ++bh)
-                if (wy[bh] != 0.f) a = fmaf(wy[bh], dy[((long long)r * out * out + bh * out + bw) * C + c], a);
+            if (bw < out_w)
+                for (int bh = 0; bh < out_h; ++bh)
+                    if (wy[bh] != 0.f) a = fmaf(wy[bh], dyr[(long long)(bh * out_w + bw) * C], a);
             tmp[bw] = a;
         }
         for (int X = 0; X < pw; ++X) {
             float v = 0.f;
             bool anyx = false;
-            for (int bw = 0; bw < out; ++bw) { const float w = wx[bw * W + X]; anyx |= w != 0.f; v = fmaf(w, tmp[bw], v); }
+#pragma unroll
+            for (int bw = 0; bw < DET_ROI_OUT_MAX; ++bw)
+                if (bw < out_w) { const float w = wx[bw * W + X]; anyx |= w != 0.f; v = fmaf(w, tmp[bw], v); }
             if (anyx) frow[(long long)(x_lo + X) * C + c] += v;
         }
     }
@@ -288,14 +296,24 @@ extern "C" int vbg_ce_bwd_rows(const float* logits, long long ld, int ncls, cons
     VBG_LAUNCH_RET();
 }
 
-extern "C" int vbg_roi_align_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out,
-                                     float scale, float* dfeat_accum, void* stream) {
-    VBG_CHECK_ARG(dy && dfeat_accum && B >= 0 && H > 0 && W > 0 && C > 0 && out > 0 && out <= DET_ROI_OUT_MAX && nroi >= 0);
-    VBG_CHECK_ARG((long long)out * W * sizeof(float) <= 48 * 1024);
+// torchvision.ops.RoIAlign(output_size=(out_h, out_w)) backward -- upstream model/grid_roi_align.py:10-19 (output_size: int or
+// (H, W)), :37-41; RoIs added in RoI order
+extern "C" int vbg_roi_align_hw_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi,
+                                        int out_h, int out_w, float scale, float* dfeat_accum, void* stream) {
+    VBG_CHECK_ARG(dy && dfeat_accum && B >= 0 && H > 0 && W > 0 && C > 0 && nroi >= 0);
+    VBG_CHECK_ARG(out_h > 0 && out_h <= DET_ROI_OUT_MAX && out_w > 0 && out_w <= DET_ROI_OUT_MAX);
+    VBG_CHECK_ARG((long long)out_w * W * sizeof(float) <= DET_ROI_LDS_BYTES);
     if (nroi == 0 || B == 0) return VBG_OK;
     VBG_CHECK_ARG(boxes && box_doc);
     const int nt = C >= 256 ? 256 : (C >= 128 ? 128 : 64);
-    VBG_LAUNCH(roi_align_bwd_det_kernel, dim3(cdiv(C, nt), H, B), dim3(nt), out * W * sizeof(float), S_, dy, H, W, C, boxes, box_doc, nroi,
-               out, scale, dfeat_accum);
+    VBG_LAUNCH(roi_align_bwd_det_kernel, dim3(cdiv(C, nt), H, B), dim3(nt), out_w * W * sizeof(float), S_, dy, H, W, C, boxes, box_doc,
+               nroi, out_h, out_w, scale, dfeat_accum);
     VBG_LAUNCH_RET();
+}
+
+// the square entry keeps its published bound, out <= 8; the (out_h, out_w) entry takes up to 32
+extern "C" int vbg_roi_align_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out,
+                                     float scale, float* dfeat_accum, void* stream) {
+    VBG_CHECK_ARG(out <= 8);
+    return vbg_roi_align_hw_bwd_det(dy, B, H, W, C, boxes, box_doc, nroi, out, out, scale, dfeat_accum, stream);
 }

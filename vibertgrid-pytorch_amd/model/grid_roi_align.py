@@ -1,5 +1,5 @@
 """GridROIAlign — mirror of the reference module (model/grid_roi_align.py:8-83): RoIAlign(output_size,
-spatial_scale=1/step, sampling_ratio=-1, aligned=False) over P_fuse, as a channel-coalesced NHWC HIP
+spatial_scale=1/step, sampling_ratio=-1, aligned=False) over P_fuse, output_size an int or (H, W), as a channel-coalesced NHWC HIP
 kernel (forward gather, backward wavefront atomics).  Boxes are the integer image-space boxes of the
 transform; the reference casts them to float (:73) and lets torchvision scale them."""
 from typing import Any, Tuple
@@ -17,18 +17,17 @@ class GridROIAlign(nn.Module):
             self.output_size = output_size
         else:
             raise TypeError(f"parameter 'output_size' requires int or tuple, {type(output_size)} were given")
-        if isinstance(output_size, tuple):
-            assert output_size[0] == output_size[1], "square ROI outputs only"
         self.spatial_scale = 1 / float(step)
 
     def forward(self, feature_map: torch.Tensor, coords: Tuple[torch.Tensor], mask: torch.Tensor = None,
                 packed=None) -> torch.Tensor:
-        """feature_map NHWC [B,H,W,C]; coords: per-image [S_b,4] boxes -> [sum S_b, out, out, C] (NHWC)."""
+        """feature_map NHWC [B,H,W,C]; coords: per-image [S_b,4] boxes -> [sum S_b, h, w, C] (NHWC)."""
         if packed is None:
             from model.BERTgrid_generator import BERTgridGenerator
             if mask is not None:
                 coords = tuple(c[mask[b] == 1] for b, c in enumerate(coords))
             packed = BERTgridGenerator.pack_boxes(tuple(coords))
         boxes, _, box_doc = packed
-        out = self.output_size if isinstance(self.output_size, int) else self.output_size[0]
+        # an int keeps the square entries; a tuple is (H, W) -- torchvision reads only its first two entries
+        out = self.output_size if isinstance(self.output_size, int) else (int(self.output_size[0]), int(self.output_size[1]))
         return Fn.RoiAlignFn.apply(feature_map, boxes, box_doc, out, self.spatial_scale)

@@ -176,6 +176,8 @@ SIGNATURES = {
     "vbg_upsample_nhwc_to_nchw": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "vbg_roi_align_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_roi_align_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp]),
+    "vbg_roi_align_hw_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp]),
+    "vbg_roi_align_hw_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_ce_fwd": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "vbg_ce_bwd": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp]),
     "vbg_compact_ws_bytes": (c_ll, [c_ll]),
@@ -202,6 +204,7 @@ SIGNATURES = {
     "vbg_segment_rows_add": (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_int, c_vp, c_ll, c_vp]),
     "vbg_ce_bwd_rows": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "vbg_roi_align_bwd_det": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp]),
+    "vbg_roi_align_hw_bwd_det": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_bn_det_ws_rows": (c_int, [c_ll, c_int]),
     "vbg_bn_stats_det": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_vp]),
     "vbg_bn_bwd_reduce_det": (c_int, [c_vp, c_vp, c_vp, c_ll, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),

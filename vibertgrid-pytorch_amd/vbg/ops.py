@@ -2016,24 +2016,54 @@ def rescale_boxes(coor_i64, rh, rw):
 # ----------------------------------------------------------------------------------------------
 # RoIAlign
 # ----------------------------------------------------------------------------------------------
+def roi_out_hw(out_size):
+    """RoIAlign output_size -> (out_h, out_w): an int is square; a tuple's first two entries are (H, W), as torchvision reads them
+    (upstream model/grid_roi_align.py:10-19)"""
+    if isinstance(out_size, int):
+        return out_size, out_size
+    return int(out_size[0]), int(out_size[1])
+
+
+# shapes csrc/roi.hip vbg_roi_align_hw_bwd runs in the separable form (the per-tap atomic kernel otherwise)
+ROI_SEP_BINS, ROI_SEP_OH, ROI_SEP_OW, ROI_DIM_MAX = 64, 8, 32, 256
+
+
+def roi_bwd_form(H, W, out_h, out_w) -> str:
+    sep = out_h * out_w <= ROI_SEP_BINS and out_h <= ROI_SEP_OH and out_w <= ROI_SEP_OW and H <= ROI_DIM_MAX and W <= ROI_DIM_MAX
+    return "sep" if sep else "tap"
+
+
 def roi_align_fwd(feat, boxes, box_doc, out_size, scale):
+    """out_size: int (the square entry) or (h, w) (the rectangular entry) -> [n, h, w, C]"""
     B, H, W, C_ = feat.shape
     n = boxes.shape[0]
-    y = torch.empty((n, out_size, out_size, C_), device=feat.device, dtype=f32)
-    check(lib.vbg_roi_align_fwd(P(feat), B, H, W, C_, P(boxes) if n else None, P(box_doc) if n else None, n, out_size, scale, P(y), _stream()), "vbg_roi_align_fwd")
+    oh, ow = roi_out_hw(out_size)
+    y = torch.empty((n, oh, ow, C_), device=feat.device, dtype=f32)
+    bx, bd = (P(boxes), P(box_doc)) if n else (None, None)
+    if isinstance(out_size, int):
+        check(lib.vbg_roi_align_fwd(P(feat), B, H, W, C_, bx, bd, n, out_size, scale, P(y), _stream()), "vbg_roi_align_fwd")
+    else:
+        check(lib.vbg_roi_align_hw_fwd(P(feat), B, H, W, C_, bx, bd, n, oh, ow, scale, P(y), _stream()), "vbg_roi_align_hw_fwd")
     return y
 
 
 def roi_align_bwd(dy, feat_shape, boxes, box_doc, out_size, scale, dfeat):
     B, H, W, C_ = feat_shape
     n = boxes.shape[0]
+    oh, ow = roi_out_hw(out_size)
+    sq = isinstance(out_size, int)
+    bx, bd = (P(boxes), P(box_doc)) if n else (None, None)
     if _DET[0]:
-        check(lib.vbg_roi_align_bwd_det(P(dy), B, H, W, C_, P(boxes) if n else None, P(box_doc) if n else None, n, out_size, scale, P(dfeat),
-                                        _stream()), "vbg_roi_align_bwd_det")
+        # (the square entry vbg_roi_align_bwd_det is this one with out_h = out_w, bounded at 8; this one takes up to 32)
+        check(lib.vbg_roi_align_hw_bwd_det(P(dy), B, H, W, C_, bx, bd, n, oh, ow, scale, P(dfeat), _stream()), "vbg_roi_align_hw_bwd_det")
         _seen("det:roi_align_bwd")
         return
     _seen("fatomic:roi_align_bwd")
-    check(lib.vbg_roi_align_bwd(P(dy), B, H, W, C_, P(boxes) if n else None, P(box_doc) if n else None, n, out_size, scale, P(dfeat), _stream()), "vbg_roi_align_bwd")
+    _seen("roi:" + roi_bwd_form(H, W, oh, ow))
+    if sq:
+        check(lib.vbg_roi_align_bwd(P(dy), B, H, W, C_, bx, bd, n, out_size, scale, P(dfeat), _stream()), "vbg_roi_align_bwd")
+    else:
+        check(lib.vbg_roi_align_hw_bwd(P(dy), B, H, W, C_, bx, bd, n, oh, ow, scale, P(dfeat), _stream()), "vbg_roi_align_hw_bwd")
 
 
 # ----------------------------------------------------------------------------------------------

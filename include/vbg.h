@@ -50,6 +50,20 @@ typedef struct vbg_conv_geo {
     int dgrad;           /* 0: src = row*stride - pad + tap;  1: src = (row + pad - tap) / stride   */
 } vbg_conv_geo;
 
+/* Frozen BatchNorm (torch.nn.BatchNorm2d in eval mode behind a bias-free convolution, model/ResNetFPN_ViBERTgrid.py:116-123) as the
+ * EPILOGUE of the convolution that feeds it: with v the finished accumulator of output channel c,
+ *   v = (v - mean[c]) * invstd[c] * gamma[c] + beta[c];  v += res[row][c] (res != NULL);  v = max(v, 0) (relu != 0);  store v
+ * -- the expression and order of vbg_bn_apply, so conv + vbg_bn_apply and the fused launch agree to the compiler's contraction of the
+ * same expression.  amax (optional): an amax slot (VBG_AMAX_WORDS words, zeroed by the caller) that receives the bit pattern of the
+ * launch's max |v|, as vbg_bn_apply's y_amax.  mean, invstd, gamma, beta: [N] fp32; res: the output's shape and row stride, 16-byte
+ * aligned, not the output itself.  No float atomics: legal in deterministic mode. */
+typedef struct vbg_bn_epilogue {
+    const float* mean; const float* invstd; const float* gamma; const float* beta;
+    const float* res;
+    int relu;
+    unsigned* amax;
+} vbg_bn_epilogue;
+
 typedef struct vbg_gemm_desc {
     int M, N, K;
     const float* A; long long lda; int a_kind; int a_vec;   /* a_vec: 16-byte vector loads legal   */
@@ -96,6 +110,10 @@ typedef struct vbg_gemm_desc {
        very long reduction: the first layer of the field-type classifier on ONE document is 128 x 1024 outputs over k = 13 312
        (model/field_type_classification_head.py:78-110) -- 32 tiles of 416 k-tiles otherwise. */
     long long slab_stride;
+    /* optional: frozen-BatchNorm epilogue (below); bn.mean == NULL (a zeroed value): none.  The row stride of bn.res is ldc.  An argument
+       error together with stats, accumulate, splitk != 1, slab_stride, groups, C2, epi != NONE, bias, N % 4 != 0, ldc % 4 != 0, a C or
+       bn.res that is not 16-byte aligned, or bn.res == C. */
+    vbg_bn_epilogue bn;
 } vbg_gemm_desc;
 
 int vbg_gemm(const vbg_gemm_desc* desc, void* stream);
@@ -319,6 +337,14 @@ int vbg_conv3x3_pw(const float* x, const void* w_planes, const float* bias, floa
 int vbg_conv3x3_pw_amp(const float* x, const void* w_planes, const float* bias, float* y, double* stats, int stats_slots, int B, int H, int W,
                        int Cs, int N, int accumulate, const unsigned* x_amax, float* split_slab, unsigned* split_tickets, int nsplit,
                        int bn, void* stream);
+/* The same convolution with a frozen-BatchNorm epilogue (vbg_bn_epilogue above; bn->mean must be set): y = relu?(bn(conv(x, w)) + res) from
+ * ONE launch, in the split form applied by the tile's finishing workgroup after it has added the slabs in block order.  Exactly one of
+ * `w` (fp32 filter [N,3,3,Cs]: form 0 or 1 as vbg_conv3x3) and `w_planes` (the plane image: form 1 = vbg_conv3x3_pw, 2 = vbg_conv3x3_pw_amp;
+ * `bn_tile` = their `bn`, 0 with `w`) is given; no bias, statistics or accumulate (a BatchNorm's convolution has none).  res and y are
+ * [B,H,W,N] (compact rows for the 7 x 7 region maps), 16-byte aligned, res != y. */
+int vbg_conv3x3_bn(const float* x, const float* w, const void* w_planes, float* y, int B, int H, int W, int Cs, int N, int form,
+                   const unsigned* x_amax, float* split_slab, unsigned* split_tickets, int nsplit, int bn_tile,
+                   const vbg_bn_epilogue* bn, void* stream);
 /* bn (vbg_conv3x3_pw / vbg_conv3x3_wprep_bytes): filters per tile the image was written for -- 0: the library's rule above; 64 / 128: the
  * caller's choice (64-filter tiles double the tile count of a launch: the late trunk stages, whose 128-filter tiles do not fill the chip);
  * the launch then runs 128-pixel tiles whatever the tile count, and nsplit > 1 needs N % bn == 0 (slabs of 128 * bn floats). */

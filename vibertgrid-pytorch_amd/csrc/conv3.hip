@@ -40,6 +40,7 @@ struct conv3_args {
     unsigned* tickets;     // [tiles] arrival counters of the split form, zero between launches
     int accumulate;
     const unsigned* a_amax; // F16 form: bits of max |X| (a device word written by the producer of X), or null: X is used as it is
+    vbg_bn_epilogue bn;    // frozen BatchNorm (+ residual, ReLU, amax) on the finished tile (include/vbg.h); bn.mean null: none
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t c3_rsrc(const float* base) {
@@ -581,6 +582,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
         part = p.slab + tile * nz * (size_t)(BM * BN);
     }
     float4 cs = make_float4(0.f, 0.f, 0.f, 0.f), cq = cs;
+    // frozen BatchNorm of the finished tile (vbg_bn_epilogue): bn_apply_kernel's expression, term for term, on the value about to be stored
+    const float* const bn_mean = p.bn.mean;
+    const float* const bn_res = p.bn.res;
+    const int bn_relu = p.bn.relu;
+    float bn_mx = 0.f;
 #pragma unroll 4
     for (int q = 0; q < BM * QN / NT; ++q) {
         const int idx = tid + q * NT;
@@ -605,6 +611,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
         }
         if (bias) { v.x += bias[gn]; v.y += bias[gn + 1]; v.z += bias[gn + 2]; v.w += bias[gn + 3]; }
         float* cp = p.Y + (long long)gm * N + gn;
+        if (bn_mean) {
+            const float4 mu = *reinterpret_cast<const float4*>(bn_mean + gn), is = *reinterpret_cast<const float4*>(p.bn.invstd + gn);
+            const float4 ga = *reinterpret_cast<const float4*>(p.bn.gamma + gn), be = *reinterpret_cast<const float4*>(p.bn.beta + gn);
+            v.x = (v.x - mu.x) * is.x * ga.x + be.x; v.y = (v.y - mu.y) * is.y * ga.y + be.y;
+            v.z = (v.z - mu.z) * is.z * ga.z + be.z; v.w = (v.w - mu.w) * is.w * ga.w + be.w;
+            if (bn_res) {
+                const float4 rv = *reinterpret_cast<const float4*>(bn_res + (long long)gm * N + gn);
+                v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+            }
+            if (bn_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            bn_mx = fmaxf(fmaxf(bn_mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        }
         if (p.stats) {
             cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
             cq.x += v.x * v.x; cq.y += v.y * v.y; cq.z += v.z * v.z; cq.w += v.w * v.w;
@@ -614,6 +632,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const conv3_args p) {
             v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
         }
         *reinterpret_cast<float4*>(cp) = v;
+    }
+    if (bn_mean && p.bn.amax) {
+        // behind the loop, where the whole block arrives (the loop `continue`s past rows and columns that do not exist; in the split
+        // form only the finishing block is here): block-wide max through the staged tile's LDS, one atomicMax on the bit pattern into
+        // word (linear block id) % 64 of the slot -- amax_publish of csrc/convaux.hip, without a second LDS object
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bn_mx = fmaxf(bn_mx, __shfl_xor(bn_mx, o, 64));
+        float* red = reinterpret_cast<float*>(smem);
+        __syncthreads();                                       // every thread has read its pieces of the staged tile
+        if ((tid & 63) == 0) red[tid >> 6] = bn_mx;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned bits = __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+            unsigned* word = p.bn.amax + ((lin + total * (unsigned)zz) & (VBG_AMAX_WORDS - 1)) * VBG_AMAX_STRIDE;
+            if (bits > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, bits);
+        }
     }
     if (p.stats) {
         constexpr int RG = NT / QN;
@@ -1095,7 +1129,7 @@ extern "C" int vbg_conv3x3_wprep(const vbg_conv3_wprep_entry* table_dev, const v
 
 static int conv3x3_impl(const float* x, const float* w, const unsigned short* wp, const float* bias, float* y, double* stats, int stats_slots,
                         int B, int H, int W, int Cs, int N, int accumulate, int form, const unsigned* x_amax, float* split_slab,
-                        unsigned* split_tickets, int nsplit, void* stream, int bn_req = 0);
+                        unsigned* split_tickets, int nsplit, void* stream, int bn_req = 0, const vbg_bn_epilogue* bne = nullptr);
 
 extern "C" int vbg_conv3x3(const float* x, const float* w, const float* bias, float* y, double* stats, int stats_slots, int B, int H,
                            int W, int Cs, int N, int accumulate, int form, const unsigned* x_amax, float* split_slab,
@@ -1120,9 +1154,22 @@ extern "C" int vbg_conv3x3_pw_amp(const float* x, const void* w_planes, const fl
                         split_tickets, nsplit, stream, bn);
 }
 
+extern "C" int vbg_conv3x3_bn(const float* x, const float* w, const void* w_planes, float* y, int B, int H, int W, int Cs, int N, int form,
+                              const unsigned* x_amax, float* split_slab, unsigned* split_tickets, int nsplit, int bn_tile,
+                              const vbg_bn_epilogue* bn, void* stream) {
+    VBG_CHECK_ARG(bn && (w != nullptr) != (w_planes != nullptr));
+    if (w) {
+        VBG_CHECK_ARG((form == 0 || form == 1) && bn_tile == 0);
+        return conv3x3_impl(x, w, nullptr, nullptr, y, nullptr, 0, B, H, W, Cs, N, 0, form, x_amax, split_slab, split_tickets, nsplit, stream, 0, bn);
+    }
+    VBG_CHECK_ARG((form == 1 || form == 2) && (((uintptr_t)w_planes) & 15) == 0 && (bn_tile == 0 || bn_tile == 64 || bn_tile == 128));
+    return conv3x3_impl(x, nullptr, (const unsigned short*)w_planes, nullptr, y, nullptr, 0, B, H, W, Cs, N, 0, form, x_amax, split_slab, split_tickets,
+                        nsplit, stream, bn_tile, bn);
+}
+
 static int conv3x3_impl(const float* x, const float* w, const unsigned short* wp, const float* bias, float* y, double* stats, int stats_slots,
                         int B, int H, int W, int Cs, int N, int accumulate, int form, const unsigned* x_amax, float* split_slab,
-                        unsigned* split_tickets, int nsplit, void* stream, int bn_req) {
+                        unsigned* split_tickets, int nsplit, void* stream, int bn_req, const vbg_bn_epilogue* bne) {
     VBG_CHECK_ARG(form == 0 || form == 1 || (form == 2 && wp));          // (2: the one-product `amp` form of the pre-split kernels)
     VBG_CHECK_ARG(bn_req == 0 || wp);
     VBG_CHECK_ARG(!x_amax || form >= 1);
@@ -1140,6 +1187,14 @@ static int conv3x3_impl(const float* x, const float* w, const unsigned short* wp
     const long long M = (long long)B * H * W;
     VBG_CHECK_ARG(M < (1ll << 31));
     a.M = (int)M; a.accumulate = accumulate; a.a_amax = x_amax; a.roi = roi ? B : 0;
+    a.bn = vbg_bn_epilogue{};
+    if (bne) {
+        // the epilogue is the LAST thing that happens to the tile: nothing that adds to it afterwards or counts the unnormalised values
+        VBG_CHECK_ARG(bne->mean && bne->invstd && bne->gamma && bne->beta && !bias && !stats && !accumulate);
+        VBG_CHECK_ARG(((((uintptr_t)bne->mean) | ((uintptr_t)bne->invstd) | ((uintptr_t)bne->gamma) | ((uintptr_t)bne->beta) | ((uintptr_t)bne->res)) & 15) == 0);
+        VBG_CHECK_ARG(bne->res != y);
+        a.bn = *bne;
+    }
     // split form: nsplit blocks per tile meet in split_slab [tiles][nsplit][128 * 128] / split_tickets [tiles] (zero; left zero)
     const bool split = nsplit > 1;
     VBG_CHECK_ARG(nsplit >= 1 && (!split || (split_slab && split_tickets && !roi && N % (bn_req ? bn_req : 128) == 0 && ((long long)H * W) % 128 == 0)));

@@ -97,6 +97,16 @@ struct sched_pipe {
 // NT = threads per block (256: 4 waves in 2x2, LDS double buffered, one barrier per k-tile).
 // PREC 1 ("amp"): the operands stay fp32 in HBM, are rounded to bf16 on their way into LDS and multiplied with
 // v_mfma_f32_32x32x16_bf16 (fp32 accumulate, 16x the fp32 matrix rate); loaders and epilogue are shared with the fp32 form.
+
+// does this instance store its tile through LDS (gemm_kernel's STAGE_OK)?  The fp32 form's 16-deep k-tiles under a 128-row tile do not
+// have the room: they store per lane, and the frozen-BatchNorm epilogue does not exist there
+template <int BM, int BN, int BK, int AK, int BKD, int PREC>
+constexpr bool gemm_stages_tile() {
+    if (PREC != 0) return true;
+    constexpr bool A_KC = (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K), B_KC = (BKD == VBG_OP_DENSE_K);
+    return BM * (BN + 4) <= 2 * ((A_KC ? BM * (BK + 4) : BK * (BM + 4)) + (B_KC ? BN * (BK + 4) : BK * (BN + 4)));
+}
+
 // PREC 3: fp32-grade products on the bf16 matrix cores.  Every operand element is split EXACTLY into three bf16 pieces
 // (x = hi + mid + lo: 8 + 8 + 8 significant bits, by truncation) held as three planes of the LDS tile, and a product is the sum
 // of the six piece products of order <= 2^-16 (hh, hm, mh, hl, lh, mm; each exact in fp32, accumulated in fp32).  The dropped
@@ -921,10 +931,36 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
     const bool atomic = accumulate && p.splitk > 1;
     const float alpha = p.alpha;
     const long long ldc = p.ldc;
+    // frozen BatchNorm of the finished tile (vbg_bn_epilogue; the host admits it with none of bias / epi / accumulate / split / groups and
+    // N % 4 == 0, aligned C): bn_apply_kernel's expression, term for term, on the value about to be stored.  It lives on the staged store
+    // path only; the host rejects the epilogue for the instances that cannot stage their tile (gemm_stages_tile above)
+    // (its seven words are read from the kernel-argument segment HERE, through a pointer the compiler cannot see through: read as
+    //  p.bn.* they are hoisted to the kernel's entry with every other argument and hold 14 scalar registers across the k-loop)
+    typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+    kernarg_ptr ka = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    const auto* const bnp = reinterpret_cast<const __attribute__((address_space(4))) vbg_bn_epilogue*>(ka + offsetof(vbg_gemm_desc, bn));
+    const float* const bn_mean = bnp->mean;
+    float bn_mx = 0.f;
+    auto bn_publish = [&]() {
+        // where the whole block arrives (the store loops `continue` past rows and columns outside the problem): block-wide max through
+        // the tile's LDS, one atomicMax on the bit pattern into word (linear block id) % 64 of the slot, as amax_publish (csrc/convaux.hip)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) bn_mx = fmaxf(bn_mx, __shfl_xor(bn_mx, o, 64));
+        __syncthreads();
+        if ((tid & 63) == 0) smem[tid >> 6] = bn_mx;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned bits = __float_as_uint(fmaxf(fmaxf(smem[0], smem[1]), fmaxf(smem[2], smem[3])));
+            unsigned* word = bnp->amax + (lin & (VBG_AMAX_WORDS - 1)) * VBG_AMAX_STRIDE;
+            if (bits > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, bits);
+        }
+    };
     // Plain stores go through LDS: the accumulator layout gives each lane single floats of 16 different rows (16 dword stores per
     // 32x32 tile, 128 contiguous bytes per row); staged through the (now idle) operand tiles, every thread writes float4s of
     // complete 64-float row pieces instead.  Output-bound products (attention scores, K = 64) are limited by exactly this.
     constexpr bool STAGE_OK = BM * CTS <= SMEM;
+    static_assert(STAGE_OK == gemm_stages_tile<BM, BN, BK, AK, BKD, PREC>(), "the host's rule for the BatchNorm epilogue is the kernel's");
     if (STAGE_OK && !atomic && (ldc & 3) == 0 && (((uintptr_t)C) & 15) == 0 && (epi != VBG_EPI_GELU_DUAL || (((uintptr_t)C2) & 15) == 0)) {
         __syncthreads();                                  // every wave is done with the operand tiles
         float* const Ct = smem;
@@ -952,6 +988,18 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
                 if (gn + 3 < N) v.w += bias[gn + 3];
             }
             float* cp = C + (long long)gm * ldc + gn;
+            if (bn_mean) {                                 // (N % 4 == 0, checked on the host: the float4 is inside the row)
+                const float4 mu = *reinterpret_cast<const float4*>(bn_mean + gn), is = *reinterpret_cast<const float4*>(bnp->invstd + gn);
+                const float4 ga = *reinterpret_cast<const float4*>(bnp->gamma + gn), be = *reinterpret_cast<const float4*>(bnp->beta + gn);
+                v.x = (v.x - mu.x) * is.x * ga.x + be.x; v.y = (v.y - mu.y) * is.y * ga.y + be.y;
+                v.z = (v.z - mu.z) * is.z * ga.z + be.z; v.w = (v.w - mu.w) * is.w * ga.w + be.w;
+                if (const float* const bn_res = bnp->res) {
+                    const float4 rv = *reinterpret_cast<const float4*>(bn_res + (long long)gm * ldc + gn);
+                    v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+                }
+                if (bnp->relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+                bn_mx = fmaxf(fmaxf(bn_mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            }
             if (p.stats) {                                 // (N % 4 == 0 is checked on the host when statistics are requested)
                 cs.x += v.x; cs.y += v.y; cs.z += v.z; cs.w += v.w;
                 cq.x += v.x * v.x; cq.y += v.y * v.y; cq.z += v.z * v.z; cq.w += v.w * v.w;
@@ -993,6 +1041,7 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
                 unsafeAtomicAdd(p.stats + (size_t)(tile_m % (unsigned)p.stats_slots) * 2 * N + (size_t)st * N + n0 + col, acc64);
             }
         }
+        if (bn_mean && bnp->amax) bn_publish();
         return;
     }
 #pragma unroll
@@ -1045,11 +1094,13 @@ __global__ __launch_bounds__(NT) void gemm_kernel(const vbg_gemm_desc p) {
 struct launch_timer { hipEvent_t start = nullptr, stop = nullptr; };
 
 template <int BM, int BN, int BK, int NT, int AK, int BKD, bool VEC, int PREC = 0>
-static void launch_one(const vbg_gemm_desc& d, int groups, int maxM, int maxN, hipStream_t s, const launch_timer& t) {
+static int launch_one(const vbg_gemm_desc& d, int groups, int maxM, int maxN, hipStream_t s, const launch_timer& t) {
+    if (d.bn.mean && !gemm_stages_tile<BM, BN, BK, AK, BKD, PREC>()) return VBG_EARG;      // never a launch that would skip the epilogue
     dim3 g(cdiv(maxM, BM), cdiv(maxN, BN), groups * d.splitk);
     (void)hipGetLastError();
     if (t.start && t.stop) hipExtLaunchKernelGGL((gemm_kernel<BM, BN, BK, NT, AK, BKD, VEC, PREC>), g, dim3(NT), 0, s, t.start, t.stop, 0, d);
     else hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, NT, AK, BKD, VEC, PREC>), g, dim3(NT), 0, s, d);
+    return VBG_OK;
 }
 
 // tile code: BM*1000+BN (128128, 128064, 64064); 0 = heuristic.  (A barrier-free one-wave-per-tile variant (NT = 64) was
@@ -1073,17 +1124,17 @@ static void pick_tile(const vbg_gemm_desc& d, int groups, int maxM, int maxN, in
 
 template <int AK, int BKD>
 static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, hipStream_t s, const launch_timer& t) {
-    int tile, bk;
+    int tile, bk, rc = VBG_OK;
     pick_tile(d, groups, maxM, maxN, tile, bk);
     if (!(d.a_vec && d.b_vec)) {                         // unaligned operands: general scalar-load path
-        launch_one<64, 64, 16, 256, AK, BKD, false>(d, groups, maxM, maxN, s, t);
+        rc = launch_one<64, 64, 16, 256, AK, BKD, false>(d, groups, maxM, maxN, s, t);
     } else if (d.bf16 == 2 && d.bk != 16 && (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K &&
                (d.tile == 0 ? !((long)cdiv(maxM, 128) * cdiv(maxN, 128) * groups * d.splitk >= 192 && maxN >= 128) : tile == 64064)) {
         // the fp16-pair form of the forward kinds (PREC 2), where the six-product form would run 64 x 64 tiles: 1024 x 1024 x 12544 163 -> 120 us,
         // the strided 3x3 convolutions 36 -> 29 / 41 -> 30 us.  On the 128 x 128 tiles it measured SLOWER than six products (131072 x 256 x 1024:
         // 391 -> 423 us; a second accumulator set on 304 registers, a VALU-heavier split): those keep PREC 3 (tools/gemm_f16_bench.py)
         if constexpr ((AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K)
-            launch_one<64, 64, 32, 256, AK, BKD, true, 2>(d, groups, maxM, maxN, s, t);
+            rc = launch_one<64, 64, 32, 256, AK, BKD, true, 2>(d, groups, maxM, maxN, s, t);
     } else if ((d.bf16 == 3 || d.bf16 == 2) && d.bk != 16 &&
                (AK != VBG_OP_DENSE_R || d.tile != 0 || BKD == VBG_OP_DENSE_R ||
                 (BKD == VBG_OP_CONV_R && d.K / d.splitk >= 2048 && maxM >= 128 && maxN >= 128))) {
@@ -1099,9 +1150,9 @@ static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, h
             if (AK == VBG_OP_DENSE_R) tile = (BKD == VBG_OP_CONV_R) ? 128132 : 64064;
             else tile = (t128 >= 192 && maxN >= 128) ? (t128 <= 256 ? 128132 : 128128) : 64064;
         }
-        if (tile == 128132 || (tile == 128128 && d.bk == 32)) launch_one<128, 128, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128128) launch_one<128, 128, 16, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
-        else launch_one<64, 64, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
+        if (tile == 128132 || (tile == 128128 && d.bk == 32)) rc = launch_one<128, 128, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
+        else if (tile == 128128) rc = launch_one<128, 128, 16, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
+        else rc = launch_one<64, 64, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
     } else if (d.bf16 == 1 && (d.bk == 0 || d.bk == 32)) {
         // amp: bf16 matrix cores (fp32 operands rounded on the way into LDS).  The loop is bound by operand traffic, not by the
         // MFMAs, so the larger tile wins as soon as it fills the chip.  (Products forced to 16-deep k-tiles -- channel counts
@@ -1116,17 +1167,18 @@ static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, h
             else big = t128 * d.splitk >= 512 && maxN >= 256;
             tile = big ? 128128 : 64064;
         }
-        if (tile == 128128) launch_one<128, 128, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
-        else launch_one<64, 64, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
+        if (tile == 128128) rc = launch_one<128, 128, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
+        else rc = launch_one<64, 64, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
     } else if (bk == 32) {
-        if (tile == 128128) launch_one<128, 128, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128064) launch_one<128, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else launch_one<64, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        if (tile == 128128) rc = launch_one<128, 128, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        else if (tile == 128064) rc = launch_one<128, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        else rc = launch_one<64, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
     } else {
-        if (tile == 128128) launch_one<128, 128, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128064) launch_one<128, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else launch_one<64, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        if (tile == 128128) rc = launch_one<128, 128, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        else if (tile == 128064) rc = launch_one<128, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        else rc = launch_one<64, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
     }
+    if (rc != VBG_OK) return rc;
     VBG_LAUNCH_RET();
 }
 
@@ -1151,6 +1203,13 @@ static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::lau
     if (d.stats) {          // fused output statistics ride on the LDS-staged store path of an unsplit, non-accumulating launch
         VBG_CHECK_ARG(d.stats_slots >= 1 && d.splitk == 1 && !d.accumulate && d.grp == nullptr && d.N % 4 == 0 && d.ldc % 4 == 0 &&
                       (uintptr_t)d.C % 16 == 0 && d.epi == VBG_EPI_NONE);
+    }
+    if (d.bn.mean) {        // frozen-BatchNorm epilogue: the last thing that happens to an unsplit, single-problem product's tile
+        const vbg_bn_epilogue& e = d.bn;
+        VBG_CHECK_ARG(e.invstd && e.gamma && e.beta && !d.stats && !d.accumulate && d.splitk == 1 && d.slab_stride == 0 && d.grp == nullptr &&
+                      !d.C2 && d.epi == VBG_EPI_NONE && !d.bias && d.N % 4 == 0 && d.ldc % 4 == 0);
+        VBG_CHECK_ARG(((uintptr_t)d.C | (uintptr_t)e.res | (uintptr_t)e.mean | (uintptr_t)e.invstd | (uintptr_t)e.gamma | (uintptr_t)e.beta) % 16 == 0);
+        VBG_CHECK_ARG(e.res != d.C);
     }
     if (d.a_nseg == 0) {
         d.a_nseg = 1; d.a_seg_ptr[0] = d.A; d.a_seg_kend[0] = d.K; d.a_seg_ld[0] = d.lda; d.a_seg_shift[0] = 0;

@@ -261,10 +261,11 @@ class SegLinearFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------
-def _conv_any(x, w4, stride, pad, bias=None, want_stats=False, w_owner=None, x_amax=None, zero_slots=False):
+def _conv_any(x, w4, stride, pad, bias=None, want_stats=False, w_owner=None, x_amax=None, zero_slots=False, bn=None):
     """x NHWC; w4 = OHWI weight.  Cin=3 stem goes through im2col (K=147, row stride 148).
     want_stats: -> third result = BatchNorm slot workspace holding the output's column sums / sums of squares (fused into the GEMM
-    epilogue), or None when the product is one the library may split (the caller then runs ops.bn_stats)."""
+    epilogue), or None when the product is one the library may split (the caller then runs ops.bn_stats).
+    bn: an ops.BnEpi -- frozen BatchNorm of the output in the epilogue of the one launch (the stem's im2col product included)."""
     B, H, W, Cin = x.shape
     Cout, kh, kw, _ = w4.shape
     K = kh * kw * Cin
@@ -276,9 +277,9 @@ def _conv_any(x, w4, stride, pad, bias=None, want_stats=False, w_owner=None, x_a
         Kp = (K + 3) // 4 * 4
         col = ops.im2col(x, kh, kw, stride, pad, Kp)
         out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=f32)
-        ops.gemm_raw(B * Ho * Wo, Cout, K, col, Kp, OP_DENSE_K, w4, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats)
+        ops.gemm_raw(B * Ho * Wo, Cout, K, col, Kp, OP_DENSE_K, w4, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, bn=bn)
         return out, col, stats
-    return ops.conv2d_fwd(x, w4, stride, pad, bias, stats=stats, w_owner=w_owner, x_amax=x_amax), None, stats
+    return ops.conv2d_fwd(x, w4, stride, pad, bias, stats=stats, w_owner=w_owner, x_amax=x_amax, bn=bn), None, stats
 
 
 def _conv_wgrad_any(dy, x, col, w4_shape, stride, pad, w_param=None, dy_amax=None, x_amax=None):
@@ -376,6 +377,16 @@ class ConvBnFn(torch.autograd.Function):
         w4 = ohwi(w)
         # one rank, training statistics: finalize rides in the apply kernel's prologue, the affine-gradient fold in the backward apply's
         fold = training and ops.bn_fold_ok(w.shape[0], sync)
+        if ops.bn_epilogue_route(training, ctx.needs_input_grad, sync):
+            # frozen statistics and no backward to come (inference(), the eval forward under no_grad): the BatchNorm, the residual, the
+            # ReLU and the amax word ride in the convolution's epilogue -- one launch, no z, nothing kept
+            y_amax = ops.amax_slot(x.device) if ops.conv3_f16_enabled() else None
+            r = None if res is None else _c(res)
+            y, _, _ = _conv_any(x, w4, stride, pad, w_owner=w, x_amax=ctx.x_amax,
+                                bn=ops.BnEpi(running_mean, _frozen_invstd(running_var, eps), gamma, beta, r, relu, y_amax))
+            if y_amax is not None:
+                y._vbg_amax = (y_amax, y._version)
+            return y
         z, col, stats = _conv_any(x, w4, stride, pad, want_stats=training, w_owner=w, x_amax=ctx.x_amax, zero_slots=fold)
         C = z.shape[-1]
         z2 = z.view(-1, C)

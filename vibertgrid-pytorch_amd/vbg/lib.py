@@ -22,6 +22,10 @@ class ConvGeo(C.Structure):
                 ("stride", c_int), ("pad", c_int), ("dgrad", c_int)]
 
 
+class BnEpilogue(C.Structure):               # include/vbg.h vbg_bn_epilogue
+    _fields_ = [("mean", c_vp), ("invstd", c_vp), ("gamma", c_vp), ("beta", c_vp), ("res", c_vp), ("relu", c_int), ("amax", c_vp)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", c_int), ("N", c_int), ("K", c_int),
                 ("A", c_vp), ("lda", c_ll), ("a_kind", c_int), ("a_vec", c_int),
@@ -33,7 +37,8 @@ class GemmDesc(C.Structure):
                 ("C", c_vp), ("ldc", c_ll), ("C2", c_vp), ("bias", c_vp),
                 ("epi", c_int), ("alpha", c_f), ("accumulate", c_int), ("splitk", c_int), ("tile", c_int),
                 ("grp", c_vp), ("ngroups", c_int), ("grp_maxM", c_int), ("grp_maxN", c_int), ("bk", c_int),
-                ("stats", c_vp), ("stats_slots", c_int), ("bf16", c_int), ("slab_stride", c_ll)]
+                ("stats", c_vp), ("stats_slots", c_int), ("bf16", c_int), ("slab_stride", c_ll),
+                ("bn", BnEpilogue)]
 
 
 class Conv3WprepEntry(C.Structure):          # include/vbg.h vbg_conv3_wprep_entry
@@ -122,6 +127,7 @@ SIGNATURES = {
     "vbg_colsum": (c_int, [c_vp, c_ll, c_int, c_int, c_vp, c_int, c_vp]),
     "vbg_colsum_f64": (c_int, [c_vp, c_ll, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_conv3x3": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
+    "vbg_conv3x3_bn": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     "vbg_conv3x3_split": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "vbg_conv3x3_pw": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
     "vbg_conv3x3_pw_amp": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),

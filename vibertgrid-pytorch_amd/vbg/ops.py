@@ -8,7 +8,7 @@ import os
 import torch
 
 from .lib import (ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AttnDesc, BertLayerFwdDesc, GemmDesc, PlaneGemmDesc, check, lib)
+                  AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, PlaneGemmDesc, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -145,11 +145,50 @@ def set_gemm_f16(on: bool):
     _GEMM_F16[0] = bool(on)
 
 
+_BN_EPILOGUE = [os.environ.get("VBG_BN_EPILOGUE", "0") not in ("", "0")]
+
+
+def set_bn_epilogue(on: bool):
+    """frozen BatchNorm (+ residual, ReLU, amax) as the EPILOGUE of the convolution in front of it on calls that no backward can follow
+    (inference(), the eval forward under no_grad): one launch instead of convolution + bn_apply.  Off by default: the fused value may
+    differ from the two-launch value in the last bit (the compiler contracts the same expression on its own in either kernel)."""
+    _BN_EPILOGUE[0] = bool(on)
+
+
+def bn_epilogue_enabled() -> bool:
+    return _BN_EPILOGUE[0]
+
+
+def bn_epilogue_route(training, needs_input_grad, sync, on=None) -> bool:
+    """does a conv + BatchNorm node take the fused launch?  Only with frozen statistics, on one rank's own numbers, and when no backward
+    can come (the fused launch keeps neither z nor anything else for one) -- a frozen BatchNorm inside a training step keeps two launches"""
+    on = _BN_EPILOGUE[0] if on is None else bool(on)
+    return bool(on) and not training and not any(needs_input_grad) and not sync
+
+
+class BnEpi:
+    """the arguments of a frozen-BatchNorm epilogue (include/vbg.h vbg_bn_epilogue): per-channel mean / invstd / gamma / beta [N], the
+    residual in the output's shape (or None), ReLU, and a zeroed amax slot that receives the bits of max |y| (or None)"""
+    __slots__ = ("mean", "invstd", "gamma", "beta", "res", "relu", "amax")
+
+    def __init__(self, mean, invstd, gamma, beta, res=None, relu=False, amax=None):
+        _chk_f32(mean, invstd, gamma, beta, res)
+        self.mean, self.invstd, self.gamma, self.beta, self.res, self.relu, self.amax = mean, invstd, gamma, beta, res, bool(relu), amax
+
+    def fill(self, e):
+        e.mean, e.invstd, e.gamma, e.beta = self.mean.data_ptr(), self.invstd.data_ptr(), self.gamma.data_ptr(), self.beta.data_ptr()
+        e.res = None if self.res is None else self.res.data_ptr()
+        e.relu = int(self.relu)
+        e.amax = None if self.amax is None else self.amax.data_ptr()
+        return e
+
+
 def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, epi=EPI_NONE, C2=None, accumulate=False,
              splitk=1, geo=None, segs=None, a_hw=(0, 0), a_relu_scale=None, grp=None, ngroups=0, grp_max=(0, 0), tile=0,
-             alpha=1.0, a_ptr_off=0, b_ptr_off=0, c_ptr_off=0, bk=0, stats=None, slab_stride=0, f16=False):
+             alpha=1.0, a_ptr_off=0, b_ptr_off=0, c_ptr_off=0, bk=0, stats=None, slab_stride=0, f16=False, bn=None):
     """A, B, Cout: tensors (their data_ptr + element offsets are used).  stats: BatchNorm slot workspace [slots*2N] fp64 that receives the
-    per-column sum / sum of squares of the output (fused into the epilogue; the launch is then never split)."""
+    per-column sum / sum of squares of the output (fused into the epilogue; the launch is then never split).  bn: a BnEpi -- frozen
+    BatchNorm of the output in the epilogue (the launch is never split; the library rejects what cannot go with it)."""
     d = GemmDesc()
     d.M, d.N, d.K = int(M), int(N), int(K)
     ap = A.data_ptr() + 4 * a_ptr_off
@@ -178,7 +217,11 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
     d.bias = None if bias is None else bias.data_ptr()
     if stats is not None:
         d.stats, d.stats_slots = stats.data_ptr(), bn_slots()
-    if splitk == 1 and not accumulate and torch.is_grad_enabled() and stats is None:
+    if bn is not None:
+        bn.fill(d.bn)
+        _seen("bn:epilogue")
+        _seen("bn:epilogue_gemm")
+    if splitk == 1 and not accumulate and torch.is_grad_enabled() and stats is None and bn is None:
         splitk = 0          # training: let the library split few-tile / long-K products; no_grad (inference, eval) stays bit-reproducible
     if splitk == 0 and accumulate:
         splitk = 1
@@ -930,11 +973,13 @@ def _conv3_tickets(device, tiles):
     return t
 
 
-def conv3x3(x, w_ohwi, bias=None, out=None, stats=None, accumulate=False, f16x2=False, x_amax=None, nsplit=None, w_planes=None, n_out=None, bn=0):
+def conv3x3(x, w_ohwi, bias=None, out=None, stats=None, accumulate=False, f16x2=False, x_amax=None, nsplit=None, w_planes=None, n_out=None, bn=0,
+            bn_epi=None):
     """y (+)= conv3x3(x NHWC, w [N,3,3,Cs]), stride 1, pad 1 (csrc/conv3.hip).  f16x2: the two-piece fp16 form -- for operands inside
     fp16's range (activations, filters); a gradient operand x needs x_amax (device word with the bits of max |x|): the kernel then
     scales x by the power of two that centres it in fp16's range and the result back (exact).  nsplit: workgroups per tile (None: the
-    library's choice for the shape)"""
+    library's choice for the shape).  bn_epi: a BnEpi -- frozen BatchNorm of the output in the epilogue (vbg_conv3x3_bn; no bias /
+    stats / accumulate)"""
     B, H, W, Cs = x.shape
     N = w_ohwi.shape[0] if n_out is None else int(n_out)
     if out is None:
@@ -966,7 +1011,21 @@ def conv3x3(x, w_ohwi, bias=None, out=None, stats=None, accumulate=False, f16x2=
         ev[0].record()
     if stats is not None:
         _seen("fatomic:conv3_stats")
-    if w_planes is not None:                 # the filter as pre-split fp16-pair planes (conv3_planes): no filter work in the kernel
+    if bn_epi is not None:
+        if bias is not None or stats is not None or accumulate:
+            raise VbgError("vbg_conv3x3_bn failed: argument error (no bias / stats / accumulate with a BatchNorm epilogue)")
+        _seen("bn:epilogue")
+        _seen("bn:epilogue_conv3")
+        onep = w_planes is not None and _AMP[0] and _AMP_FAST[0]
+        if w_planes is not None:
+            _seen("conv3:pw")
+            if onep:
+                _seen("conv3:onep")
+        e = bn_epi.fill(BnEpilogue())
+        check(lib.vbg_conv3x3_bn(P(x), None if w_planes is not None else P(w_ohwi), P(w_planes), P(out), B, H, W, Cs, N,
+                                 (2 if onep else 1) if w_planes is not None else int(bool(f16x2)), P(x_amax), P(slab), P(tickets), nz, int(bn),
+                                 C.byref(e), _stream()), "vbg_conv3x3_bn")
+    elif w_planes is not None:               # the filter as pre-split fp16-pair planes (conv3_planes): no filter work in the kernel
         _seen("conv3:pw")
         onep = _AMP[0] and _AMP_FAST[0]       # autocast region: the hi pieces only, one product
         if onep:
@@ -1194,8 +1253,9 @@ def conv3x3_wgrad(dy, x, dw_ohwi, slabs=True, f16x2=False, dy_amax=None, x_amax=
     return dw_ohwi
 
 
-def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=None, x_amax=None):
-    """x NHWC [B,H,W,Cin] contiguous; w_ohwi [Cout,kh,kw,Cin] contiguous -> y NHWC [B,Ho,Wo,Cout]."""
+def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=None, x_amax=None, bn=None):
+    """x NHWC [B,H,W,Cin] contiguous; w_ohwi [Cout,kh,kw,Cin] contiguous -> y NHWC [B,Ho,Wo,Cout].  bn: a BnEpi -- frozen BatchNorm
+    (+ residual, ReLU, amax) of the output in the epilogue of whichever kernel takes the convolution."""
     _chk_f32(x, w_ohwi, bias)
     B, H, W, Cin = x.shape
     Cout, kh, kw, _ = w_ohwi.shape
@@ -1209,17 +1269,17 @@ def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=
         if late is not None:
             wp = conv3_planes(w_owner, w_ohwi, False, bn=late[0])
             if wp is not None:
-                return conv3x3(x, w_ohwi, bias, out, stats, f16x2=True, w_planes=wp, x_amax=x_amax, nsplit=late[1], bn=late[0])
+                return conv3x3(x, w_ohwi, bias, out, stats, f16x2=True, w_planes=wp, x_amax=x_amax, nsplit=late[1], bn=late[0], bn_epi=bn)
         wp = conv3_planes(w_owner, w_ohwi, False) if (_CONV3_F16[0] and conv3_pw_ok(B, H, W, Cin, Cout)) else None
         # x_amax: the producer's amax slot of the activation, when it published one (bn_apply in a training step).  The fp16 form then
         # scales x by the power of two that centres its largest magnitude in fp16's range, like a gradient operand: an activation of
         # 65520 or more no longer becomes inf, and small activations keep more bits -- exact either way
-        return conv3x3(x, w_ohwi, bias, out, stats, f16x2=_CONV3_F16[0], w_planes=wp, x_amax=x_amax if _CONV3_F16[0] else None)
+        return conv3x3(x, w_ohwi, bias, out, stats, f16x2=_CONV3_F16[0], w_planes=wp, x_amax=x_amax if _CONV3_F16[0] else None, bn_epi=bn)
     if kh == 1 and kw == 1 and stride == 1 and pad == 0:
-        gemm_raw(M, Cout, K, x, Cin, OP_DENSE_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, f16=True)
+        gemm_raw(M, Cout, K, x, Cin, OP_DENSE_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, f16=True, bn=bn)
     else:
         gemm_raw(M, Cout, K, x, Cin, OP_CONV_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias,
-                 geo=conv_geo(H, W, Cin, Ho, Wo, kh, kw, stride, pad, 0), stats=stats, f16=True)
+                 geo=conv_geo(H, W, Cin, Ho, Wo, kh, kw, stride, pad, 0), stats=stats, f16=True, bn=bn)
     return out
 
 
@@ -1892,6 +1952,7 @@ def bn_apply(x2d, res2d, mean, invstd, gamma, beta, relu, out=None, y_amax=None)
     M, C_ = x2d.shape
     if out is None:
         out = torch.empty_like(x2d)
+    _seen("bn:apply")
     check(lib.vbg_bn_apply(P(x2d), P(res2d), M, C_, P(mean), P(invstd), P(gamma), P(beta), int(relu), P(out), P(y_amax), _stream()), "vbg_bn_apply")
     return out
 

@@ -45,7 +45,9 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, long long ld, in
         float s = 0.f;
         for (int c = 0; c < ncls; ++c) s += expf(x[c] - mx);
         const float lp = (x[t] - mx) - logf(s);
-        loss[i] = -(weight ? weight[t] : 1.f) * lp;
+        // lp <= 0, its zero is +0: `0 - w * lp` makes every zero loss +0.  `-w * lp` gave -0 for a saturated row and +0 for a class of weight
+        // 0; the OHEM selection must tie them as torch's comparison sort does, whether or not the radix sort folds the two zeros together
+        loss[i] = 0.f - (weight ? weight[t] : 1.f) * lp;
     }
 }
 

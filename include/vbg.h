@@ -643,6 +643,21 @@ int vbg_sgd_step(float* p, const float* g, float* mom, long long n, float lr, fl
                  int first_step, float grad_scale, void* stream);
 int vbg_adamw_step(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
                    float eps, float wd, int step, float grad_scale, void* stream);
+/* The same two steps with per-group hyper-parameters (torch param groups) in ONE launch.  `chunks` (device memory, 16-byte
+ * aligned) lists the work: chunk k updates elements [start, start + length) with the hyper-parameters of groups[group]; start and
+ * length are multiples of 4 elements, chunks do not overlap, and p / g / mom / m / v are 16-byte aligned.  Blocks stride over
+ * the chunks, so the host bounds the work per block by cutting every run of equal group into chunks of a bounded length.
+ * `groups` is HOST memory (1 <= ngroups <= VBG_OPTIM_MAX_GROUPS), copied into the kernel arguments: no device copy, no sync.
+ * Elements no chunk covers are neither read nor written.  first_step / step / grad_scale are shared by all groups; the AdamW
+ * bias corrections 1 - b^step are formed per group in double, as vbg_adamw_step forms them.  nchunks == 0 is a no-op. */
+#define VBG_OPTIM_MAX_GROUPS 32
+typedef struct { long long start; int length; int group; } vbg_optim_chunk;
+typedef struct { float lr, momentum, wd; } vbg_sgd_group;
+typedef struct { float lr, b1, b2, eps, wd; } vbg_adamw_group;
+int vbg_sgd_step_seg(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
+                     const vbg_sgd_group* groups, int ngroups, int first_step, float grad_scale, void* stream);
+int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, const vbg_optim_chunk* chunks, int nchunks,
+                       const vbg_adamw_group* groups, int ngroups, int step, float grad_scale, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

@@ -98,6 +98,19 @@ class BertLayerFwdDesc(C.Structure):         # include/vbg.h vbg_bert_layer_fwd_
                 ("fo", c_vp), ("y", c_vp), ("xhat2", c_vp), ("rstd2", c_vp), ("py", PlanesRef), ("pyq", PlanesRef)]
 
 
+class OptimChunk(C.Structure):               # include/vbg.h vbg_optim_chunk
+    _fields_ = [("start", c_ll), ("length", c_int), ("group", c_int)]
+
+
+class SgdGroup(C.Structure):                 # include/vbg.h vbg_sgd_group
+    _fields_ = [("lr", c_f), ("momentum", c_f), ("wd", c_f)]
+
+
+class AdamwGroup(C.Structure):               # include/vbg.h vbg_adamw_group
+    _fields_ = [("lr", c_f), ("b1", c_f), ("b2", c_f), ("eps", c_f), ("wd", c_f)]
+
+
+OPTIM_MAX_GROUPS = 32                        # include/vbg.h VBG_OPTIM_MAX_GROUPS
 ATTN_FWD, ATTN_DQ, ATTN_DKV = 0, 1, 2
 OP_DENSE_K, OP_DENSE_R, OP_CONV_K, OP_CONV_R, OP_WT_R = 0, 1, 2, 3, 4
 EPI_NONE, EPI_RELU, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD = 0, 1, 2, 3
@@ -201,6 +214,8 @@ SIGNATURES = {
     "vbg_crf_viterbi": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),
+    "vbg_sgd_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroup), c_int, c_int, c_f, c_vp]),
+    "vbg_adamw_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamwGroup), c_int, c_int, c_f, c_vp]),
     "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
     "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_sum_det_ws_elems": (c_int, []),

@@ -8,7 +8,7 @@ import os
 import torch
 
 from .lib import (ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, PlaneGemmDesc, VbgError, check, lib)
+                  AdamwGroup, AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -2304,3 +2304,60 @@ def sgd_step(p, g, mom, lr, momentum, wd, first, grad_scale=1.0):
 
 def adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale=1.0):
     check(lib.vbg_adamw_step(P(p), P(g), P(m), P(v), p.numel(), lr, b1, b2, eps, wd, step, grad_scale, _stream()), "vbg_adamw_step")
+
+
+class ChunkTable:
+    """the work list of a segmented optimizer step: rows (start, length, group) in device memory (include/vbg.h vbg_optim_chunk), with
+    what the launch has to hold the buffers against -- `numel` (no chunk reaches past it) and `ngroups` (every row's group is below it)"""
+
+    def __init__(self, rows, n, ngroups, numel):
+        self.rows, self.n, self.ngroups, self.numel = rows, n, ngroups, numel
+
+
+def chunk_table(chunks, ngroups, numel, device):
+    """ChunkTable of `chunks` ([n, 3] integers: start, length, group) for buffers of `numel` elements.  The kernels trust the table, so
+    it is checked here, once, where it is built: starts and lengths multiples of 4 (float4 access), lengths positive, chunks inside the
+    buffers and disjoint, groups in [0, ngroups)."""
+    import numpy as np
+    c = np.asarray(chunks, dtype=np.int64).reshape(-1, 3)
+    if not 1 <= ngroups <= OPTIM_MAX_GROUPS:
+        raise ValueError(f"{ngroups} groups: the segmented optimizer steps take 1 .. {OPTIM_MAX_GROUPS}")
+    if len(c):
+        start, length, group = c[:, 0], c[:, 1], c[:, 2]
+        if (start % 4).any() or (length % 4).any() or (length <= 0).any() or (length >= 1 << 31).any():
+            raise ValueError("chunk starts and lengths must be multiples of 4 elements, lengths in (0, 2^31)")
+        if (start < 0).any() or (start + length > numel).any():
+            raise ValueError(f"a chunk lies outside the buffers ({numel} elements)")
+        if (group < 0).any() or (group >= ngroups).any():
+            raise ValueError(f"chunk group outside [0, {ngroups})")
+        o = np.argsort(start, kind="stable")
+        if (start[o][1:] < (start + length)[o][:-1]).any():
+            raise ValueError("chunks overlap")
+    if len(c) >= 1 << 31:
+        raise ValueError("too many chunks")
+    packed = np.zeros((len(c),), dtype=np.dtype([("start", "<i8"), ("length", "<i4"), ("group", "<i4")]))
+    packed["start"], packed["length"], packed["group"] = c[:, 0], c[:, 1], c[:, 2]
+    rows = torch.from_numpy(packed.view(np.int32).reshape(-1, 4).copy()).to(device)
+    return ChunkTable(rows, len(c), int(ngroups), int(numel))
+
+
+def _seg_args(table, groups, *bufs):
+    if len(groups) != table.ngroups:
+        raise ValueError(f"{len(groups)} sets of hyper-parameters for a chunk table over {table.ngroups} groups")
+    for b in bufs:
+        if b.dtype != f32 or not b.is_contiguous() or b.numel() < table.numel or b.device != table.rows.device:
+            raise ValueError("segmented optimizer step: contiguous fp32 buffers on the table's device, at least as long as the table's numel")
+
+
+def sgd_step_seg(p, g, mom, table, groups, first, grad_scale=1.0):
+    """vbg_sgd_step_seg: groups = [(lr, momentum, weight_decay)] per group of `table` (a ChunkTable); one launch"""
+    _seg_args(table, groups, p, g, mom)
+    hp = (SgdGroup * len(groups))(*[SgdGroup(*map(float, h)) for h in groups])
+    check(lib.vbg_sgd_step_seg(P(p), P(g), P(mom), P(table.rows), table.n, hp, len(groups), int(first), grad_scale, _stream()), "vbg_sgd_step_seg")
+
+
+def adamw_step_seg(p, g, m, v, table, groups, step, grad_scale=1.0):
+    """vbg_adamw_step_seg: groups = [(lr, beta1, beta2, eps, weight_decay)] per group of `table` (a ChunkTable); one launch"""
+    _seg_args(table, groups, p, g, m, v)
+    hp = (AdamwGroup * len(groups))(*[AdamwGroup(*map(float, h)) for h in groups])
+    check(lib.vbg_adamw_step_seg(P(p), P(g), P(m), P(v), P(table.rows), table.n, hp, len(groups), int(step), grad_scale, _stream()), "vbg_adamw_step_seg")

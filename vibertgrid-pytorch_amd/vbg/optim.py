@@ -7,7 +7,9 @@ pipeline/train_val_utils.py:272-284, designed for MI355X instead of translated:
 * every trainable parameter of a group lives in ONE flat fp32 buffer (so do its gradient and optimizer
   state); `param.data` / `param.grad` are views, conv weights keep their channels_last (OHWI) memory;
 * `zero_grad` is one memset, each optimizer step is ONE HIP launch over the flat range
-  (libvbg `vbg_sgd_step` / `vbg_adamw_step`, 20 / 28 B per parameter);
+  (libvbg `vbg_sgd_step` / `vbg_adamw_step`, 20 / 28 B per parameter); with several torch param groups (no weight decay on biases
+  and LayerNorm weights, layer-wise learning rates) it is still ONE launch: `vbg_sgd_step_seg` / `vbg_adamw_step_seg` walk a chunk
+  table over the same buffers and take every group's hyper-parameters by value;
 * data parallel: the flat gradient buffer is cut into large contiguous buckets; a bucket is all-reduced
   (RCCL over xGMI, async, its own stream) as soon as autograd has accumulated its last gradient, so the
   exchange overlaps the rest of backward; no bucket copies (gradients ARE the bucket); the 1/world
@@ -369,6 +371,73 @@ def _torch_defaults(cls, **kw):
     return dict(cls([torch.nn.Parameter(torch.zeros(1))], **kw).defaults)
 
 
+SEG_CHUNK = 4096          # elements per row of the chunk table (16 KB per buffer: 4 float4 trips of a 256-thread block)
+MAX_GROUPS = ops.OPTIM_MAX_GROUPS
+_UNSUPPORTED = (("nesterov", False), ("dampening", 0), ("amsgrad", False), ("maximize", False))
+
+
+class ParamGroups(list):
+    """[{"params": [(name, parameter), ...], **overrides}] that remembers the one list the groups were cut from (`layout`: the
+    model's registration order), which decides the order of the flat buffers -- the groups themselves never do"""
+    layout = None
+
+
+def decay_groups(named, no_decay=("bias", "LayerNorm.weight"), **no_decay_overrides):
+    """The two param groups of the usual fine-tuning split, for FusedAdamW / FusedSGD: parameters whose name contains one of the
+    `no_decay` fragments go into the second group, which overrides `weight_decay=0.0` (or whatever `no_decay_overrides` says
+    instead); everything else keeps the constructor's defaults:
+
+        opt = FusedAdamW(decay_groups(bert_named), device, lr=5e-5, weight_decay=0.01)
+
+    A layer-wise list is built the same way, keyed on the `layer.N.` part of the name -- one dict per layer (times the decay split,
+    if wanted), at most 32 dicts in all:
+
+        def depth(name):                                   # embeddings 0, encoder layer N -> N + 1
+            return int(name.split("layer.")[1].split(".")[0]) + 1 if "layer." in name else 0
+        groups = [{"params": [(n, p) for n, p in named if depth(n) == d], "lr": 5e-5 * 0.9 ** (12 - d)} for d in range(13)]
+
+    The groups only choose hyper-parameters: the flat layout, the gradient buckets and the single launch stay as they are.  The
+    list returned here remembers `named`, so a flat buffer the optimizer has to create is laid out as for the single list; with a
+    hand-built list pass `layout=named` to the optimizer for the same effect (otherwise the layout follows the groups in the order
+    given -- correct, but the gradient buckets of FlatReducer then no longer fill in backward order)."""
+    named = list(named)
+    if not no_decay_overrides:
+        no_decay_overrides = {"weight_decay": 0.0}
+    plain = [(n, p) for n, p in named if not any(k in n for k in no_decay)]
+    bare = [(n, p) for n, p in named if any(k in n for k in no_decay)]
+    groups = ParamGroups([{"params": plain}, {"params": bare, **no_decay_overrides}])
+    groups.layout = named
+    return groups
+
+
+def run_table(group: FlatGroup, group_of: Dict[int, int]):
+    """[(start, length, group)] over the flat layout: consecutive slots of the same param group merge into one run, a run covers its
+    slots' padding (slots are padded to 8 elements), and nothing covers [end of the last slot, total).  group_of: id(param) -> index"""
+    runs = []
+    for p, off in zip(group.params, group.offsets):
+        k, end = group_of[id(p)], off + (p.numel() + 7) // 8 * 8
+        if runs and runs[-1][2] == k and runs[-1][0] + runs[-1][1] == off:
+            runs[-1][1] = end - runs[-1][0]
+        else:
+            runs.append([off, end - off, k])
+    return [tuple(r) for r in runs]
+
+
+def chunk_rows(runs, chunk: int):
+    """the runs cut into rows (start, length, group) of at most `chunk` elements ([n, 3] int64): the kernels give one block a row at a
+    time, so the work per block is bounded by `chunk`, not by the longest run"""
+    import numpy as np
+    if chunk < 4 or chunk % 4:
+        raise ValueError("chunk length: a positive multiple of 4 elements")
+    runs = np.asarray(runs, dtype=np.int64).reshape(-1, 3)
+    per = (runs[:, 1] + chunk - 1) // chunk
+    which = np.repeat(np.arange(len(runs)), per)
+    k = np.arange(len(which)) - np.repeat(np.cumsum(per) - per, per)          # index of the row inside its run
+    start = runs[which, 0] + k * chunk
+    length = np.minimum(chunk, runs[which, 0] + runs[which, 1] - start)
+    return np.stack([start, length, runs[which, 2]], axis=1)
+
+
 class _FlatOptimizer(torch.optim.Optimizer):
     """A torch.optim.Optimizer whose parameters, gradients and state live in flat buffers and whose step is one HIP launch.
     Being an Optimizer, it plugs into the reference's loop unchanged: `StepLR(optimizer=...)` (train_SROIE.py:247) and
@@ -378,13 +447,49 @@ class _FlatOptimizer(torch.optim.Optimizer):
     (train_SROIE.py:377-416 saves them, resume loads them).
     One deliberate difference: the step is element-wise over the whole flat range, so a parameter that received NO gradient in a
     step still gets weight decay / momentum applied (torch skips `grad is None` parameters).  On this model that only concerns the
-    per-class nets of classifier_mode full in steps where no segment was predicted positive."""
+    per-class nets of classifier_mode full in steps where no segment was predicted positive.
+
+    Two things are called "group" here and they are different: `self.group` is the FlatGroup, the ONE flat buffer all parameters of
+    this optimizer live in (what FlatReducer, clip_grad_norm_ and the model's plane caches work on); `self.param_groups` are torch's
+    param groups, sets of parameters that share hyper-parameters.  The constructor takes either one list of (name, parameter) pairs
+    (one param group) or a list of dicts `{"params": [(name, p), ...], "lr": ..., "weight_decay": ...}` with torch's own keys, one
+    param group each; missing keys take the constructor's defaults.  All param groups live in the one FlatGroup, whose layout does not
+    depend on them; `step()` reads every param group's current values on each call (schedulers, per-step weight-decay schedules) and
+    hands them to one segmented launch.  With one param group the step is the plain whole-range launch.  Checkpoints of several
+    groups number the parameters group by group in the order given, as torch.optim does for the same groups.  Flat storage is fixed
+    at construction: `add_param_group` afterwards raises.  seg_chunk: elements per row of the chunk table (default SEG_CHUNK); layout: the
+    (name, parameter) list that orders a flat buffer created here (decay_groups() supplies it; default: the groups in the order given)."""
 
     _state_names: Tuple[str, ...] = ()
 
-    def __init__(self, named, device, defaults: Dict):
-        ref = getattr(named, "ref_names", None)
-        named = list(named)
+    def __init__(self, named, device, defaults: Dict, seg_chunk=None, layout=None):
+        if layout is None:
+            layout = getattr(named, "layout", None)
+        named = list(named) if not hasattr(named, "ref_names") else named
+        if len(named) > 0 and isinstance(named[0], dict):
+            dicts = [dict(d) for d in named]
+            if len(dicts) > MAX_GROUPS:
+                raise ValueError(f"{len(dicts)} param groups: one segmented launch carries at most {MAX_GROUPS}")
+            seen = set()
+            for k, d in enumerate(dicts):
+                if "params" not in d or len(d["params"]) == 0:
+                    raise ValueError(f"param group {k} is empty")
+                for n, p in d["params"]:
+                    if id(p) in seen:
+                        raise ValueError(f"parameter {n} appears in more than one param group")
+                    seen.add(id(p))
+                self._check_options({**defaults, **{k2: v for k2, v in d.items() if k2 != "params"}})
+        else:
+            dicts = [{"params": named}]
+        self._check_options(defaults)
+        # the single list keeps the reference's indices (NamedParams.ref_names); several groups are numbered group by group
+        ref = getattr(dicts[0]["params"], "ref_names", None) if len(dicts) == 1 else None
+        named = [np_ for d in dicts for np_ in d["params"]]
+        flat_named = named
+        if layout is not None:              # the order of the flat buffers: the one list the groups were cut from, not the groups
+            flat_named = list(layout)
+            if len(flat_named) != len(named) or {id(p) for _, p in flat_named} != {id(p) for _, p in named}:
+                raise ValueError("layout must list exactly the parameters of the param groups, each once")
         # a group the model (or an earlier optimizer) already homed exactly these parameters in is adopted, not rebuilt
         homes = {id(getattr(p, "_vbg_flat", (None,))[0]): getattr(p, "_vbg_flat", (None,))[0] for _, p in named}
         g = next(iter(homes.values())) if len(homes) == 1 else None
@@ -393,15 +498,39 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self.group = g
             g.zero_grad()
         else:
-            self.group = FlatGroup(named, device)
+            self.group = FlatGroup(flat_named, device)
         if ref is not None:                 # indices of the reference optimizer's full parameter list (unused tensors included)
             assert set(n for n, _ in named) <= set(ref)
             self.group.ref_names = list(ref)
-        super().__init__([p for _, p in named], defaults)
+        self._group_names = [[n for n, _ in d["params"]] for d in dicts]
+        self._constructed = False
+        super().__init__([dict(d, params=[p for _, p in d["params"]]) for d in dicts], defaults)
+        self._constructed = True
         self.grad_scale = 1.0
         self.steps = 0
+        # several param groups: the runs of each over the flat layout, cut into rows of bounded length, uploaded once
+        self.segmented = len(dicts) > 1
+        self.runs, self.chunk_rows, self.table = None, None, None
+        if self.segmented:
+            group_of = {id(p): k for k, d in enumerate(dicts) for _, p in d["params"]}
+            self.runs = run_table(self.group, group_of)
+            self.chunk_rows = chunk_rows(self.runs, int(seg_chunk or SEG_CHUNK))
+            self.table = ops.chunk_table(self.chunk_rows, len(dicts), self.group.total, self.group.pflat.device)
         import weakref
         self.group._vbg_optimizer = weakref.ref(self)          # (ViBERTgridNet._home: a group a live optimizer steps is never silently replaced)
+
+    @staticmethod
+    def _check_options(opts: Dict):
+        """what the kernels do not implement is refused where the param group is created, not dropped"""
+        for key, off in _UNSUPPORTED:
+            if key in opts and opts[key] != off:
+                raise ValueError(f"{key}={opts[key]!r} is not supported by the fused optimizers (only {key}={off!r})")
+
+    def add_param_group(self, param_group):
+        if getattr(self, "_constructed", True):
+            raise NotImplementedError("flat storage is fixed at construction: pass every param group to the constructor, as a list of "
+                                      "dicts {'params': [(name, parameter), ...], 'lr': ..., 'weight_decay': ...}")
+        super().add_param_group(param_group)
 
     def zero_grad(self, set_to_none: bool = False):
         self.group.zero_grad()
@@ -410,37 +539,46 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def _flat_state(self) -> Dict[str, torch.Tensor]:
         raise NotImplementedError
 
+    def _ref_lists(self):
+        """per param group, the names its checkpoint indices stand for, in index order: the reference's full list for the single
+        group (never-used tensors keep their index), the group's own parameters in the order given otherwise"""
+        return [list(self.group.ref_names)] if not self.segmented else self._group_names
+
     def state_dict(self):
         g = self.group
         pos = {n: i for i, n in enumerate(g.names)}
-        state = {}
-        if self.steps > 0:
-            for ref_i, n in enumerate(g.ref_names):
-                if n not in pos:             # a tensor that never receives a gradient: torch keeps no state for it either
-                    continue
-                i = pos[n]
-                st = {k: g.view(flat, i).clone() for k, flat in self._flat_state().items()}
-                if "exp_avg" in st:
-                    st = {"step": torch.tensor(float(self.steps)), **st}
-                state[ref_i] = st
-        groups = [dict({k: v for k, v in pg.items() if k != "params"}, params=list(range(len(g.ref_names)))) for pg in self.param_groups]
+        lists = self._ref_lists()
+        state, groups, ref_i = {}, [], 0
+        for pg, names in zip(self.param_groups, lists):
+            groups.append(dict({k: v for k, v in pg.items() if k != "params"}, params=list(range(ref_i, ref_i + len(names)))))
+            for n in names:
+                if self.steps > 0 and n in pos:          # (not in pos: a tensor that never receives a gradient -- torch keeps no state for it either)
+                    i = pos[n]
+                    st = {k: g.view(flat, i).clone() for k, flat in self._flat_state().items()}
+                    if "exp_avg" in st:
+                        st = {"step": torch.tensor(float(self.steps)), **st}
+                    state[ref_i] = st
+                ref_i += 1
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         g = self.group
         pos = {n: i for i, n in enumerate(g.names)}
+        lists = self._ref_lists()
+        got = [len(src["params"]) for src in sd.get("param_groups", [])]
+        if sd.get("param_groups") and got != [len(names) for names in lists]:
+            raise ValueError(f"optimizer checkpoint covers {got} parameters per param group, this optimizer's reference lists have "
+                             f"{[len(names) for names in lists]}: build the optimizer from split_parameters(model) (and the same param "
+                             "groups) so that the indices are the reference's")
         for pg, src in zip(self.param_groups, sd["param_groups"]):
             pg.update({k: v for k, v in src.items() if k != "params"})
         flats = self._flat_state()
         for f in flats.values():
             f.zero_()
         self.steps = 0
-        n_ref = len(sd["param_groups"][0]["params"]) if sd.get("param_groups") else len(g.ref_names)
-        if n_ref != len(g.ref_names):
-            raise ValueError(f"optimizer checkpoint covers {n_ref} parameters, this optimizer's reference list has {len(g.ref_names)}: "
-                             "build the optimizer from split_parameters(model) so that the indices are the reference's")
+        ref_names = [n for names in lists for n in names]
         for ref_i, st in sd["state"].items():
-            n = g.ref_names[int(ref_i)]
+            n = ref_names[int(ref_i)]
             if n not in pos:                 # state of a tensor kept out of the flat buffers (it never receives a gradient)
                 continue
             i = pos[n]
@@ -456,8 +594,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
 class FusedSGD(_FlatOptimizer):
     """torch.optim.SGD(momentum, weight_decay) semantics (dampening 0, no nesterov) over a flat buffer."""
 
-    def __init__(self, named, device, lr, momentum=0.0, weight_decay=0.0):
-        super().__init__(named, device, _torch_defaults(torch.optim.SGD, lr=lr, momentum=momentum, weight_decay=weight_decay))
+    def __init__(self, named, device, lr, momentum=0.0, weight_decay=0.0, seg_chunk=None, layout=None):
+        super().__init__(named, device, _torch_defaults(torch.optim.SGD, lr=lr, momentum=momentum, weight_decay=weight_decay), seg_chunk, layout)
         self.mom = torch.zeros_like(self.group.pflat)
 
     def _flat_state(self):
@@ -465,9 +603,13 @@ class FusedSGD(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        g = self.param_groups[0]
-        ops.sgd_step(self.group.pflat, self.group.gflat, self.mom, float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]),
-                     self.steps == 0, self.grad_scale)
+        if self.segmented:
+            ops.sgd_step_seg(self.group.pflat, self.group.gflat, self.mom, self.table,
+                             [(g["lr"], g["momentum"], g["weight_decay"]) for g in self.param_groups], self.steps == 0, self.grad_scale)
+        else:
+            g = self.param_groups[0]
+            ops.sgd_step(self.group.pflat, self.group.gflat, self.mom, float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]),
+                         self.steps == 0, self.grad_scale)
         self.steps += 1
         ops.bump_weight_epoch()
 
@@ -475,8 +617,9 @@ class FusedSGD(_FlatOptimizer):
 class FusedAdamW(_FlatOptimizer):
     """torch.optim.AdamW semantics (decoupled weight decay, bias correction, amsgrad off)."""
 
-    def __init__(self, named, device, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
-        super().__init__(named, device, _torch_defaults(torch.optim.AdamW, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, named, device, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, seg_chunk=None, layout=None):
+        super().__init__(named, device, _torch_defaults(torch.optim.AdamW, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), seg_chunk,
+                         layout)
         self.m = torch.zeros_like(self.group.pflat)
         self.v = torch.zeros_like(self.group.pflat)
 
@@ -485,10 +628,15 @@ class FusedAdamW(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        g = self.param_groups[0]
         self.steps += 1
-        ops.adamw_step(self.group.pflat, self.group.gflat, self.m, self.v, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                       float(g["eps"]), float(g["weight_decay"]), self.steps, self.grad_scale)
+        if self.segmented:
+            ops.adamw_step_seg(self.group.pflat, self.group.gflat, self.m, self.v, self.table,
+                               [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in self.param_groups],
+                               self.steps, self.grad_scale)
+        else:
+            g = self.param_groups[0]
+            ops.adamw_step(self.group.pflat, self.group.gflat, self.m, self.v, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
+                           float(g["eps"]), float(g["weight_decay"]), self.steps, self.grad_scale)
         ops.bump_weight_epoch()
 
 

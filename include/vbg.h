@@ -658,6 +658,24 @@ int vbg_sgd_step_seg(float* p, const float* g, float* mom, const vbg_optim_chunk
                      const vbg_sgd_group* groups, int ngroups, int first_step, float grad_scale, void* stream);
 int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, const vbg_optim_chunk* chunks, int nchunks,
                        const vbg_adamw_group* groups, int ngroups, int step, float grad_scale, void* stream);
+/* The segmented steps with the rest of torch.optim's rule per group (torch 2.10, single-tensor paths), for stock torch.optim.SGD /
+ * Adam / AdamW objects stepped through vbg.optim.fuse.  Same chunk table and buffer contract as above.
+ *   SGD:  g' = (maximize ? -g : g) * grad_scale + wd * p;  momentum != 0: buf = first ? g' : momentum * buf + (1 - dampening) * g';
+ *         d = nesterov ? g' + momentum * buf : buf (momentum 0: d = g');  p -= lr * d.  Chunks of momentum-0 groups neither read nor
+ *         write `mom`, which may be NULL when every group has momentum 0.
+ *   Adam: g' = (maximize ? -g : g) * grad_scale;  coupled: g' += wd * p, else p *= 1 - lr * wd;  moments as vbg_adamw_step;  amsgrad:
+ *         vmax = max(vmax, v) and vmax stands under the square root.  Bias corrections from the GROUP's step (>= 1), in double.  `vmax`
+ *         is read and written only in chunks of amsgrad groups; NULL is accepted when no group has the flag, an argument error otherwise.
+ * A group without flags (beyond `first`), with dampening 0 (and momentum != 0) is updated by the statements of vbg_sgd_step_seg /
+ * vbg_adamw_step_seg: same bits. */
+typedef struct { float lr, momentum, dampening, wd; int flags; } vbg_sgd_group_opt;
+    /* flags: 1 nesterov, 2 maximize, 4 first (no momentum buffer yet) */
+typedef struct { float lr, b1, b2, eps, wd; int step; int flags; } vbg_adam_group_opt;
+    /* flags: 1 amsgrad, 2 maximize, 4 coupled weight decay (torch.optim.Adam / decoupled_weight_decay=False) */
+int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
+                         const vbg_sgd_group_opt* groups, int ngroups, float grad_scale, void* stream);
+int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                          const vbg_adam_group_opt* groups, int ngroups, float grad_scale, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

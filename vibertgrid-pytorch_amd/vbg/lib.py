@@ -110,6 +110,16 @@ class AdamwGroup(C.Structure):               # include/vbg.h vbg_adamw_group
     _fields_ = [("lr", c_f), ("b1", c_f), ("b2", c_f), ("eps", c_f), ("wd", c_f)]
 
 
+class SgdGroupOpt(C.Structure):              # include/vbg.h vbg_sgd_group_opt
+    _fields_ = [("lr", c_f), ("momentum", c_f), ("dampening", c_f), ("wd", c_f), ("flags", c_int)]
+
+
+class AdamGroupOpt(C.Structure):             # include/vbg.h vbg_adam_group_opt
+    _fields_ = [("lr", c_f), ("b1", c_f), ("b2", c_f), ("eps", c_f), ("wd", c_f), ("step", c_int), ("flags", c_int)]
+
+
+SGD_NESTEROV, SGD_MAXIMIZE, SGD_FIRST = 1, 2, 4          # vbg_sgd_group_opt.flags
+ADAM_AMSGRAD, ADAM_MAXIMIZE, ADAM_COUPLED = 1, 2, 4      # vbg_adam_group_opt.flags
 OPTIM_MAX_GROUPS = 32                        # include/vbg.h VBG_OPTIM_MAX_GROUPS
 ATTN_FWD, ATTN_DQ, ATTN_DKV = 0, 1, 2
 OP_DENSE_K, OP_DENSE_R, OP_CONV_K, OP_CONV_R, OP_WT_R = 0, 1, 2, 3, 4
@@ -216,6 +226,8 @@ SIGNATURES = {
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_sgd_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroup), c_int, c_int, c_f, c_vp]),
     "vbg_adamw_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamwGroup), c_int, c_int, c_f, c_vp]),
+    "vbg_sgd_step_seg_opt": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroupOpt), c_int, c_f, c_vp]),
+    "vbg_adam_step_seg_opt": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamGroupOpt), c_int, c_f, c_vp]),
     "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
     "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_sum_det_ws_elems": (c_int, []),

@@ -7,8 +7,8 @@ import os
 
 import torch
 
-from .lib import (ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AdamwGroup, AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, VbgError, check, lib)
+from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
+                  AdamGroupOpt, AdamwGroup, AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -2361,3 +2361,26 @@ def adamw_step_seg(p, g, m, v, table, groups, step, grad_scale=1.0):
     _seg_args(table, groups, p, g, m, v)
     hp = (AdamwGroup * len(groups))(*[AdamwGroup(*map(float, h)) for h in groups])
     check(lib.vbg_adamw_step_seg(P(p), P(g), P(m), P(v), P(table.rows), table.n, hp, len(groups), int(step), grad_scale, _stream()), "vbg_adamw_step_seg")
+
+
+def sgd_step_seg_opt(p, g, mom, table, groups, grad_scale=1.0):
+    """vbg_sgd_step_seg_opt: groups = [(lr, momentum, dampening, weight_decay, flags)] per group of `table`, flags of vbg.lib SGD_*; one
+    launch.  mom: None when every group has momentum 0 (the buffer is not touched then)"""
+    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
+    if mom is None and any(float(h[1]) != 0.0 for h in groups):
+        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
+    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
+    check(lib.vbg_sgd_step_seg_opt(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), grad_scale, _stream()),
+          "vbg_sgd_step_seg_opt")
+
+
+def adam_step_seg_opt(p, g, m, v, vmax, table, groups, grad_scale=1.0):
+    """vbg_adam_step_seg_opt: groups = [(lr, beta1, beta2, eps, weight_decay, step, flags)] per group of `table`, flags of vbg.lib ADAM_*;
+    one launch.  vmax: None when no group has the amsgrad flag"""
+    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
+    if vmax is None and any(int(h[6]) & 1 for h in groups):
+        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
+    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
+                                        for h in groups])
+    check(lib.vbg_adam_step_seg_opt(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), grad_scale,
+                                    _stream()), "vbg_adam_step_seg_opt")

@@ -9,7 +9,8 @@ pipeline/train_val_utils.py:272-284, designed for MI355X instead of translated:
 * `zero_grad` is one memset, each optimizer step is ONE HIP launch over the flat range
   (libvbg `vbg_sgd_step` / `vbg_adamw_step`, 20 / 28 B per parameter); with several torch param groups (no weight decay on biases
   and LayerNorm weights, layer-wise learning rates) it is still ONE launch: `vbg_sgd_step_seg` / `vbg_adamw_step_seg` walk a chunk
-  table over the same buffers and take every group's hyper-parameters by value;
+  table over the same buffers and take every group's hyper-parameters by value; `fuse(optimizer)` gives the same single launch to an
+  unchanged torch.optim.SGD / Adam / AdamW object, with torch's semantics kept whole (`vbg_sgd_step_seg_opt` / `vbg_adam_step_seg_opt`);
 * data parallel: the flat gradient buffer is cut into large contiguous buckets; a bucket is all-reduced
   (RCCL over xGMI, async, its own stream) as soon as autograd has accumulated its last gradient, so the
   exchange overlaps the rest of backward; no bucket copies (gradients ARE the bucket); the 1/world
@@ -412,9 +413,12 @@ def decay_groups(named, no_decay=("bias", "LayerNorm.weight"), **no_decay_overri
 
 def run_table(group: FlatGroup, group_of: Dict[int, int]):
     """[(start, length, group)] over the flat layout: consecutive slots of the same param group merge into one run, a run covers its
-    slots' padding (slots are padded to 8 elements), and nothing covers [end of the last slot, total).  group_of: id(param) -> index"""
+    slots' padding (slots are padded to 8 elements), and nothing covers [end of the last slot, total).  group_of: id(param) -> index;
+    a parameter of the layout that group_of leaves out (fuse(): no gradient in this step) is covered by no run"""
     runs = []
     for p, off in zip(group.params, group.offsets):
+        if id(p) not in group_of:
+            continue
         k, end = group_of[id(p)], off + (p.numel() + 7) // 8 * 8
         if runs and runs[-1][2] == k and runs[-1][0] + runs[-1][1] == off:
             runs[-1][1] = end - runs[-1][0]
@@ -638,6 +642,254 @@ class FusedAdamW(_FlatOptimizer):
             ops.adamw_step(self.group.pflat, self.group.gflat, self.m, self.v, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
                            float(g["eps"]), float(g["weight_decay"]), self.steps, self.grad_scale)
         ops.bump_weight_epoch()
+
+
+# ---- stock torch.optim objects on the fused kernels --------------------------------------------------------------------------
+class _Fallback(Exception):
+    """this step() call goes to torch's own step (the reason is the message)"""
+
+
+class _FusedState:
+    """what fuse() keeps on the optimizer instance (`_vbg_fused`): the flat state buffers of the FlatGroup last stepped, which state
+    tensors are views of them, and the chunk tables built so far"""
+    MAX_TABLES = 8
+
+    def __init__(self, seg_chunk):
+        self.seg_chunk = int(seg_chunk or SEG_CHUNK)
+        self.group = None
+        self.flat = {}            # torch's state key -> flat buffer of the group's layout
+        self.owned = {}           # (id(param), key) -> the view of self.flat[key] that optimizer.state[param][key] must still be
+        self.tables = {}          # per-slot kernel-group assignment (tuple over the layout, -1: absent) -> ChunkTable
+        self.rows = None          # the chunk rows of the last fused step ([n, 3] int64), for inspection
+        self.launches = 0
+        self.fallbacks = 0
+        self.last_fallback = None
+
+    def adopt(self, group):
+        if self.group is not group:          # another home (the model re-homed its parameters): state held in the old buffers is
+            self.group, self.flat, self.owned, self.tables = group, {}, {}, {}          # separate tensors from here on, copied in below
+
+    def buffer(self, key):
+        if key not in self.flat:
+            self.flat[key] = torch.zeros_like(self.group.pflat)
+        return self.flat[key]
+
+    def home(self, st, p, i, key, fresh):
+        """optimizer.state[p][key] as a view of the flat buffer: a tensor torch's own step or load_state_dict put there is copied in"""
+        own = self.owned.get((id(p), key))
+        cur = None if fresh else st.get(key)
+        if own is not None and cur is own:
+            return
+        if own is None:
+            own = self.owned[(id(p), key)] = self.group.view(self.buffer(key), i)
+        if cur is not None:
+            own.copy_(cur)
+        elif key != "momentum_buffer":          # (a first momentum step overwrites its slot)
+            own.zero_()
+        st[key] = own
+
+    def table(self, assign, ngroups):
+        t = self.tables.get(assign)
+        if t is None:
+            g = self.group
+            rows = chunk_rows(run_table(g, {id(p): k for p, k in zip(g.params, assign) if k >= 0}), self.seg_chunk)
+            if len(self.tables) >= self.MAX_TABLES:
+                self.tables.pop(next(iter(self.tables)))
+            t = self.tables[assign] = ops.chunk_table(rows, ngroups, g.total, g.pflat.device)
+            t.chunk_rows = rows
+        self.rows = t.chunk_rows
+        return t
+
+
+def _parent_step(cls):
+    """torch's own step of `cls` without the hook wrapper torch.optim.Optimizer puts around every step (the subclass's step carries one
+    already: pre / post hooks run once per call)"""
+    f = cls.step
+    return getattr(f, "__wrapped__", f) if getattr(f, "hooked", False) else f
+
+
+class _FusedStock:
+    """step() of the classes fuse() switches a torch.optim instance to.  Everything else -- constructor, param_groups, state, zero_grad,
+    load_state_dict, hooks -- is the parent's."""
+    _vbg_parent = None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        fs = self._vbg_fused
+        if closure is None:
+            try:
+                plan = self._vbg_plan(fs)
+            except _Fallback as e:
+                fs.fallbacks += 1
+                fs.last_fallback = str(e)
+            else:
+                self._vbg_launch(fs, *plan)
+                fs.launches += 1
+                ops.bump_weight_epoch()
+                return None
+        else:
+            fs.fallbacks += 1
+            fs.last_fallback = "closure"
+        return _parent_step(self._vbg_parent)(self, closure)
+
+    def _vbg_present(self, fs):
+        """[(param group index, parameter, slot index)] of the parameters with a gradient, after the checks that decide whether this
+        call can be one launch over one FlatGroup"""
+        present, group = [], None
+        for k, pg in enumerate(self.param_groups):
+            if pg.get("fused") or pg.get("capturable") or pg.get("differentiable"):
+                raise _Fallback("fused / capturable / differentiable param group")
+            for p in pg["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                home = getattr(p, "_vbg_flat", None)
+                if home is None:
+                    raise _Fallback("a parameter with a gradient is not homed in flat storage")
+                if group is None:
+                    group = home[0]
+                elif home[0] is not group:
+                    raise _Fallback("the parameters with a gradient live in more than one flat group")
+                i = group._index[id(p)]
+                if g is not group.gviews[i]:
+                    raise _Fallback("a .grad is not the flat gradient view (sparse, replaced or cast)")
+                present.append((k, p, i))
+        if group is None:
+            raise _Fallback("no parameter has a gradient")
+        if not group.valid():
+            raise _Fallback("the parameters moved away from their flat buffer (Module.to / a fresh .data)")
+        fs.adopt(group)
+        return present
+
+    def state_dict(self):
+        """torch's checkpoint, with the state tensors cloned: the views would drag the whole flat buffers into the file"""
+        sd = super().state_dict()
+        sd["state"] = {i: {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()} for i, st in sd["state"].items()}
+        return sd
+
+
+def _combos(fs, keys):
+    """kernel groups: the distinct keys in order of first appearance -> (per-slot assignment over the layout, distinct keys)"""
+    index, assign = {}, [-1] * len(fs.group.params)
+    for i, key in keys:
+        j = index.get(key)
+        if j is None:
+            j = index[key] = len(index)
+        assign[i] = j
+    if len(index) > MAX_GROUPS:
+        raise _Fallback(f"{len(index)} combinations of param group and step count: one launch carries at most {MAX_GROUPS}")
+    return tuple(assign), list(index)
+
+
+class _StockSGD(_FusedStock, torch.optim.SGD):
+    _vbg_parent = torch.optim.SGD
+
+    def _vbg_plan(self, fs):
+        present = self._vbg_present(fs)
+        keys, homes = [], []
+        for k, p, i in present:
+            if self.param_groups[k]["momentum"] != 0:
+                st = self.state[p]
+                first = st.get("momentum_buffer") is None
+                homes.append((st, p, i, first))
+            else:
+                first = False
+            keys.append((i, (k, first)))
+        assign, combos = _combos(fs, keys)
+        return assign, combos, homes
+
+    def _vbg_launch(self, fs, assign, combos, homes):
+        for st, p, i, first in homes:
+            fs.home(st, p, i, "momentum_buffer", first)
+        hp = []
+        for k, first in combos:
+            pg = self.param_groups[k]
+            flags = ops.SGD_NESTEROV * bool(pg["nesterov"]) + ops.SGD_MAXIMIZE * bool(pg["maximize"]) + ops.SGD_FIRST * first
+            hp.append((float(pg["lr"]), float(pg["momentum"]), float(pg["dampening"]), float(pg["weight_decay"]), flags))
+        g = fs.group
+        ops.sgd_step_seg_opt(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, 1.0)
+
+
+class _AdamStep(_FusedStock):
+    def _vbg_plan(self, fs):
+        present = self._vbg_present(fs)
+        keys, homes = [], []
+        for k, p, i in present:
+            st = self.state[p]
+            fresh = len(st) == 0
+            ams = bool(self.param_groups[k]["amsgrad"])
+            if not fresh and ("exp_avg" not in st or "exp_avg_sq" not in st or "step" not in st or (ams and "max_exp_avg_sq" not in st)):
+                raise _Fallback("optimizer state without torch's keys")          # (torch's own step raises what it raises)
+            keys.append((i, (k, 1 if fresh else int(st["step"]) + 1)))
+            homes.append((st, p, i, fresh, ams))
+        assign, combos = _combos(fs, keys)
+        return assign, combos, homes
+
+    def _vbg_launch(self, fs, assign, combos, homes):
+        steps = []
+        for st, p, i, fresh, ams in homes:
+            if fresh:
+                st["step"] = torch.tensor(0.0, dtype=torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32)          # (on the host, as torch keeps it)
+            fs.home(st, p, i, "exp_avg", fresh)
+            fs.home(st, p, i, "exp_avg_sq", fresh)
+            if ams:
+                fs.home(st, p, i, "max_exp_avg_sq", fresh)
+            steps.append(st["step"])
+        hp, any_ams = [], False
+        for k, step in combos:
+            pg = self.param_groups[k]
+            coupled = not pg.get("decoupled_weight_decay", False)
+            flags = ops.ADAM_AMSGRAD * bool(pg["amsgrad"]) + ops.ADAM_MAXIMIZE * bool(pg["maximize"]) + ops.ADAM_COUPLED * coupled
+            any_ams = any_ams or bool(pg["amsgrad"])
+            hp.append((float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), float(pg["weight_decay"]), step, flags))
+        g = fs.group
+        ops.adam_step_seg_opt(g.pflat, g.gflat, fs.buffer("exp_avg"), fs.buffer("exp_avg_sq"), fs.buffer("max_exp_avg_sq") if any_ams else None,
+                              fs.table(assign, len(hp)), hp, 1.0)
+        torch._foreach_add_(steps, 1)
+
+
+class _StockAdam(_AdamStep, torch.optim.Adam):
+    _vbg_parent = torch.optim.Adam
+
+
+class _StockAdamW(_AdamStep, torch.optim.AdamW):
+    _vbg_parent = torch.optim.AdamW
+
+
+_STOCK = {torch.optim.SGD: _StockSGD, torch.optim.Adam: _StockAdam, torch.optim.AdamW: _StockAdamW}
+
+
+def fuse(optimizer, seg_chunk=None):
+    """Make a stock torch.optim.SGD / Adam / AdamW whose parameters are homed in flat storage (home_parameters: ViBERTgridNet does it
+    at its first training forward) step in ONE HIP launch, with torch's semantics kept exactly -- every option (nesterov, dampening,
+    maximize, amsgrad, coupled or decoupled weight decay), parameters whose `.grad` is None skipped, per-parameter step counts,
+    GradScaler, schedulers, torch's checkpoint format.  Returns the SAME object, its class switched to a subclass that overrides
+    `step`; call it between building the optimizer and building its lr schedulers:
+
+        optimizer_cnn = vbg.optim.fuse(torch.optim.SGD(cnn_params, lr=..., momentum=...))
+        optimizer_bert = vbg.optim.fuse(torch.optim.AdamW(bert_params, lr=...))
+
+    A step() call that cannot be one launch runs torch's own step for that call: a closure; a parameter with a gradient that is not
+    homed (yet), lives in another flat group or has moved away from it (Module.to); a `.grad` that is not the flat gradient view (a
+    sparse or replaced gradient); a param group with fused / capturable / differentiable set; optimizer state without torch's keys;
+    more than 32 combinations of (param group, step count).  Both paths read and write the same `optimizer.state`: the moments are
+    views of flat buffers under torch's own keys, and tensors that torch's step or load_state_dict put there are copied in at the next
+    fused step.  `optimizer._vbg_fused` counts `launches` and `fallbacks` and keeps the reason of the last one.  seg_chunk: elements per
+    row of the chunk tables (default SEG_CHUNK)."""
+    cls = type(optimizer)
+    if cls not in _STOCK:
+        raise ValueError(f"fuse() takes instances of exactly torch.optim.SGD, Adam or AdamW, not {cls.__module__}.{cls.__qualname__}")
+    for k, pg in enumerate(optimizer.param_groups):
+        for key in ("capturable", "differentiable"):
+            if pg.get(key):
+                raise ValueError(f"param group {k} has {key}=True: not supported by the fused step")
+    if "step" in vars(optimizer) or hasattr(optimizer.step, "_wrapped_by_lr_sched"):
+        raise ValueError("optimizer.step is already wrapped (an lr scheduler was built on this optimizer): call fuse() before building "
+                         "schedulers, so that they wrap the fused step")
+    optimizer.__class__ = _STOCK[cls]
+    optimizer._vbg_fused = _FusedState(seg_chunk)
+    optimizer._patch_step_function()          # the step pre / post hooks of torch.optim.Optimizer, around the new step
+    return optimizer
 
 
 def clip_grad_norm_(optimizers, max_norm: float, norm_scale: float = 1.0) -> float:

@@ -666,8 +666,8 @@ int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, const vbg_o
  *   Adam: g' = (maximize ? -g : g) * grad_scale;  coupled: g' += wd * p, else p *= 1 - lr * wd;  moments as vbg_adamw_step;  amsgrad:
  *         vmax = max(vmax, v) and vmax stands under the square root.  Bias corrections from the GROUP's step (>= 1), in double.  `vmax`
  *         is read and written only in chunks of amsgrad groups; NULL is accepted when no group has the flag, an argument error otherwise.
- * A group without flags (beyond `first`), with dampening 0 (and momentum != 0) is updated by the statements of vbg_sgd_step_seg /
- * vbg_adamw_step_seg: same bits. */
+ * A group without flags (beyond `first`), with dampening 0 (and momentum != 0) is updated by the statements of the whole-range steps:
+ * same bits as vbg_sgd_step / vbg_adamw_step, and as vbg_sgd_step_seg / vbg_adamw_step_seg, which are this case of the same launch. */
 typedef struct { float lr, momentum, dampening, wd; int flags; } vbg_sgd_group_opt;
     /* flags: 1 nesterov, 2 maximize, 4 first (no momentum buffer yet) */
 typedef struct { float lr, b1, b2, eps, wd; int step; int flags; } vbg_adam_group_opt;

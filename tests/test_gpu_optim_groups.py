@@ -126,28 +126,31 @@ def test_more_chunk_rows_than_blocks(ops, which):
         assert close(m, mr, 1e-6, 1e-7) and close(v, vr, 1e-6, 1e-7)
 
 
-@pytest.mark.parametrize("which", ["sgd", "adamw"])
+@pytest.mark.parametrize("which", ["sgd", "adamw", "sgd_momentum0"])
 def test_same_bits_as_the_whole_range_launch(ops, which):
     """three groups with identical hyper-parameters over contiguous runs tiling 4096 elements == ops.sgd_step / ops.adamw_step, bit for
-    bit: both kernels inline one statement of the update"""
+    bit: both kernels inline one statement of the update.  sgd_momentum0: a momentum-0 group of ops.sgd_step_seg still goes through
+    that statement, in p AND in the momentum buffer it writes"""
     n = 4096
     runs = [(0, 1000, 0), (1000, 72, 1), (1072, n - 1072, 2)]
     table = ops.chunk_table(cut(runs, CHUNK), 3, n, dev())
     p0, grads = _opt_inputs(n)
-    a = [p0.to(dev())] + [torch.zeros(n, device=dev()) for _ in range(1 if which == "sgd" else 2)]
+    sgd_hp = SGD_HP[2] if which == "sgd_momentum0" else SGD_HP[0]
+    assert (sgd_hp[1] == 0) == (which == "sgd_momentum0")
+    a = [p0.to(dev())] + [torch.zeros(n, device=dev()) for _ in range(2 if which == "adamw" else 1)]
     b = [t.clone() for t in a]
     for gs in (1.0, 0.125):
         for i, g in enumerate(grads):
             gd = g.to(dev())
-            if which == "sgd":
-                ops.sgd_step_seg(a[0], gd, a[1], table, [SGD_HP[0]] * 3, i == 0, gs)
-                ops.sgd_step(b[0], gd, b[1], *SGD_HP[0], i == 0, gs)
-            else:
+            if which == "adamw":
                 ops.adamw_step_seg(a[0], gd, a[1], a[2], table, [ADAMW_HP[0]] * 3, i + 1, gs)
                 ops.adamw_step(b[0], gd, b[1], b[2], *ADAMW_HP[0], i + 1, gs)
+            else:
+                ops.sgd_step_seg(a[0], gd, a[1], table, [sgd_hp] * 3, i == 0, gs)
+                ops.sgd_step(b[0], gd, b[1], *sgd_hp, i == 0, gs)
             for x, y in zip(a, b):
                 assert torch.equal(x, y), (which, gs, i)
-    assert not torch.equal(a[0].cpu(), p0)
+    assert not torch.equal(a[0].cpu(), p0) and bool(a[1].any())
 
 
 # ------------------------------------------------------------------------------------------

@@ -2,7 +2,9 @@
 floor, at the sizes the product steps: the bert-base AdamW buffer and a 41.8 M-element SGD buffer (the two layouts of
 tools/optim_groups_bench.py, here with real parameters homed in a vbg.optim.FlatGroup).  Then the kernels alone: the segmented entries
 with torch's options (vbg_adam_step_seg_opt / vbg_sgd_step_seg_opt) against vbg_adamw_step_seg / vbg_sgd_step_seg over the same
-table -- bound set beforehand, as in profiles/optim_groups.txt: at most 1.05x.
+table -- bound set beforehand, as in profiles/optim_groups.txt: at most 1.05x.  Both pairs of entries launch ONE kernel per rule
+(sgd_seg_kernel / adam_seg_kernel), so the `_seg` row and the `_opt`, flags 0 row time the same code through two entries; both rows
+stay, as the measurement that the one kernel serves both (profiles/optim_seg_merge.txt).
 
 Same protocol as that tool: one process, every variant warmed up, ROUNDS rounds that visit the variants in turn; per variant the
 median, min and max over the rounds.  Reported per step() call: device time between two events around REPS back-to-back calls, and

@@ -5,7 +5,9 @@
 // Two forms of each step share ONE statement of the per-element arithmetic (sgd_update / adamw_update): the whole-range kernels
 // (one set of hyper-parameters), and the segmented kernels, which walk a chunk table (start, length, group) and take up to
 // VBG_OPTIM_MAX_GROUPS sets of hyper-parameters by value in their arguments (torch param groups over a layout that cannot be
-// reordered by group: a group is a set of scattered runs of slots).
+// reordered by group: a group is a set of scattered runs of slots).  There is one segmented kernel per rule, on one chunk walk
+// (walk_chunks) and one stream loop (stream_chunk); vbg_sgd_step_seg / vbg_adamw_step_seg translate their groups into the default
+// case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.
 #include "vbg_common.h"
 #include "../../include/vbg.h"
 
@@ -104,218 +106,101 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // lengths are multiples of 4 elements and every chunk lies inside the buffers (checked where the table is built, vbg/ops.py);
 // what no chunk covers is neither read nor written.
 constexpr int SEG_THREADS = 256;
-struct AdamwHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; };
-struct SgdGroups { vbg_sgd_group g[VBG_OPTIM_MAX_GROUPS]; };
-struct AdamwGroups { AdamwHp g[VBG_OPTIM_MAX_GROUPS]; };
+
+template <class Body>
+__device__ __forceinline__ void walk_chunks(const vbg_optim_chunk* __restrict__ tbl, int nchunks, Body body) {
+    int c = blockIdx.x;
+    if (c >= nchunks) return;
+    vbg_optim_chunk ch = tbl[c];
+    for (;;) {
+        const int nxt = c + (int)gridDim.x;
+        vbg_optim_chunk chn = ch;
+        if (nxt < nchunks) chn = tbl[nxt];
+        body(ch);
+        if (nxt >= nchunks) break;
+        c = nxt;
+        ch = chn;
+    }
+}
+
+// One chunk: p, g and the first NS of the state arrays s0, s1, s2 as float4s, upd(p, g, s0, s1, s2) on each of the four elements,
+// p and those NS arrays stored.  An array past NS is neither read nor written (its pointer may be NULL): upd gets a zero it must
+// not use.
+template <int NS, class Upd>
+__device__ __forceinline__ void stream_chunk(const vbg_optim_chunk& ch, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s0,
+                                             float* __restrict__ s1, float* __restrict__ s2, Upd upd) {
+    float4* p4 = reinterpret_cast<float4*>(p + ch.start);
+    const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
+    float4* a4 = NS > 0 ? reinterpret_cast<float4*>(s0 + ch.start) : nullptr;
+    float4* b4 = NS > 1 ? reinterpret_cast<float4*>(s1 + ch.start) : nullptr;
+    float4* c4 = NS > 2 ? reinterpret_cast<float4*>(s2 + ch.start) : nullptr;
+    const int n4 = ch.length >> 2;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+        float4 pv = p4[i];
+        const float4 gv = g4[i];
+        float4 av = {}, bv = {}, cv = {};
+        if constexpr (NS > 0) av = a4[i];
+        if constexpr (NS > 1) bv = b4[i];
+        if constexpr (NS > 2) cv = c4[i];
+        upd(pv.x, gv.x, av.x, bv.x, cv.x);
+        upd(pv.y, gv.y, av.y, bv.y, cv.y);
+        upd(pv.z, gv.z, av.z, bv.z, cv.z);
+        upd(pv.w, gv.w, av.w, bv.w, cv.w);
+        p4[i] = pv;
+        if constexpr (NS > 0) a4[i] = av;
+        if constexpr (NS > 1) b4[i] = bv;
+        if constexpr (NS > 2) c4[i] = cv;
+    }
+}
+
+// A chunk's group decides, uniformly for the block, which statement streams it: the default case runs sgd_update / adamw_update,
+// a momentum-0 group never touches the momentum buffer unless keep_mom is set (vbg_sgd_step_seg, which always has a buffer and
+// writes it; never reachable through vbg_sgd_group_opt.flags), and max_exp_avg_sq is only touched in chunks of amsgrad groups.
+struct SgdHp { float lr, momentum, dampening, wd; int flags, keep_mom; };
+struct AdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int flags; };
+struct SgdGroups { SgdHp g[VBG_OPTIM_MAX_GROUPS]; };
+struct AdamGroups { AdamHp g[VBG_OPTIM_MAX_GROUPS]; };
 
 __global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom,
-                               const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdGroups hp, int first, float gs) {
-    int c = blockIdx.x;
-    if (c >= nchunks) return;
-    vbg_optim_chunk ch = tbl[c];
-    for (;;) {
-        const int nxt = c + (int)gridDim.x;
-        vbg_optim_chunk chn = ch;
-        if (nxt < nchunks) chn = tbl[nxt];
-        const vbg_sgd_group h = hp.g[ch.group];
-        float4* p4 = reinterpret_cast<float4*>(p + ch.start);
-        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
-        float4* m4 = reinterpret_cast<float4*>(mom + ch.start);
-        const int n4 = ch.length >> 2;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-            float4 pv = p4[i];
-            const float4 gv = g4[i];
-            float4 mv = m4[i];
-            sgd_update(pv.x, gv.x, mv.x, h.lr, h.momentum, h.wd, first, gs);
-            sgd_update(pv.y, gv.y, mv.y, h.lr, h.momentum, h.wd, first, gs);
-            sgd_update(pv.z, gv.z, mv.z, h.lr, h.momentum, h.wd, first, gs);
-            sgd_update(pv.w, gv.w, mv.w, h.lr, h.momentum, h.wd, first, gs);
-            p4[i] = pv;
-            m4[i] = mv;
-        }
-        if (nxt >= nchunks) break;
-        c = nxt;
-        ch = chn;
-    }
-}
-
-__global__ void __launch_bounds__(SEG_THREADS) adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                 const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamwGroups hp, float gs) {
-    int c = blockIdx.x;
-    if (c >= nchunks) return;
-    vbg_optim_chunk ch = tbl[c];
-    for (;;) {
-        const int nxt = c + (int)gridDim.x;
-        vbg_optim_chunk chn = ch;
-        if (nxt < nchunks) chn = tbl[nxt];
-        const AdamwHp h = hp.g[ch.group];
-        const float step_size = h.lr / h.bc1;
-        float4* p4 = reinterpret_cast<float4*>(p + ch.start);
-        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
-        float4* m4 = reinterpret_cast<float4*>(m + ch.start);
-        float4* v4 = reinterpret_cast<float4*>(v + ch.start);
-        const int n4 = ch.length >> 2;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-            float4 pv = p4[i];
-            const float4 gv = g4[i];
-            float4 mv = m4[i];
-            float4 vv = v4[i];
-            adamw_update(pv.x, gv.x, mv.x, vv.x, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-            adamw_update(pv.y, gv.y, mv.y, vv.y, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-            adamw_update(pv.z, gv.z, mv.z, vv.z, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-            adamw_update(pv.w, gv.w, mv.w, vv.w, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-            p4[i] = pv;
-            m4[i] = mv;
-            v4[i] = vv;
-        }
-        if (nxt >= nchunks) break;
-        c = nxt;
-        ch = chn;
-    }
-}
-
-// ---- segmented forms with every torch.optim option per group ------------------------------------------------------------
-// The same walk over the chunk table.  A chunk's group decides, uniformly for the block, which loop streams it: the default case
-// runs the loop of sgd_seg_kernel / adamw_seg_kernel, momentum 0 never touches the momentum buffer, and max_exp_avg_sq is only
-// touched in chunks of amsgrad groups.
-struct AdamOptHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int flags; };
-struct SgdOptGroups { vbg_sgd_group_opt g[VBG_OPTIM_MAX_GROUPS]; };
-struct AdamOptGroups { AdamOptHp g[VBG_OPTIM_MAX_GROUPS]; };
-
-__global__ void __launch_bounds__(SEG_THREADS) sgd_seg_opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom,
-                                   const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdOptGroups hp, float gs) {
-    int c = blockIdx.x;
-    if (c >= nchunks) return;
-    vbg_optim_chunk ch = tbl[c];
-    for (;;) {
-        const int nxt = c + (int)gridDim.x;
-        vbg_optim_chunk chn = ch;
-        if (nxt < nchunks) chn = tbl[nxt];
-        const vbg_sgd_group_opt h = hp.g[ch.group];
+                               const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdGroups hp, float gs) {
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        const SgdHp h = hp.g[ch.group];
         const int first = (h.flags & SGD_FIRST) != 0, nesterov = (h.flags & SGD_NESTEROV) != 0, maximize = (h.flags & SGD_MAXIMIZE) != 0;
-        float4* p4 = reinterpret_cast<float4*>(p + ch.start);
-        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
-        const int n4 = ch.length >> 2;
-        if (h.momentum == 0.f) {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float none = 0.f;
-                sgd_update_opt(pv.x, gv.x, none, h.lr, 0.f, h.dampening, h.wd, 0, 0, maximize, 0, gs);
-                sgd_update_opt(pv.y, gv.y, none, h.lr, 0.f, h.dampening, h.wd, 0, 0, maximize, 0, gs);
-                sgd_update_opt(pv.z, gv.z, none, h.lr, 0.f, h.dampening, h.wd, 0, 0, maximize, 0, gs);
-                sgd_update_opt(pv.w, gv.w, none, h.lr, 0.f, h.dampening, h.wd, 0, 0, maximize, 0, gs);
-                p4[i] = pv;
-            }
-        } else if ((h.flags & ~SGD_FIRST) == 0 && h.dampening == 0.f) {
-            float4* m4 = reinterpret_cast<float4*>(mom + ch.start);
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float4 mv = m4[i];
-                sgd_update(pv.x, gv.x, mv.x, h.lr, h.momentum, h.wd, first, gs);
-                sgd_update(pv.y, gv.y, mv.y, h.lr, h.momentum, h.wd, first, gs);
-                sgd_update(pv.z, gv.z, mv.z, h.lr, h.momentum, h.wd, first, gs);
-                sgd_update(pv.w, gv.w, mv.w, h.lr, h.momentum, h.wd, first, gs);
-                p4[i] = pv;
-                m4[i] = mv;
-            }
-        } else {
-            float4* m4 = reinterpret_cast<float4*>(mom + ch.start);
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float4 mv = m4[i];
-                sgd_update_opt(pv.x, gv.x, mv.x, h.lr, h.momentum, h.dampening, h.wd, 1, nesterov, maximize, first, gs);
-                sgd_update_opt(pv.y, gv.y, mv.y, h.lr, h.momentum, h.dampening, h.wd, 1, nesterov, maximize, first, gs);
-                sgd_update_opt(pv.z, gv.z, mv.z, h.lr, h.momentum, h.dampening, h.wd, 1, nesterov, maximize, first, gs);
-                sgd_update_opt(pv.w, gv.w, mv.w, h.lr, h.momentum, h.dampening, h.wd, 1, nesterov, maximize, first, gs);
-                p4[i] = pv;
-                m4[i] = mv;
-            }
-        }
-        if (nxt >= nchunks) break;
-        c = nxt;
-        ch = chn;
-    }
+        if (h.momentum == 0.f && !h.keep_mom)
+            stream_chunk<0>(ch, p, g, nullptr, nullptr, nullptr, [&](float& pv, float gv, float& none, float&, float&) {
+                sgd_update_opt(pv, gv, none, h.lr, 0.f, h.dampening, h.wd, 0, 0, maximize, 0, gs);
+            });
+        else if ((h.flags & ~SGD_FIRST) == 0 && h.dampening == 0.f)
+            stream_chunk<1>(ch, p, g, mom, nullptr, nullptr, [&](float& pv, float gv, float& mv, float&, float&) {
+                sgd_update(pv, gv, mv, h.lr, h.momentum, h.wd, first, gs);
+            });
+        else
+            stream_chunk<1>(ch, p, g, mom, nullptr, nullptr, [&](float& pv, float gv, float& mv, float&, float&) {
+                sgd_update_opt(pv, gv, mv, h.lr, h.momentum, h.dampening, h.wd, 1, nesterov, maximize, first, gs);
+            });
+    });
 }
 
-__global__ void __launch_bounds__(SEG_THREADS) adam_seg_opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                    float* __restrict__ vmax, const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamOptGroups hp, float gs) {
-    int c = blockIdx.x;
-    if (c >= nchunks) return;
-    vbg_optim_chunk ch = tbl[c];
-    for (;;) {
-        const int nxt = c + (int)gridDim.x;
-        vbg_optim_chunk chn = ch;
-        if (nxt < nchunks) chn = tbl[nxt];
-        const AdamOptHp h = hp.g[ch.group];
+__global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ vmax, const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamGroups hp, float gs) {
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        const AdamHp h = hp.g[ch.group];
         const float step_size = h.lr / h.bc1;
         const int maximize = (h.flags & ADAM_MAXIMIZE) != 0, coupled = (h.flags & ADAM_COUPLED) != 0;
-        float4* p4 = reinterpret_cast<float4*>(p + ch.start);
-        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
-        float4* m4 = reinterpret_cast<float4*>(m + ch.start);
-        float4* v4 = reinterpret_cast<float4*>(v + ch.start);
-        const int n4 = ch.length >> 2;
-        if (h.flags == 0) {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float4 mv = m4[i];
-                float4 vv = v4[i];
-                adamw_update(pv.x, gv.x, mv.x, vv.x, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-                adamw_update(pv.y, gv.y, mv.y, vv.y, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-                adamw_update(pv.z, gv.z, mv.z, vv.z, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-                adamw_update(pv.w, gv.w, mv.w, vv.w, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
-                p4[i] = pv;
-                m4[i] = mv;
-                v4[i] = vv;
-            }
-        } else if (h.flags & ADAM_AMSGRAD) {
-            float4* x4 = reinterpret_cast<float4*>(vmax + ch.start);
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float4 mv = m4[i];
-                float4 vv = v4[i];
-                float4 xv = x4[i];
-                adam_update_opt(pv.x, gv.x, mv.x, vv.x, xv.x, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 1, maximize, coupled, gs);
-                adam_update_opt(pv.y, gv.y, mv.y, vv.y, xv.y, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 1, maximize, coupled, gs);
-                adam_update_opt(pv.z, gv.z, mv.z, vv.z, xv.z, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 1, maximize, coupled, gs);
-                adam_update_opt(pv.w, gv.w, mv.w, vv.w, xv.w, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 1, maximize, coupled, gs);
-                p4[i] = pv;
-                m4[i] = mv;
-                v4[i] = vv;
-                x4[i] = xv;
-            }
-        } else {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 pv = p4[i];
-                const float4 gv = g4[i];
-                float4 mv = m4[i];
-                float4 vv = v4[i];
-                float none = 0.f;
-                adam_update_opt(pv.x, gv.x, mv.x, vv.x, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
-                adam_update_opt(pv.y, gv.y, mv.y, vv.y, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
-                adam_update_opt(pv.z, gv.z, mv.z, vv.z, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
-                adam_update_opt(pv.w, gv.w, mv.w, vv.w, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
-                p4[i] = pv;
-                m4[i] = mv;
-                v4[i] = vv;
-            }
-        }
-        if (nxt >= nchunks) break;
-        c = nxt;
-        ch = chn;
-    }
+        if (h.flags == 0)
+            stream_chunk<2>(ch, p, g, m, v, nullptr, [&](float& pv, float gv, float& mv, float& vv, float&) {
+                adamw_update(pv, gv, mv, vv, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, gs);
+            });
+        else if (h.flags & ADAM_AMSGRAD)
+            stream_chunk<3>(ch, p, g, m, v, vmax, [&](float& pv, float gv, float& mv, float& vv, float& xv) {
+                adam_update_opt(pv, gv, mv, vv, xv, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 1, maximize, coupled, gs);
+            });
+        else
+            stream_chunk<2>(ch, p, g, m, v, nullptr, [&](float& pv, float gv, float& mv, float& vv, float& none) {
+                adam_update_opt(pv, gv, mv, vv, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
+            });
+    });
 }
 
 static inline int ew_grid(long long n, int block) {
@@ -323,6 +208,13 @@ static inline int ew_grid(long long n, int block) {
     if (g > 256 * 8) g = 256 * 8;
     if (g < 1) g = 1;
     return (int)g;
+}
+
+// Adam's bias corrections 1 - b1^step and sqrt(1 - b2^step), formed in double
+struct BiasCorr { float bc1, bc2_sqrt; };
+static inline BiasCorr bias_corr(float b1, float b2, int step) {
+    const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+    return BiasCorr{(float)bc1, (float)sqrt(bc2)};
 }
 
 }  // namespace vbg
@@ -347,42 +239,55 @@ extern "C" int vbg_adamw_step(float* p, const float* g, float* m, float* v, long
     if (n == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && m && v);
     const long long n4 = (ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(m) && ALIGNED16(v)) ? n / 4 : 0;
-    const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);
+    const BiasCorr bc = bias_corr(b1, b2, step);
     VBG_LAUNCH(adamw_kernel, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, lr, b1, b2,
-                       eps, wd, (float)bc1, (float)sqrt(bc2), grad_scale);
+                       eps, wd, bc.bc1, bc.bc2_sqrt, grad_scale);
     VBG_LAUNCH_RET();
 }
 
-// the segmented forms: buffers 16-byte aligned (float4 access at start, a multiple of 4 elements); the table is device memory,
-// the hyper-parameters are copied from host memory into the kernel arguments (no copy to the device, no sync)
+// the segmented forms: buffers 16-byte aligned (float4 access at start, a multiple of 4 elements; NULL where an entry accepts it);
+// the table is device memory, the hyper-parameters are copied from host memory into the kernel arguments (no copy to the device,
+// no sync)
+static int launch_sgd_seg(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const SgdGroups& hp,
+                          float grad_scale, void* stream) {
+    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(mom) && ALIGNED16(chunks));
+    VBG_LAUNCH(sgd_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, mom, chunks, nchunks, hp,
+               grad_scale);
+    VBG_LAUNCH_RET();
+}
+
+static int launch_adam_seg(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                           const AdamGroups& hp, float grad_scale, void* stream) {
+    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(m) && ALIGNED16(v) && ALIGNED16(vmax) && ALIGNED16(chunks));
+    VBG_LAUNCH(adam_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, m, v, vmax, chunks, nchunks, hp,
+               grad_scale);
+    VBG_LAUNCH_RET();
+}
+
+// lr / momentum / wd per group, first_step shared: the default case of the kernel, and a momentum-0 group keeps writing its buffer
 extern "C" int vbg_sgd_step_seg(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
                                 const vbg_sgd_group* groups, int ngroups, int first_step, float grad_scale, void* stream) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && mom && chunks && groups);
-    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(mom) && ALIGNED16(chunks));
     SgdGroups hp = {};
-    for (int i = 0; i < ngroups; ++i) hp.g[i] = groups[i];
-    VBG_LAUNCH(sgd_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, mom, chunks, nchunks, hp, first_step,
-               grad_scale);
-    VBG_LAUNCH_RET();
+    for (int i = 0; i < ngroups; ++i) hp.g[i] = SgdHp{groups[i].lr, groups[i].momentum, 0.f, groups[i].wd, first_step ? SGD_FIRST : 0, 1};
+    return launch_sgd_seg(p, g, mom, chunks, nchunks, hp, grad_scale, stream);
 }
 
+// lr / betas / eps / wd per group, step shared: flags 0
 extern "C" int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, const vbg_optim_chunk* chunks, int nchunks,
                                   const vbg_adamw_group* groups, int ngroups, int step, float grad_scale, void* stream) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0 && step >= 1);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && m && v && chunks && groups);
-    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(m) && ALIGNED16(v) && ALIGNED16(chunks));
-    AdamwGroups hp = {};
+    AdamGroups hp = {};
     for (int i = 0; i < ngroups; ++i) {
         const vbg_adamw_group& s = groups[i];
-        const double bc1 = 1.0 - pow((double)s.b1, (double)step), bc2 = 1.0 - pow((double)s.b2, (double)step);
-        hp.g[i] = AdamwHp{s.lr, s.b1, s.b2, s.eps, s.wd, (float)bc1, (float)sqrt(bc2)};
+        const BiasCorr bc = bias_corr(s.b1, s.b2, step);
+        hp.g[i] = AdamHp{s.lr, s.b1, s.b2, s.eps, s.wd, bc.bc1, bc.bc2_sqrt, 0};
     }
-    VBG_LAUNCH(adamw_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, m, v, chunks, nchunks, hp,
-               grad_scale);
-    VBG_LAUNCH_RET();
+    return launch_adam_seg(p, g, m, v, nullptr, chunks, nchunks, hp, grad_scale, stream);
 }
 
 // every torch.optim option per group (flags of include/vbg.h): same table, same checks.  mom may be NULL when every group has momentum
@@ -392,17 +297,15 @@ extern "C" int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const 
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && chunks && groups);
-    SgdOptGroups hp = {};
+    SgdGroups hp = {};
     bool any_mom = false;
     for (int i = 0; i < ngroups; ++i) {
-        hp.g[i] = groups[i];
-        any_mom = any_mom || groups[i].momentum != 0.f;
+        const vbg_sgd_group_opt& s = groups[i];
+        hp.g[i] = SgdHp{s.lr, s.momentum, s.dampening, s.wd, s.flags, 0};
+        any_mom = any_mom || s.momentum != 0.f;
     }
     VBG_CHECK_ARG(mom || !any_mom);
-    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(mom) && ALIGNED16(chunks));
-    VBG_LAUNCH(sgd_seg_opt_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, mom, chunks, nchunks, hp,
-               grad_scale);
-    VBG_LAUNCH_RET();
+    return launch_sgd_seg(p, g, mom, chunks, nchunks, hp, grad_scale, stream);
 }
 
 extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
@@ -410,16 +313,13 @@ extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* 
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && m && v && chunks && groups);
-    AdamOptGroups hp = {};
+    AdamGroups hp = {};
     for (int i = 0; i < ngroups; ++i) {
         const vbg_adam_group_opt& s = groups[i];
         VBG_CHECK_ARG(s.step >= 1);
         VBG_CHECK_ARG(vmax || !(s.flags & ADAM_AMSGRAD));
-        const double bc1 = 1.0 - pow((double)s.b1, (double)s.step), bc2 = 1.0 - pow((double)s.b2, (double)s.step);
-        hp.g[i] = AdamOptHp{s.lr, s.b1, s.b2, s.eps, s.wd, (float)bc1, (float)sqrt(bc2), s.flags};
+        const BiasCorr bc = bias_corr(s.b1, s.b2, s.step);
+        hp.g[i] = AdamHp{s.lr, s.b1, s.b2, s.eps, s.wd, bc.bc1, bc.bc2_sqrt, s.flags};
     }
-    VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(m) && ALIGNED16(v) && ALIGNED16(vmax) && ALIGNED16(chunks));
-    VBG_LAUNCH(adam_seg_opt_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, m, v, vmax, chunks, nchunks,
-               hp, grad_scale);
-    VBG_LAUNCH_RET();
+    return launch_adam_seg(p, g, m, v, vmax, chunks, nchunks, hp, grad_scale, stream);
 }

@@ -676,6 +676,17 @@ int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const vbg_optim_c
                          const vbg_sgd_group_opt* groups, int ngroups, float grad_scale, void* stream);
 int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
                           const vbg_adam_group_opt* groups, int ngroups, float grad_scale, void* stream);
+/* The same two steps under torch.amp.GradScaler's protocol for optimizers that declare _step_supports_amp_scaling: the scale and the
+ * inf flag are fp32 scalars in DEVICE memory, read by the kernel -- no host sync, no separate unscale pass.  found_inf (required):
+ * non-zero makes the whole launch a no-op, p / g / every state array left as they were.  grad_scale (NULL: the caller unscaled the
+ * gradients already): g' = g * inv with inv = (float)(1.0 / (double)*grad_scale), a product rounded on its own and stored back to g;
+ * the rule then runs on g' with grad_scale 1, in the statements of the *_seg_opt entries (same bits as those on the same g').  With
+ * NULL g is not written.  Everything else -- table, groups, optional buffers, argument errors -- as vbg_sgd_step_seg_opt /
+ * vbg_adam_step_seg_opt. */
+int vbg_sgd_step_seg_amp(float* p, float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
+                         const vbg_sgd_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
+int vbg_adam_step_seg_amp(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                          const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

@@ -12,7 +12,15 @@ host time of the call itself (perf_counter around it, device idle at the start).
 tests/test_gpu_train_loop.py (torch.optim.SGD + AdamW around the model on the e2e fixture) with and without fuse(), N alternating
 processes each, milliseconds per step.
 
-    python tools/stock_optim_bench.py [--out FILE] [--rounds 9] [--reps 10] [--e2e 3]"""
+`--gradscaler N` measures GradScaler's two routes instead (nothing else runs then): cfg2's two optimizers -- AdamW over the bert-base
+layout, SGD with momentum over the CNN-shaped one --, homed, gradients present, one shared torch.amp.GradScaler, and per iteration
+`scaler.scale(x); scaler.step(sgd); scaler.step(adamw); scaler.update()`, with `fuse(opt)` and with `fuse(opt, amp_scaling=True)`, N
+alternating processes per setting.  Per iteration (device idle at its start, the scaled gradients put back before it, outside the
+timed window): host time of the four calls, device time between two events around them; then the step kernels alone, with their bytes
+per second.
+
+    python tools/stock_optim_bench.py [--out FILE] [--rounds 9] [--reps 10] [--e2e 3]
+    python tools/stock_optim_bench.py --gradscaler 3 [--out FILE] [--steps 20] [--warmup 5]"""
 import argparse
 import os
 import statistics
@@ -189,6 +197,97 @@ def e2e(n, steps, warmup, emit):
     emit("  plain         : " + "   ".join(f"{v:7.2f}" for v in res["plain"]))
 
 
+def gradscaler_child(amp, steps, warmup, reps):
+    """one process of the GradScaler mode; prints `GS <amp> host_us device_us launches fallbacks skipped` and the kernels' rates"""
+    from vbg import ops
+    from vbg import optim as vo
+    dev = torch.device("cuda")
+    sides = []
+    for kind, meta in (("sgd", cnn_named()), ("adamw", bert_named())):
+        nm = real(meta, dev, 1)
+        group = vo.FlatGroup(nm, dev)
+        cls, kw = (torch.optim.AdamW, ADAMW_KW) if kind == "adamw" else (torch.optim.SGD, SGD_KW)
+        opt = vo.fuse(cls([p for _, p in nm], **kw), amp_scaling=amp)
+        scaled = torch.randn(group.total, device=dev, generator=torch.Generator(device=dev).manual_seed(2)) * (0.02 * 65536.0)
+        sides.append((kind, group, opt, scaled))
+    scaler = torch.amp.GradScaler("cuda", growth_interval=10 ** 9)          # (the scale stays at 65536: every iteration does the same work)
+    x = torch.zeros((), device=dev)
+    host, devt = [], []
+    for it in range(warmup + steps):
+        for _, group, _, scaled in sides:
+            group.gflat.copy_(scaled)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        t0 = time.perf_counter()
+        scaler.scale(x)
+        for _, _, opt, _ in sides:
+            scaler.step(opt)
+        scaler.update()
+        t1 = time.perf_counter()
+        e1.record()
+        e1.synchronize()
+        if it >= warmup:
+            host.append((t1 - t0) * 1e6)
+            devt.append(e0.elapsed_time(e1) * 1e3)
+    fs = [opt._vbg_fused for _, _, opt, _ in sides]
+    for f_ in fs:
+        f_.reconcile()
+        assert f_.fallbacks == 0 and f_.launches == warmup + steps and f_.skipped == 0, f_.last_fallback
+    print(f"GS {int(amp)} {statistics.median(host):.1f} {statistics.median(devt):.1f} {sum(f_.launches for f_ in fs) // (warmup + steps)} "
+          f"{sum(f_.fallbacks for f_ in fs)} {sum(f_.skipped for f_ in fs)}", flush=True)
+    # the step kernels alone, one group over the whole layout: REPS back-to-back calls between two events
+    one, zero = torch.ones((), device=dev), torch.zeros((), device=dev)
+    for kind, group, opt, scaled in sides:
+        table = opt._vbg_fused.table(tuple([0] * len(group.params)), 1)
+        st = [opt._vbg_fused.flat[k] for k in (("momentum_buffer",) if kind == "sgd" else ("exp_avg", "exp_avg_sq"))]
+        if kind == "sgd":
+            hp = [(0.005, 0.9, 0.0, 0.005, 0)]
+            calls = (("vbg_sgd_step_seg_opt", 20, lambda: ops.sgd_step_seg_opt(group.pflat, group.gflat, st[0], table, hp, 1.0)),
+                     ("vbg_sgd_step_seg_amp", 24, lambda: ops.sgd_step_seg_amp(group.pflat, group.gflat, st[0], table, hp, one, zero)),
+                     ("vbg_sgd_step_seg_amp, found_inf set", 0, lambda: ops.sgd_step_seg_amp(group.pflat, group.gflat, st[0], table, hp, one, one)))
+        else:
+            hp = [(5e-5, 0.9, 0.999, 1e-8, 0.01, 3, 0)]
+            calls = (("vbg_adam_step_seg_opt", 28, lambda: ops.adam_step_seg_opt(group.pflat, group.gflat, st[0], st[1], None, table, hp, 1.0)),
+                     ("vbg_adam_step_seg_amp", 32, lambda: ops.adam_step_seg_amp(group.pflat, group.gflat, st[0], st[1], None, table, hp, one, zero)),
+                     ("vbg_adam_step_seg_amp, found_inf set", 0, lambda: ops.adam_step_seg_amp(group.pflat, group.gflat, st[0], st[1], None, table, hp, one, one)))
+        group.gflat.normal_(0.0, 0.02, generator=torch.Generator(device=dev).manual_seed(4))
+        for label, nbytes, fn in calls:
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            us = e0.elapsed_time(e1) / reps * 1e3
+            print(f"KERNEL {int(amp)} {label}|{us:.1f}|{nbytes * group.total / us * 1e-3:.0f}", flush=True)
+
+
+def gradscaler(n, steps, warmup, reps, emit):
+    res, kern = {0: [], 1: []}, {}
+    for _ in range(n):
+        for amp in (0, 1):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gradscaler-child", str(amp), "--steps", str(steps), "--warmup", str(warmup),
+                                  "--reps", str(reps)], check=True, capture_output=True, text=True, timeout=300).stdout
+            for ln in out.splitlines():
+                if ln.startswith("GS "):
+                    res[amp].append(ln.split()[2:])
+                elif ln.startswith("KERNEL "):
+                    label, us, gbs = ln[9:].split("|")
+                    kern.setdefault(label, []).append((float(us), float(gbs)))
+    emit(f"GradScaler loop, cfg2's two optimizers (SGD over the CNN-shaped layout, AdamW over bert-base), homed, gradients present, one shared scaler;")
+    emit(f"per iteration scale -> step(sgd) -> step(adamw) -> update; median of {steps} iterations after {warmup}; {n} alternating processes per setting:")
+    for amp, label in ((0, "fuse(opt)"), (1, "fuse(opt, amp_scaling=True)")):
+        emit(f"  {label:<30} host us / iteration: " + "  ".join(f"{float(r[0]):8.1f}" for r in res[amp]) + "    device us / iteration: "
+             + "  ".join(f"{float(r[1]):8.1f}" for r in res[amp]) + f"    fused launches / iteration {res[amp][0][2]}, fallbacks {res[amp][0][3]}, skipped {res[amp][0][4]}")
+    emit(f"the step kernels alone (one group, {reps} back-to-back calls between two events; every process of both settings), us per call (GB/s):")
+    for label, v in kern.items():
+        emit(f"  {label:<40} " + "  ".join(f"{us:7.1f} ({gbs:5.0f})" if gbs else f"{us:7.1f}" for us, gbs in v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -196,6 +295,8 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--e2e", type=int, default=0, help="alternating processes per mode of the end-to-end stock loop (0: skip)")
     ap.add_argument("--e2e-child", default=None, choices=["fuse", "plain"])
+    ap.add_argument("--gradscaler", type=int, default=0, help="alternating processes per setting of the GradScaler loop (runs only that)")
+    ap.add_argument("--gradscaler-child", default=None, choices=["0", "1"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
@@ -203,12 +304,22 @@ def main():
         raise SystemExit("stock_optim_bench: needs the GPU (no timing is taken without one)")
     if a.e2e_child:
         return e2e_child(a.e2e_child, a.steps, a.warmup)
+    if a.gradscaler_child:
+        return gradscaler_child(a.gradscaler_child == "1", a.steps, a.warmup, a.reps)
     lines = []
 
     def emit(s):
         print(s, flush=True)
         lines.append(s)
 
+    if a.gradscaler:
+        emit(f"{torch.cuda.get_device_name(0)}")
+        gradscaler(a.gradscaler, a.steps, a.warmup, a.reps, emit)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     emit(f"{torch.cuda.get_device_name(0)}; {a.rounds} rounds x {a.reps} calls per variant, variants visited in turn; median (min, max) per call")
     emit("AdamW over the bert-base layout (pooler left out):")
     ok = measure("adamw", bert_named(), a.rounds, a.reps, emit)

@@ -7,7 +7,9 @@
 // VBG_OPTIM_MAX_GROUPS sets of hyper-parameters by value in their arguments (torch param groups over a layout that cannot be
 // reordered by group: a group is a set of scattered runs of slots).  There is one segmented kernel per rule, on one chunk walk
 // (walk_chunks) and one stream loop (stream_chunk); vbg_sgd_step_seg / vbg_adamw_step_seg translate their groups into the default
-// case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.
+// case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.  vbg_sgd_step_seg_amp / vbg_adam_step_seg_amp
+// are the AMP instantiation of the same two kernels (SegScale below).
+#include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
 
@@ -107,6 +109,30 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // what no chunk covers is neither read nor written.
 constexpr int SEG_THREADS = 256;
 
+// How a segmented launch learns the gradient scale.  The host form carries it by value (gs multiplies the gradient inside the rule).
+// The AMP form (torch.amp.GradScaler's protocol for optimizers with _step_supports_amp_scaling) reads two fp32 scalars from device
+// memory: found_inf != 0 makes every block return before it touches a buffer; with a scale, every chunk's gradients are first
+// multiplied by inv = float(1 / double(*scale)) (torch's own inverse) in place (unscale_chunk); with scale NULL (the caller unscaled
+// already) g is only read.  The rule then runs on what g holds with gs (1 from the entries), in the statements of the host form.
+template <bool AMP> struct SegScale { float gs; };
+template <> struct SegScale<true> { float gs; const float* scale; const float* found_inf; };
+template <bool AMP> using GradPtr = std::conditional_t<AMP, float*, const float*>;
+
+// -> false: the launch is a skipped step.  Uniform over the launch.
+template <bool AMP>
+__device__ __forceinline__ bool seg_scale(const SegScale<AMP>& sc, float& inv, bool& store_g) {
+    inv = 1.f;
+    store_g = false;
+    if constexpr (AMP) {
+        if (*sc.found_inf != 0.f) return false;
+        if (sc.scale) {
+            inv = (float)(1.0 / (double)*sc.scale);
+            store_g = true;
+        }
+    }
+    return true;
+}
+
 template <class Body>
 __device__ __forceinline__ void walk_chunks(const vbg_optim_chunk* __restrict__ tbl, int nchunks, Body body) {
     int c = blockIdx.x;
@@ -154,6 +180,20 @@ __device__ __forceinline__ void stream_chunk(const vbg_optim_chunk& ch, float* _
     }
 }
 
+// The AMP form's own pass over a chunk, ahead of stream_chunk: g *= inv, each product rounded on its own and stored.  A thread
+// writes exactly the float4s it reads back in stream_chunk (same index walk), where they come from the cache: the chunk's traffic
+// to memory is one read and one write of g more, and the rule runs on loaded values in the very statements of the host-scale form.
+__device__ __forceinline__ void unscale_chunk(const vbg_optim_chunk& ch, float* __restrict__ g, float inv) {
+    float4* g4 = reinterpret_cast<float4*>(g + ch.start);
+    const int n4 = ch.length >> 2;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+        float4 gv = g4[i];
+        gv.x = __fmul_rn(gv.x, inv); gv.y = __fmul_rn(gv.y, inv); gv.z = __fmul_rn(gv.z, inv); gv.w = __fmul_rn(gv.w, inv);
+        g4[i] = gv;
+    }
+}
+
 // A chunk's group decides, uniformly for the block, which statement streams it: the default case runs sgd_update / adamw_update,
 // a momentum-0 group never touches the momentum buffer unless keep_mom is set (vbg_sgd_step_seg, which always has a buffer and
 // writes it; never reachable through vbg_sgd_group_opt.flags), and max_exp_avg_sq is only touched in chunks of amsgrad groups.
@@ -162,9 +202,15 @@ struct AdamHp { float lr, b1, b2, eps, wd, bc1, bc2_sqrt; int flags; };
 struct SgdGroups { SgdHp g[VBG_OPTIM_MAX_GROUPS]; };
 struct AdamGroups { AdamHp g[VBG_OPTIM_MAX_GROUPS]; };
 
-__global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ mom,
-                               const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdGroups hp, float gs) {
+template <bool AMP>
+__global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict__ p, GradPtr<AMP> __restrict__ g, float* __restrict__ mom,
+                               const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdGroups hp, SegScale<AMP> sc) {
+    float inv;
+    bool store_g;
+    if (!seg_scale(sc, inv, store_g)) return;
+    const float gs = sc.gs;
     walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv);
         const SgdHp h = hp.g[ch.group];
         const int first = (h.flags & SGD_FIRST) != 0, nesterov = (h.flags & SGD_NESTEROV) != 0, maximize = (h.flags & SGD_MAXIMIZE) != 0;
         if (h.momentum == 0.f && !h.keep_mom)
@@ -182,9 +228,15 @@ __global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict_
     });
 }
 
-__global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                float* __restrict__ vmax, const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamGroups hp, float gs) {
+template <bool AMP>
+__global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict__ p, GradPtr<AMP> __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ vmax, const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamGroups hp, SegScale<AMP> sc) {
+    float inv;
+    bool store_g;
+    if (!seg_scale(sc, inv, store_g)) return;
+    const float gs = sc.gs;
     walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv);
         const AdamHp h = hp.g[ch.group];
         const float step_size = h.lr / h.bc1;
         const int maximize = (h.flags & ADAM_MAXIMIZE) != 0, coupled = (h.flags & ADAM_COUPLED) != 0;
@@ -248,19 +300,20 @@ extern "C" int vbg_adamw_step(float* p, const float* g, float* m, float* v, long
 // the segmented forms: buffers 16-byte aligned (float4 access at start, a multiple of 4 elements; NULL where an entry accepts it);
 // the table is device memory, the hyper-parameters are copied from host memory into the kernel arguments (no copy to the device,
 // no sync)
-static int launch_sgd_seg(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const SgdGroups& hp,
-                          float grad_scale, void* stream) {
+template <bool AMP>
+static int launch_sgd_seg(float* p, GradPtr<AMP> g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const SgdGroups& hp,
+                          const SegScale<AMP>& sc, void* stream) {
     VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(mom) && ALIGNED16(chunks));
-    VBG_LAUNCH(sgd_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, mom, chunks, nchunks, hp,
-               grad_scale);
+    VBG_LAUNCH(sgd_seg_kernel<AMP>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, mom, chunks, nchunks, hp, sc);
     VBG_LAUNCH_RET();
 }
 
-static int launch_adam_seg(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
-                           const AdamGroups& hp, float grad_scale, void* stream) {
+template <bool AMP>
+static int launch_adam_seg(float* p, GradPtr<AMP> g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                           const AdamGroups& hp, const SegScale<AMP>& sc, void* stream) {
     VBG_CHECK_ARG(ALIGNED16(p) && ALIGNED16(g) && ALIGNED16(m) && ALIGNED16(v) && ALIGNED16(vmax) && ALIGNED16(chunks));
-    VBG_LAUNCH(adam_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, m, v, vmax, chunks, nchunks, hp,
-               grad_scale);
+    VBG_LAUNCH(adam_seg_kernel<AMP>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, p, g, m, v, vmax, chunks, nchunks, hp,
+               sc);
     VBG_LAUNCH_RET();
 }
 
@@ -272,7 +325,7 @@ extern "C" int vbg_sgd_step_seg(float* p, const float* g, float* mom, const vbg_
     VBG_CHECK_ARG(p && g && mom && chunks && groups);
     SgdGroups hp = {};
     for (int i = 0; i < ngroups; ++i) hp.g[i] = SgdHp{groups[i].lr, groups[i].momentum, 0.f, groups[i].wd, first_step ? SGD_FIRST : 0, 1};
-    return launch_sgd_seg(p, g, mom, chunks, nchunks, hp, grad_scale, stream);
+    return launch_sgd_seg<false>(p, g, mom, chunks, nchunks, hp, SegScale<false>{grad_scale}, stream);
 }
 
 // lr / betas / eps / wd per group, step shared: flags 0
@@ -287,14 +340,17 @@ extern "C" int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, 
         const BiasCorr bc = bias_corr(s.b1, s.b2, step);
         hp.g[i] = AdamHp{s.lr, s.b1, s.b2, s.eps, s.wd, bc.bc1, bc.bc2_sqrt, 0};
     }
-    return launch_adam_seg(p, g, m, v, nullptr, chunks, nchunks, hp, grad_scale, stream);
+    return launch_adam_seg<false>(p, g, m, v, nullptr, chunks, nchunks, hp, SegScale<false>{grad_scale}, stream);
 }
 
 // every torch.optim option per group (flags of include/vbg.h): same table, same checks.  mom may be NULL when every group has momentum
-// 0, vmax when no group has the amsgrad flag; a group's bias corrections come from ITS step
-extern "C" int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
-                                    const vbg_sgd_group_opt* groups, int ngroups, float grad_scale, void* stream) {
+// 0, vmax when no group has the amsgrad flag; a group's bias corrections come from ITS step.  The *_amp entries are the same calls
+// with the scale and the inf flag in device memory (SegScale<true>; found_inf is required, grad_scale may be NULL) and g writable.
+template <bool AMP>
+static int sgd_step_seg_opt(float* p, GradPtr<AMP> g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const vbg_sgd_group_opt* groups,
+                            int ngroups, const SegScale<AMP>& sc, void* stream) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
+    if constexpr (AMP) VBG_CHECK_ARG(sc.found_inf && (uintptr_t)sc.found_inf % 4 == 0 && (uintptr_t)sc.scale % 4 == 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && chunks && groups);
     SgdGroups hp = {};
@@ -305,12 +361,14 @@ extern "C" int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const 
         any_mom = any_mom || s.momentum != 0.f;
     }
     VBG_CHECK_ARG(mom || !any_mom);
-    return launch_sgd_seg(p, g, mom, chunks, nchunks, hp, grad_scale, stream);
+    return launch_sgd_seg<AMP>(p, g, mom, chunks, nchunks, hp, sc, stream);
 }
 
-extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
-                                     const vbg_adam_group_opt* groups, int ngroups, float grad_scale, void* stream) {
+template <bool AMP>
+static int adam_step_seg_opt(float* p, GradPtr<AMP> g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                             const vbg_adam_group_opt* groups, int ngroups, const SegScale<AMP>& sc, void* stream) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
+    if constexpr (AMP) VBG_CHECK_ARG(sc.found_inf && (uintptr_t)sc.found_inf % 4 == 0 && (uintptr_t)sc.scale % 4 == 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && m && v && chunks && groups);
     AdamGroups hp = {};
@@ -321,5 +379,25 @@ extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* 
         const BiasCorr bc = bias_corr(s.b1, s.b2, s.step);
         hp.g[i] = AdamHp{s.lr, s.b1, s.b2, s.eps, s.wd, bc.bc1, bc.bc2_sqrt, s.flags};
     }
-    return launch_adam_seg(p, g, m, v, vmax, chunks, nchunks, hp, grad_scale, stream);
+    return launch_adam_seg<AMP>(p, g, m, v, vmax, chunks, nchunks, hp, sc, stream);
+}
+
+extern "C" int vbg_sgd_step_seg_opt(float* p, const float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
+                                    const vbg_sgd_group_opt* groups, int ngroups, float grad_scale, void* stream) {
+    return sgd_step_seg_opt<false>(p, g, mom, chunks, nchunks, groups, ngroups, SegScale<false>{grad_scale}, stream);
+}
+
+extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                                     const vbg_adam_group_opt* groups, int ngroups, float grad_scale, void* stream) {
+    return adam_step_seg_opt<false>(p, g, m, v, vmax, chunks, nchunks, groups, ngroups, SegScale<false>{grad_scale}, stream);
+}
+
+extern "C" int vbg_sgd_step_seg_amp(float* p, float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const vbg_sgd_group_opt* groups,
+                                    int ngroups, const float* grad_scale, const float* found_inf, void* stream) {
+    return sgd_step_seg_opt<true>(p, g, mom, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf}, stream);
+}
+
+extern "C" int vbg_adam_step_seg_amp(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                                     const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream) {
+    return adam_step_seg_opt<true>(p, g, m, v, vmax, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf}, stream);
 }

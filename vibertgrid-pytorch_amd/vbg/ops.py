@@ -2384,3 +2384,37 @@ def adam_step_seg_opt(p, g, m, v, vmax, table, groups, grad_scale=1.0):
                                         for h in groups])
     check(lib.vbg_adam_step_seg_opt(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), grad_scale,
                                     _stream()), "vbg_adam_step_seg_opt")
+
+
+def _amp_scalars(table, grad_scale, found_inf):
+    """the two scalars of GradScaler's protocol: fp32, one element each, on the table's device; grad_scale may be None"""
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is None and name == "grad_scale":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
+            raise ValueError(f"segmented AMP optimizer step: {name} must be one fp32 element on the table's device")
+    return (None if grad_scale is None else P(grad_scale)), P(found_inf)
+
+
+def sgd_step_seg_amp(p, g, mom, table, groups, grad_scale, found_inf):
+    """vbg_sgd_step_seg_amp: sgd_step_seg_opt with the scale (a device scalar, or None: g is unscaled already) and GradScaler's inf flag
+    (a device scalar; non-zero: the launch does nothing) read by the kernel; g is overwritten with the unscaled gradient"""
+    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
+    if mom is None and any(float(h[1]) != 0.0 for h in groups):
+        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
+    sc, fi = _amp_scalars(table, grad_scale, found_inf)
+    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
+    check(lib.vbg_sgd_step_seg_amp(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), sc, fi, _stream()),
+          "vbg_sgd_step_seg_amp")
+
+
+def adam_step_seg_amp(p, g, m, v, vmax, table, groups, grad_scale, found_inf):
+    """vbg_adam_step_seg_amp: adam_step_seg_opt under the same protocol (see sgd_step_seg_amp)"""
+    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
+    if vmax is None and any(int(h[6]) & 1 for h in groups):
+        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
+    sc, fi = _amp_scalars(table, grad_scale, found_inf)
+    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
+                                        for h in groups])
+    check(lib.vbg_adam_step_seg_amp(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), sc, fi,
+                                    _stream()), "vbg_adam_step_seg_amp")

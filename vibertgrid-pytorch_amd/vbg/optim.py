@@ -596,7 +596,11 @@ class _FlatOptimizer(torch.optim.Optimizer):
 
 
 class FusedSGD(_FlatOptimizer):
-    """torch.optim.SGD(momentum, weight_decay) semantics (dampening 0, no nesterov) over a flat buffer."""
+    """torch.optim.SGD(momentum, weight_decay) semantics (dampening 0, no nesterov) over a flat buffer.
+    `grad_scale` is a HOST float here (1 / world size, set by FlatReducer).  torch.amp.GradScaler's protocol for optimizers that
+    consume the scale themselves assigns a device tensor to an attribute of that name and deletes it after the step, so this class
+    does not declare `_step_supports_amp_scaling`: under a GradScaler it takes the scaler's generic route (unscale_, inf check on
+    the host).  The in-launch unscale and inf skip exist for stock torch.optim objects: `fuse(optimizer, amp_scaling=True)`."""
 
     def __init__(self, named, device, lr, momentum=0.0, weight_decay=0.0, seg_chunk=None, layout=None):
         super().__init__(named, device, _torch_defaults(torch.optim.SGD, lr=lr, momentum=momentum, weight_decay=weight_decay), seg_chunk, layout)
@@ -619,7 +623,8 @@ class FusedSGD(_FlatOptimizer):
 
 
 class FusedAdamW(_FlatOptimizer):
-    """torch.optim.AdamW semantics (decoupled weight decay, bias correction, amsgrad off)."""
+    """torch.optim.AdamW semantics (decoupled weight decay, bias correction, amsgrad off).  Like FusedSGD it keeps a host float
+    `grad_scale` and therefore does not declare `_step_supports_amp_scaling` (see there)."""
 
     def __init__(self, named, device, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, seg_chunk=None, layout=None):
         super().__init__(named, device, _torch_defaults(torch.optim.AdamW, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), seg_chunk,
@@ -651,11 +656,16 @@ class _Fallback(Exception):
 
 class _FusedState:
     """what fuse() keeps on the optimizer instance (`_vbg_fused`): the flat state buffers of the FlatGroup last stepped, which state
-    tensors are views of them, and the chunk tables built so far"""
+    tensors are views of them, and the chunk tables built so far.  With amp_scaling: what the last launch under GradScaler's protocol
+    did to `optimizer.state` on the host, until reconcile() has learnt whether the device skipped that step"""
     MAX_TABLES = 8
 
-    def __init__(self, seg_chunk):
+    def __init__(self, seg_chunk, amp=False):
         self.seg_chunk = int(seg_chunk or SEG_CHUNK)
+        self.amp = bool(amp)
+        self.skipped = 0          # steps that found_inf turned into no-ops (counted at reconcile; a skipped fallback at once)
+        self._pending = None      # (host copy of found_inf, event behind the copy or None, undo) of the last AMP launch
+        self._flag = None         # the pinned host scalar the copies go to
         self.group = None
         self.flat = {}            # torch's state key -> flat buffer of the group's layout
         self.owned = {}           # (id(param), key) -> the view of self.flat[key] that optimizer.state[param][key] must still be
@@ -688,6 +698,35 @@ class _FusedState:
             own.zero_()
         st[key] = own
 
+    def defer(self, found_inf, undo):
+        """after an AMP launch: the host does not know whether the kernel took its early exit and does not wait to find out.  The flag
+        travels to a pinned host scalar behind the launch; `undo` takes the step's host bookkeeping back if it turns out set"""
+        if found_inf.is_cuda:
+            if self._flag is None:
+                self._flag = torch.zeros(1, dtype=torch.float32).pin_memory()
+            self._flag.copy_(found_inf.detach().reshape(1), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._pending = (self._flag, ev, undo)
+        else:
+            self._pending = (found_inf.detach().reshape(1).clone(), None, undo)
+
+    def reconcile(self):
+        """make `optimizer.state` what torch's own loop leaves behind if the last step under GradScaler's protocol was skipped on the
+        device: step counts back by one, state entries and first momentum buffers that step created removed.  Runs at the start of
+        every step(), in state_dict() and load_state_dict(); call it before reading `optimizer.state` directly right after a
+        `scaler.step(optimizer)`.  Waits for ONE event, the copy of found_inf behind that launch -- long complete by the next step of a
+        training loop"""
+        if self._pending is None:
+            return
+        flag, ev, undo = self._pending
+        self._pending = None
+        if ev is not None and not ev.query():
+            ev.synchronize()
+        if float(flag) != 0.0:
+            undo()
+            self.skipped += 1
+
     def table(self, assign, ngroups):
         t = self.tables.get(assign)
         if t is None:
@@ -716,21 +755,80 @@ class _FusedStock:
     @torch.no_grad()
     def step(self, closure=None):
         fs = self._vbg_fused
+        fs.reconcile()
+        # GradScaler's protocol (fuse(amp_scaling=True)): for the length of this call the scaler has put two device scalars on the
+        # object, `found_inf` and `grad_scale` (None: the caller has run scaler.unscale_ already)
+        found_inf = getattr(self, "found_inf", None) if fs.amp else None
+        amp = None if found_inf is None else (getattr(self, "grad_scale", None), found_inf)
+        known = None if amp is None else set(self.state)
         if closure is None:
             try:
                 plan = self._vbg_plan(fs)
+                if amp is not None:
+                    self._vbg_amp_check(fs, *amp)
             except _Fallback as e:
                 fs.fallbacks += 1
                 fs.last_fallback = str(e)
             else:
-                self._vbg_launch(fs, *plan)
+                if amp is None:
+                    self._vbg_launch(fs, *plan)
+                else:
+                    undo = self._vbg_launch(fs, *plan, amp=amp)
+                    created = [p for p in self.state if p not in known]
+                    fs.defer(found_inf, lambda: self._vbg_undo(undo, created))
                 fs.launches += 1
-                ops.bump_weight_epoch()
+                ops.bump_weight_epoch()          # (after a launch that turns out skipped: one redundant re-split of the plane images)
                 return None
         else:
             fs.fallbacks += 1
             fs.last_fallback = "closure"
+        if amp is not None:
+            # torch's own step knows nothing of the two attributes: do here what GradScaler would have done before calling it
+            self._vbg_undo([], [p for p in self.state if p not in known and not self.state[p]])          # (entries the plan touched)
+            if float(found_inf) != 0.0:          # (a sync, on this rare path only)
+                fs.skipped += 1
+                return None
+            self._vbg_unscale(amp[0])
+            # (torch's single-tensor and foreach steps read the two attributes themselves and refuse them: out of sight for the call,
+            # back for GradScaler to delete)
+            hidden = {k: self.__dict__.pop(k) for k in ("grad_scale", "found_inf") if k in self.__dict__}
+            try:
+                return _parent_step(self._vbg_parent)(self, closure)
+            finally:
+                self.__dict__.update(hidden)
         return _parent_step(self._vbg_parent)(self, closure)
+
+    @staticmethod
+    def _vbg_amp_check(fs, grad_scale, found_inf):
+        dev = fs.group.pflat.device
+        for t in (found_inf,) if grad_scale is None else (grad_scale, found_inf):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != dev:
+                raise _Fallback("grad_scale / found_inf is not one fp32 element on the flat buffers' device")
+
+    def _vbg_undo(self, undo, created):
+        """the host bookkeeping of a step the device skipped, taken back (`undo`: callables of _vbg_launch; `created`: parameters whose
+        state entry did not exist before that step)"""
+        for f in undo:
+            f()
+        for p in created:
+            self.state.pop(p, None)
+
+    def _vbg_unscale(self, grad_scale):
+        """GradScaler.unscale_ for a step that falls back to torch's own: the present gradients times the inverse scale, in place"""
+        if grad_scale is None:
+            return
+        inv = grad_scale.double().reciprocal().float()
+        by = {}
+        for pg in self.param_groups:
+            for p in pg["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.is_sparse:
+                    g = g._values()
+                by.setdefault((g.device, g.dtype), []).append(g)
+        for (dev, _), grads in by.items():
+            torch._amp_foreach_non_finite_check_and_unscale_(grads, torch.zeros(1, device=dev), inv.to(dev))
 
     def _vbg_present(self, fs):
         """[(param group index, parameter, slot index)] of the parameters with a gradient, after the checks that decide whether this
@@ -763,9 +861,14 @@ class _FusedStock:
 
     def state_dict(self):
         """torch's checkpoint, with the state tensors cloned: the views would drag the whole flat buffers into the file"""
+        self._vbg_fused.reconcile()
         sd = super().state_dict()
         sd["state"] = {i: {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()} for i, st in sd["state"].items()}
         return sd
+
+    def load_state_dict(self, state_dict):
+        self._vbg_fused.reconcile()
+        return super().load_state_dict(state_dict)
 
 
 def _combos(fs, keys):
@@ -798,8 +901,12 @@ class _StockSGD(_FusedStock, torch.optim.SGD):
         assign, combos = _combos(fs, keys)
         return assign, combos, homes
 
-    def _vbg_launch(self, fs, assign, combos, homes):
+    def _vbg_launch(self, fs, assign, combos, homes, amp=None):
+        undo = []
         for st, p, i, first in homes:
+            if amp is not None and first:          # skipped: the slot was never written (and home() does not zero it), the key goes again
+                undo.append((lambda st=st: st.__setitem__("momentum_buffer", None)) if "momentum_buffer" in st else
+                            (lambda st=st: st.pop("momentum_buffer", None)))
             fs.home(st, p, i, "momentum_buffer", first)
         hp = []
         for k, first in combos:
@@ -807,7 +914,11 @@ class _StockSGD(_FusedStock, torch.optim.SGD):
             flags = ops.SGD_NESTEROV * bool(pg["nesterov"]) + ops.SGD_MAXIMIZE * bool(pg["maximize"]) + ops.SGD_FIRST * first
             hp.append((float(pg["lr"]), float(pg["momentum"]), float(pg["dampening"]), float(pg["weight_decay"]), flags))
         g = fs.group
-        ops.sgd_step_seg_opt(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, 1.0)
+        if amp is None:
+            ops.sgd_step_seg_opt(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, 1.0)
+        else:
+            ops.sgd_step_seg_amp(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, *amp)
+        return undo
 
 
 class _AdamStep(_FusedStock):
@@ -825,9 +936,11 @@ class _AdamStep(_FusedStock):
         assign, combos = _combos(fs, keys)
         return assign, combos, homes
 
-    def _vbg_launch(self, fs, assign, combos, homes):
-        steps = []
+    def _vbg_launch(self, fs, assign, combos, homes, amp=None):
+        steps, undo = [], []
         for st, p, i, fresh, ams in homes:
+            if fresh and amp is not None:          # skipped: an entry that was empty is empty again
+                undo.append(st.clear)
             if fresh:
                 st["step"] = torch.tensor(0.0, dtype=torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32)          # (on the host, as torch keeps it)
             fs.home(st, p, i, "exp_avg", fresh)
@@ -843,9 +956,14 @@ class _AdamStep(_FusedStock):
             any_ams = any_ams or bool(pg["amsgrad"])
             hp.append((float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), float(pg["weight_decay"]), step, flags))
         g = fs.group
-        ops.adam_step_seg_opt(g.pflat, g.gflat, fs.buffer("exp_avg"), fs.buffer("exp_avg_sq"), fs.buffer("max_exp_avg_sq") if any_ams else None,
-                              fs.table(assign, len(hp)), hp, 1.0)
+        bufs = (g.pflat, g.gflat, fs.buffer("exp_avg"), fs.buffer("exp_avg_sq"), fs.buffer("max_exp_avg_sq") if any_ams else None, fs.table(assign, len(hp)), hp)
+        if amp is None:
+            ops.adam_step_seg_opt(*bufs, 1.0)
+        else:
+            ops.adam_step_seg_amp(*bufs, *amp)
+            undo.insert(0, lambda: torch._foreach_sub_(steps, 1))          # (bias corrections always come from the true step count)
         torch._foreach_add_(steps, 1)
+        return undo
 
 
 class _StockAdam(_AdamStep, torch.optim.Adam):
@@ -859,7 +977,7 @@ class _StockAdamW(_AdamStep, torch.optim.AdamW):
 _STOCK = {torch.optim.SGD: _StockSGD, torch.optim.Adam: _StockAdam, torch.optim.AdamW: _StockAdamW}
 
 
-def fuse(optimizer, seg_chunk=None):
+def fuse(optimizer, seg_chunk=None, amp_scaling=False):
     """Make a stock torch.optim.SGD / Adam / AdamW whose parameters are homed in flat storage (home_parameters: ViBERTgridNet does it
     at its first training forward) step in ONE HIP launch, with torch's semantics kept exactly -- every option (nesterov, dampening,
     maximize, amsgrad, coupled or decoupled weight decay), parameters whose `.grad` is None skipped, per-parameter step counts,
@@ -875,7 +993,17 @@ def fuse(optimizer, seg_chunk=None):
     more than 32 combinations of (param group, step count).  Both paths read and write the same `optimizer.state`: the moments are
     views of flat buffers under torch's own keys, and tensors that torch's step or load_state_dict put there are copied in at the next
     fused step.  `optimizer._vbg_fused` counts `launches` and `fallbacks` and keeps the reason of the last one.  seg_chunk: elements per
-    row of the chunk tables (default SEG_CHUNK)."""
+    row of the chunk tables (default SEG_CHUNK).
+
+    amp_scaling=True declares `_step_supports_amp_scaling` on this instance, torch's protocol for optimizers that consume GradScaler's
+    scale themselves: `scaler.step(optimizer)` then runs only its read-only inf check, puts the device scalars `grad_scale` and
+    `found_inf` on the object for the length of the call, and the launch (`vbg_sgd_step_seg_amp` / `vbg_adam_step_seg_amp`) unscales
+    the gradients and skips the step on an inf by itself -- no `unscale_` pass, no `found_inf.item()` drain.  A skipped step is then a
+    launch that does nothing, and the host learns of it later: `optimizer._vbg_fused.reconcile()` (run by the next step(), by
+    state_dict() and load_state_dict(); call it yourself before reading `optimizer.state` right after `scaler.step`) takes the step
+    counts and the state entries of a skipped step back and counts it in `skipped`.  A call that falls back to torch's own step under
+    the protocol does GradScaler's part first: it reads found_inf (a sync), returns on an inf, unscales the gradients otherwise.
+    Without the two attributes (a plain `optimizer.step()`, a disabled scaler) the step is the one without the option."""
     cls = type(optimizer)
     if cls not in _STOCK:
         raise ValueError(f"fuse() takes instances of exactly torch.optim.SGD, Adam or AdamW, not {cls.__module__}.{cls.__qualname__}")
@@ -887,7 +1015,9 @@ def fuse(optimizer, seg_chunk=None):
         raise ValueError("optimizer.step is already wrapped (an lr scheduler was built on this optimizer): call fuse() before building "
                          "schedulers, so that they wrap the fused step")
     optimizer.__class__ = _STOCK[cls]
-    optimizer._vbg_fused = _FusedState(seg_chunk)
+    optimizer._vbg_fused = _FusedState(seg_chunk, amp_scaling)
+    if amp_scaling:
+        optimizer._step_supports_amp_scaling = True
     optimizer._patch_step_function()          # the step pre / post hooks of torch.optim.Optimizer, around the new step
     return optimizer
 

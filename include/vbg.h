@@ -687,6 +687,32 @@ int vbg_sgd_step_seg_amp(float* p, float* g, float* mom, const vbg_optim_chunk* 
                          const vbg_sgd_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
 int vbg_adam_step_seg_amp(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
                           const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm type 2) without a host sync and without a pass of its own over the
+ * gradients: a norm pass over the chunk table the step will walk, a one-block finish that leaves the norm and torch's coefficient in
+ * device memory, and the step entries below, which read the coefficient as the *_amp entries read the scale.
+ * vbg_grad_sumsq_seg: partials[c] = sum of g[start .. start + length)^2 of row c, c in [0, nchunks) -- a plain store per row (no
+ *   atomics, nothing to zero, the same bits on every call), summed per thread over its float4s and then over the block, in fp32.
+ *   Same table and alignment contract as the segmented steps; the group field is ignored, what no row covers is not read, nchunks == 0
+ *   is a no-op.  partials is device memory of >= nchunks floats.
+ * vbg_clip_coef: one block sums partials[0 .. n) in double in a fixed order (partials of several tables side by side: one norm over
+ *   several optimizers) and writes out[0] = total = (float)sqrt(sum) * norm_scale [* (float)(1.0 / (double)*grad_scale) when grad_scale,
+ *   a device scalar, is given: the gradients still hold scaled values] and out[1] = the coefficient in fp32 as torch forms it:
+ *   c = (1 / (total + 1e-6f)) * max_norm (torch evaluates `max_norm / tensor` as reciprocal times scalar), out[1] = c > 1 ? 1 : c --
+ *   a NaN norm gives NaN, an inf norm 0, n == 0 gives (0, 1).  out: 2 floats of device memory.
+ * vbg_sgd_step_seg_clip / vbg_adam_step_seg_clip: the *_amp entries with clip_coef (device scalar, required; out + 1 above), found_inf
+ *   optional (NULL: no scaler) and the host float of the *_seg_opt entries (host_scale, applied inside the rule).  Per chunk, before the
+ *   rule: g' = (g * inv) * coef, inv as in the *_amp entries (1 without grad_scale), each product rounded on its own, stored back to g
+ *   -- what torch's unscale_ and clip leave in .grad.  With coef == 1.0f and grad_scale NULL g is not written (the products would be g).
+ *   found_inf non-zero: the launch does nothing.  keep_mom != 0 (SGD): momentum-0 groups write `mom` as in vbg_sgd_step_seg, which is
+ *   then required; with it, groups without flags reproduce vbg_sgd_step_seg on the clipped gradient bit for bit. */
+int vbg_grad_sumsq_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, void* stream);
+int vbg_clip_coef(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, float* out, void* stream);
+int vbg_sgd_step_seg_clip(float* p, float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks,
+                          const vbg_sgd_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf,
+                          const float* clip_coef, float host_scale, int keep_mom, void* stream);
+int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                           const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf,
+                           const float* clip_coef, float host_scale, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

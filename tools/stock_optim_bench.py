@@ -19,8 +19,17 @@ alternating processes per setting.  Per iteration (device idle at its start, the
 timed window): host time of the four calls, device time between two events around them; then the step kernels alone, with their bytes
 per second.
 
+`--clip N` measures gradient-norm clipping in front of the step (nothing else runs then), on the same two optimizers, homed, gradients
+present, N alternating processes per setting: `vbg.optim.clip_grad_norm_` + FusedSGD / FusedAdamW against `vbg.optim.clip_in_step` + the
+same; `fuse(opt)` + torch.nn.utils.clip_grad_norm_ against `fuse(opt)` + clip_in_step; and the GradScaler loop with `unscale_` + torch's
+clip against `clip_in_step(scaler=...)` on `fuse(opt, amp_scaling=True)` -- each with the clip biting (max_norm = norm / 2) and not
+biting (2 x norm).  Per iteration (device idle at its start, the gradients put back before it, outside the timed window): host time of
+the calls from the clip to the last step / update, device time between two events around them, and the device operations (kernels,
+copies, memsets) one iteration issues, counted by torch.profiler in an iteration of its own after the timed ones.
+
     python tools/stock_optim_bench.py [--out FILE] [--rounds 9] [--reps 10] [--e2e 3]
-    python tools/stock_optim_bench.py --gradscaler 3 [--out FILE] [--steps 20] [--warmup 5]"""
+    python tools/stock_optim_bench.py --gradscaler 3 [--out FILE] [--steps 20] [--warmup 5]
+    python tools/stock_optim_bench.py --clip 3 [--out FILE] [--steps 20] [--warmup 5]"""
 import argparse
 import os
 import statistics
@@ -288,6 +297,132 @@ def gradscaler(n, steps, warmup, reps, emit):
         emit(f"  {label:<40} " + "  ".join(f"{us:7.1f} ({gbs:5.0f})" if gbs else f"{us:7.1f}" for us, gbs in v))
 
 
+CLIP_SETTINGS = (("flat_old", "FusedSGD / FusedAdamW, clip_grad_norm_"), ("flat_new", "FusedSGD / FusedAdamW, clip_in_step"),
+                 ("stock_old", "fuse(opt), torch clip_grad_norm_"), ("stock_new", "fuse(opt), clip_in_step"),
+                 ("gs_old", "GradScaler: unscale_, torch clip, step"), ("gs_new", "GradScaler: clip_in_step(scaler=), step"))
+
+
+def clip_child(setting, steps, warmup):
+    """one process of the clip mode; prints `CLIP <setting> <bite> host_us device_us device_ops` for the clip biting and not biting"""
+    from vbg import optim as vo
+    dev = torch.device("cuda")
+    flat, gs = setting.startswith("flat"), setting.startswith("gs")
+    new = setting.endswith("new")
+    scale = 65536.0 if gs else 1.0
+    sides = []
+    for kind, meta in (("sgd", cnn_named()), ("adamw", bert_named())):
+        nm = real(meta, dev, 1)
+        cls, kw = (torch.optim.AdamW, ADAMW_KW) if kind == "adamw" else (torch.optim.SGD, SGD_KW)
+        if flat:
+            opt = (vo.FusedAdamW if kind == "adamw" else vo.FusedSGD)(nm, dev, **kw)
+            group = opt.group
+        else:
+            group = vo.FlatGroup(nm, dev)
+            opt = vo.fuse(cls([p for _, p in nm], **kw), amp_scaling=gs)
+        saved = torch.zeros_like(group.gflat)          # gradients where parameters are, zeros in the padding (as backward leaves the buffer)
+        for p, off in zip(group.params, group.offsets):
+            saved[off:off + p.numel()].normal_(0.0, 0.02 * scale, generator=torch.Generator(device=dev).manual_seed(2 + off % 97))
+        sides.append((group, opt, saved))
+    opts = [opt for _, opt, _ in sides]
+    params = [p for group, _, _ in sides for p in group.params]
+    norm = float(torch.sqrt(sum((saved.double() ** 2).sum() for _, _, saved in sides))) / scale
+    scaler = torch.amp.GradScaler("cuda", growth_interval=10 ** 9) if gs else None
+    x = torch.zeros((), device=dev)
+
+    def iteration(max_norm):
+        if gs:
+            scaler.scale(x)
+            if new:
+                vo.clip_in_step(opts, max_norm, scaler=scaler)
+            else:
+                for opt in opts:
+                    scaler.unscale_(opt)
+                torch.nn.utils.clip_grad_norm_(params, max_norm)
+            for opt in opts:
+                scaler.step(opt)
+            scaler.update()
+            return
+        if new:
+            vo.clip_in_step(opts, max_norm)
+        elif flat:
+            vo.clip_grad_norm_(opts, max_norm)
+        else:
+            torch.nn.utils.clip_grad_norm_(params, max_norm)
+        for opt in opts:
+            opt.step()
+
+    def put_back():
+        for group, _, saved in sides:
+            group.gflat.copy_(saved)
+            for p, gv in zip(group.params, group.gviews):
+                if p.grad is not gv:
+                    p.grad = gv
+
+    for bite in (1, 0):
+        max_norm = norm * (0.5 if bite else 2.0)
+        host, devt = [], []
+        for it in range(warmup + steps):
+            put_back()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            t0 = time.perf_counter()
+            iteration(max_norm)
+            t1 = time.perf_counter()
+            e1.record()
+            e1.synchronize()
+            if it >= warmup:
+                host.append((t1 - t0) * 1e6)
+                devt.append(e0.elapsed_time(e1) * 1e3)
+        # the clip did what the setting says: .grad holds the unscaled gradient, times 1/2 where it bites
+        got = float(torch.sqrt(sum((group.gflat.double() ** 2).sum() for group, _, _ in sides)))
+        want = norm * (0.5 if bite else 1.0)
+        assert abs(got - want) <= 1e-3 * want, (setting, bite, got, want)
+        ops_n = -1
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            put_back()
+            torch.cuda.synchronize()
+            with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                iteration(max_norm)
+                torch.cuda.synchronize()
+            ops_n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+        except Exception as e:          # (the count is reported as not measured)
+            print("profiler:", type(e).__name__, e, file=sys.stderr)
+        print(f"CLIP {setting} {bite} {statistics.median(host):.1f} {statistics.median(devt):.1f} {ops_n}", flush=True)
+    for opt in opts:
+        fs = getattr(opt, "_vbg_fused", None)
+        if fs is not None:
+            fs.reconcile()
+            assert fs.fallbacks == 0 and fs.skipped == 0, fs.last_fallback
+
+
+def clip(n, steps, warmup, emit):
+    res = {}
+    for _ in range(n):
+        for setting, _ in CLIP_SETTINGS:
+            try:
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--clip-child", setting, "--steps", str(steps), "--warmup", str(warmup)],
+                                     check=True, capture_output=True, text=True, timeout=300).stdout
+            except subprocess.CalledProcessError as e:
+                print(e.stderr[-4000:], file=sys.stderr, flush=True)
+                raise
+            print(f"  ({setting}: done)", file=sys.stderr, flush=True)
+            for ln in out.splitlines():
+                if ln.startswith("CLIP "):
+                    _, s_, bite, host, devt, ops_n = ln.split()
+                    res.setdefault((s_, int(bite)), []).append((float(host), float(devt), int(ops_n)))
+    emit("gradient-norm clipping in front of the step, cfg2's two optimizers (SGD over the CNN-shaped layout, AdamW over bert-base), homed, gradients")
+    emit(f"present; per iteration clip -> step(sgd) -> step(adamw) (GradScaler settings: scale -> [unscale_ x2] -> clip -> scaler.step x2 -> update);")
+    emit(f"median of {steps} iterations after {warmup}; {n} alternating processes per setting; device ops: kernels + copies + memsets of one iteration (-1: not measured)")
+    for bite in (1, 0):
+        emit("clip biting (max_norm = norm / 2):" if bite else "clip not biting (max_norm = 2 x norm):")
+        for setting, label in CLIP_SETTINGS:
+            r = res[(setting, bite)]
+            emit(f"  {label:<42} host us / iteration: " + "  ".join(f"{h:8.1f}" for h, _, _ in r) + "    device us / iteration: "
+                 + "  ".join(f"{d:8.1f}" for _, d, _ in r) + f"    device ops / iteration {r[0][2]}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -297,6 +432,8 @@ def main():
     ap.add_argument("--e2e-child", default=None, choices=["fuse", "plain"])
     ap.add_argument("--gradscaler", type=int, default=0, help="alternating processes per setting of the GradScaler loop (runs only that)")
     ap.add_argument("--gradscaler-child", default=None, choices=["0", "1"])
+    ap.add_argument("--clip", type=int, default=0, help="alternating processes per setting of the clipping loop (runs only that)")
+    ap.add_argument("--clip-child", default=None, choices=[s_ for s_, _ in CLIP_SETTINGS])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
@@ -306,15 +443,20 @@ def main():
         return e2e_child(a.e2e_child, a.steps, a.warmup)
     if a.gradscaler_child:
         return gradscaler_child(a.gradscaler_child == "1", a.steps, a.warmup, a.reps)
+    if a.clip_child:
+        return clip_child(a.clip_child, a.steps, a.warmup)
     lines = []
 
     def emit(s):
         print(s, flush=True)
         lines.append(s)
 
-    if a.gradscaler:
+    if a.gradscaler or a.clip:
         emit(f"{torch.cuda.get_device_name(0)}")
-        gradscaler(a.gradscaler, a.steps, a.warmup, a.reps, emit)
+        if a.clip:
+            clip(a.clip, a.steps, a.warmup, emit)
+        else:
+            gradscaler(a.gradscaler, a.steps, a.warmup, a.reps, emit)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:

@@ -8,7 +8,9 @@
 // reordered by group: a group is a set of scattered runs of slots).  There is one segmented kernel per rule, on one chunk walk
 // (walk_chunks) and one stream loop (stream_chunk); vbg_sgd_step_seg / vbg_adamw_step_seg translate their groups into the default
 // case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.  vbg_sgd_step_seg_amp / vbg_adam_step_seg_amp
-// are the AMP instantiation of the same two kernels (SegScale below).
+// are the AMP instantiation of the same two kernels (SegScale below), and vbg_sgd_step_seg_clip / vbg_adam_step_seg_clip the same
+// instantiation with one more device scalar, the coefficient of a gradient-norm clip that vbg_grad_sumsq_seg (per-row sums of squares
+// over the same chunk table) and vbg_clip_coef (their sum in double, torch's coefficient) leave in device memory.
 #include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
@@ -113,21 +115,29 @@ constexpr int SEG_THREADS = 256;
 // The AMP form (torch.amp.GradScaler's protocol for optimizers with _step_supports_amp_scaling) reads two fp32 scalars from device
 // memory: found_inf != 0 makes every block return before it touches a buffer; with a scale, every chunk's gradients are first
 // multiplied by inv = float(1 / double(*scale)) (torch's own inverse) in place (unscale_chunk); with scale NULL (the caller unscaled
-// already) g is only read.  The rule then runs on what g holds with gs (1 from the entries), in the statements of the host form.
+// already) g is only read.  The rule then runs on what g holds with gs (1 from the *_amp entries), in the statements of the host form.
+// The *_clip entries add `clip`, the coefficient of clip_grad_norm_ as a third device scalar: g' = (g * inv) * coef, two products each
+// rounded on its own, stored back; a coefficient of exactly 1 with no scale leaves g unwritten (the product would be g).  There
+// found_inf may be NULL (no scaler).
 template <bool AMP> struct SegScale { float gs; };
-template <> struct SegScale<true> { float gs; const float* scale; const float* found_inf; };
+template <> struct SegScale<true> { float gs; const float* scale; const float* found_inf; const float* clip; };
 template <bool AMP> using GradPtr = std::conditional_t<AMP, float*, const float*>;
 
 // -> false: the launch is a skipped step.  Uniform over the launch.
 template <bool AMP>
-__device__ __forceinline__ bool seg_scale(const SegScale<AMP>& sc, float& inv, bool& store_g) {
+__device__ __forceinline__ bool seg_scale(const SegScale<AMP>& sc, float& inv, float& coef, bool& store_g) {
     inv = 1.f;
+    coef = 1.f;
     store_g = false;
     if constexpr (AMP) {
-        if (*sc.found_inf != 0.f) return false;
+        if (sc.found_inf && *sc.found_inf != 0.f) return false;
         if (sc.scale) {
             inv = (float)(1.0 / (double)*sc.scale);
             store_g = true;
+        }
+        if (sc.clip) {
+            coef = *sc.clip;
+            store_g = store_g || coef != 1.f;          // (a NaN coefficient is stored: torch's clip writes the NaNs too)
         }
     }
     return true;
@@ -183,13 +193,16 @@ __device__ __forceinline__ void stream_chunk(const vbg_optim_chunk& ch, float* _
 // The AMP form's own pass over a chunk, ahead of stream_chunk: g *= inv, each product rounded on its own and stored.  A thread
 // writes exactly the float4s it reads back in stream_chunk (same index walk), where they come from the cache: the chunk's traffic
 // to memory is one read and one write of g more, and the rule runs on loaded values in the very statements of the host-scale form.
-__device__ __forceinline__ void unscale_chunk(const vbg_optim_chunk& ch, float* __restrict__ g, float inv) {
+// With a clip coefficient the second product follows the first, rounded on its own as well (torch: unscale_, then the clip's mul_);
+// inv == 1 (no scale) and coef == 1 (no clip) multiply exactly, so one statement serves every combination.
+__device__ __forceinline__ void unscale_chunk(const vbg_optim_chunk& ch, float* __restrict__ g, float inv, float coef) {
     float4* g4 = reinterpret_cast<float4*>(g + ch.start);
     const int n4 = ch.length >> 2;
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
     for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
         float4 gv = g4[i];
-        gv.x = __fmul_rn(gv.x, inv); gv.y = __fmul_rn(gv.y, inv); gv.z = __fmul_rn(gv.z, inv); gv.w = __fmul_rn(gv.w, inv);
+        gv.x = __fmul_rn(__fmul_rn(gv.x, inv), coef); gv.y = __fmul_rn(__fmul_rn(gv.y, inv), coef);
+        gv.z = __fmul_rn(__fmul_rn(gv.z, inv), coef); gv.w = __fmul_rn(__fmul_rn(gv.w, inv), coef);
         g4[i] = gv;
     }
 }
@@ -205,12 +218,12 @@ struct AdamGroups { AdamHp g[VBG_OPTIM_MAX_GROUPS]; };
 template <bool AMP>
 __global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict__ p, GradPtr<AMP> __restrict__ g, float* __restrict__ mom,
                                const vbg_optim_chunk* __restrict__ tbl, int nchunks, SgdGroups hp, SegScale<AMP> sc) {
-    float inv;
+    float inv, coef;
     bool store_g;
-    if (!seg_scale(sc, inv, store_g)) return;
+    if (!seg_scale(sc, inv, coef, store_g)) return;
     const float gs = sc.gs;
     walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
-        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv);
+        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv, coef);
         const SgdHp h = hp.g[ch.group];
         const int first = (h.flags & SGD_FIRST) != 0, nesterov = (h.flags & SGD_NESTEROV) != 0, maximize = (h.flags & SGD_MAXIMIZE) != 0;
         if (h.momentum == 0.f && !h.keep_mom)
@@ -231,12 +244,12 @@ __global__ void __launch_bounds__(SEG_THREADS) sgd_seg_kernel(float* __restrict_
 template <bool AMP>
 __global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict__ p, GradPtr<AMP> __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                 float* __restrict__ vmax, const vbg_optim_chunk* __restrict__ tbl, int nchunks, AdamGroups hp, SegScale<AMP> sc) {
-    float inv;
+    float inv, coef;
     bool store_g;
-    if (!seg_scale(sc, inv, store_g)) return;
+    if (!seg_scale(sc, inv, coef, store_g)) return;
     const float gs = sc.gs;
     walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
-        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv);
+        if constexpr (AMP) if (store_g) unscale_chunk(ch, g, inv, coef);
         const AdamHp h = hp.g[ch.group];
         const float step_size = h.lr / h.bc1;
         const int maximize = (h.flags & ADAM_MAXIMIZE) != 0, coupled = (h.flags & ADAM_COUPLED) != 0;
@@ -253,6 +266,58 @@ __global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict
                 adam_update_opt(pv, gv, mv, vv, none, h.lr, h.b1, h.b2, h.eps, h.wd, step_size, h.bc2_sqrt, 0, maximize, coupled, gs);
             });
     });
+}
+
+// ---- gradient-norm clipping on the device ------------------------------------------------------------------------------
+// The norm pass on the same row walk: block b on row c leaves partials[c] = sum of g[start .. start + length)^2, a plain store (no
+// atomics, nothing to zero beforehand, the same bits on every call).  A thread sums the squares of its own float4s in fp32 (a row of
+// 4096 elements: 4 float4s, 16 products), block_sum adds the 256 thread sums: a short fp32 chain per row, the long sum over rows is
+// left to clip_coef_kernel, in double.  The group field of a row is ignored; what no row covers is not read.
+__global__ void __launch_bounds__(SEG_THREADS) grad_sumsq_seg_kernel(const float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
+                                                                      float* __restrict__ partials) {
+    __shared__ float sh[16];
+    int c = blockIdx.x;
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
+        const int n4 = ch.length >> 2;
+        float acc = 0.f;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+            const float4 gv = g4[i];
+            acc += gv.x * gv.x;
+            acc += gv.y * gv.y;
+            acc += gv.z * gv.z;
+            acc += gv.w * gv.w;
+        }
+        const float r = block_sum(acc, sh);
+        if (threadIdx.x == 0) partials[c] = r;
+        c += (int)gridDim.x;
+    });
+}
+
+// The finish: partials[0 .. n) summed in double in a fixed order (thread t takes t, t + T, ...; then a fixed tree), and the two fp32
+// numbers a clip needs: out[0] = the total norm, out[1] = the coefficient in torch's own statements --
+// `max_norm / (total_norm + 1e-6)` is `(total_norm + 1e-6).reciprocal() * max_norm` there, then `clamp(max=1.0)`, which keeps a NaN
+// (fminf would not) and turns an inf norm into 0.
+constexpr int COEF_THREADS = 256;
+__global__ void __launch_bounds__(COEF_THREADS) clip_coef_kernel(const float* __restrict__ partials, int n, float max_norm, float norm_scale,
+                                                                  const float* __restrict__ grad_scale, float* __restrict__ out) {
+    __shared__ double sh[COEF_THREADS];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += COEF_THREADS) s += (double)partials[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = COEF_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        float total = __fmul_rn((float)sqrt(sh[0]), norm_scale);
+        if (grad_scale) total = __fmul_rn(total, (float)(1.0 / (double)*grad_scale));          // (the gradients still hold scaled values)
+        const float c = __fmul_rn(__fdiv_rn(1.f, __fadd_rn(total, 1e-6f)), max_norm);
+        out[0] = total;
+        out[1] = c > 1.f ? 1.f : c;
+    }
 }
 
 static inline int ew_grid(long long n, int block) {
@@ -346,19 +411,25 @@ extern "C" int vbg_adamw_step_seg(float* p, const float* g, float* m, float* v, 
 // every torch.optim option per group (flags of include/vbg.h): same table, same checks.  mom may be NULL when every group has momentum
 // 0, vmax when no group has the amsgrad flag; a group's bias corrections come from ITS step.  The *_amp entries are the same calls
 // with the scale and the inf flag in device memory (SegScale<true>; found_inf is required, grad_scale may be NULL) and g writable.
+// the device scalars of an AMP launch: 4-byte aligned; without a clip coefficient (the *_amp entries) found_inf is required, with one
+// (the *_clip entries, which refuse a NULL coefficient themselves) it may be NULL
+static inline bool amp_scalars_ok(const SegScale<true>& sc) {
+    return (sc.found_inf || sc.clip) && (uintptr_t)sc.found_inf % 4 == 0 && (uintptr_t)sc.scale % 4 == 0 && (uintptr_t)sc.clip % 4 == 0;
+}
+
 template <bool AMP>
 static int sgd_step_seg_opt(float* p, GradPtr<AMP> g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const vbg_sgd_group_opt* groups,
-                            int ngroups, const SegScale<AMP>& sc, void* stream) {
+                            int ngroups, const SegScale<AMP>& sc, void* stream, int keep_mom = 0) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
-    if constexpr (AMP) VBG_CHECK_ARG(sc.found_inf && (uintptr_t)sc.found_inf % 4 == 0 && (uintptr_t)sc.scale % 4 == 0);
+    if constexpr (AMP) VBG_CHECK_ARG(amp_scalars_ok(sc));
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && chunks && groups);
     SgdGroups hp = {};
     bool any_mom = false;
     for (int i = 0; i < ngroups; ++i) {
         const vbg_sgd_group_opt& s = groups[i];
-        hp.g[i] = SgdHp{s.lr, s.momentum, s.dampening, s.wd, s.flags, 0};
-        any_mom = any_mom || s.momentum != 0.f;
+        hp.g[i] = SgdHp{s.lr, s.momentum, s.dampening, s.wd, s.flags, keep_mom != 0};
+        any_mom = any_mom || s.momentum != 0.f || keep_mom;
     }
     VBG_CHECK_ARG(mom || !any_mom);
     return launch_sgd_seg<AMP>(p, g, mom, chunks, nchunks, hp, sc, stream);
@@ -368,7 +439,7 @@ template <bool AMP>
 static int adam_step_seg_opt(float* p, GradPtr<AMP> g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
                              const vbg_adam_group_opt* groups, int ngroups, const SegScale<AMP>& sc, void* stream) {
     VBG_CHECK_ARG(ngroups >= 1 && ngroups <= VBG_OPTIM_MAX_GROUPS && nchunks >= 0);
-    if constexpr (AMP) VBG_CHECK_ARG(sc.found_inf && (uintptr_t)sc.found_inf % 4 == 0 && (uintptr_t)sc.scale % 4 == 0);
+    if constexpr (AMP) VBG_CHECK_ARG(amp_scalars_ok(sc));
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(p && g && m && v && chunks && groups);
     AdamGroups hp = {};
@@ -394,10 +465,43 @@ extern "C" int vbg_adam_step_seg_opt(float* p, const float* g, float* m, float* 
 
 extern "C" int vbg_sgd_step_seg_amp(float* p, float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const vbg_sgd_group_opt* groups,
                                     int ngroups, const float* grad_scale, const float* found_inf, void* stream) {
-    return sgd_step_seg_opt<true>(p, g, mom, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf}, stream);
+    return sgd_step_seg_opt<true>(p, g, mom, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf, nullptr}, stream);
 }
 
 extern "C" int vbg_adam_step_seg_amp(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
                                      const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream) {
-    return adam_step_seg_opt<true>(p, g, m, v, vmax, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf}, stream);
+    return adam_step_seg_opt<true>(p, g, m, v, vmax, chunks, nchunks, groups, ngroups, SegScale<true>{1.f, grad_scale, found_inf, nullptr}, stream);
+}
+
+// The *_amp entries with the coefficient of a gradient-norm clip (vbg_clip_coef's out + 1) as a third device scalar, required here;
+// found_inf may be NULL (no scaler), host_scale multiplies the gradient inside the rule as grad_scale does in the *_seg_opt entries.
+// keep_mom != 0: a momentum-0 group goes through the momentum statement and writes its buffer, as in vbg_sgd_step_seg.
+extern "C" int vbg_sgd_step_seg_clip(float* p, float* g, float* mom, const vbg_optim_chunk* chunks, int nchunks, const vbg_sgd_group_opt* groups,
+                                     int ngroups, const float* grad_scale, const float* found_inf, const float* clip_coef, float host_scale,
+                                     int keep_mom, void* stream) {
+    VBG_CHECK_ARG(clip_coef);
+    return sgd_step_seg_opt<true>(p, g, mom, chunks, nchunks, groups, ngroups, SegScale<true>{host_scale, grad_scale, found_inf, clip_coef}, stream,
+                                  keep_mom);
+}
+
+extern "C" int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
+                                      const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf,
+                                      const float* clip_coef, float host_scale, void* stream) {
+    VBG_CHECK_ARG(clip_coef);
+    return adam_step_seg_opt<true>(p, g, m, v, vmax, chunks, nchunks, groups, ngroups, SegScale<true>{host_scale, grad_scale, found_inf, clip_coef},
+                                   stream);
+}
+
+extern "C" int vbg_grad_sumsq_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, void* stream) {
+    VBG_CHECK_ARG(nchunks >= 0);
+    if (nchunks == 0) return VBG_OK;
+    VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
+    VBG_LAUNCH(grad_sumsq_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_clip_coef(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, float* out, void* stream) {
+    VBG_CHECK_ARG(n >= 0 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 && (uintptr_t)grad_scale % 4 == 0);
+    VBG_LAUNCH(clip_coef_kernel, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, out);
+    VBG_LAUNCH_RET();
 }

@@ -2418,3 +2418,66 @@ def adam_step_seg_amp(p, g, m, v, vmax, table, groups, grad_scale, found_inf):
                                         for h in groups])
     check(lib.vbg_adam_step_seg_amp(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), sc, fi,
                                     _stream()), "vbg_adam_step_seg_amp")
+
+
+def _clip_scalars(table, grad_scale, found_inf, clip_coef):
+    """the device scalars of the *_seg_clip entries: fp32, one element each, on the table's device; only clip_coef is required"""
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf), ("clip_coef", clip_coef)):
+        if t is None and name != "clip_coef":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
+            raise ValueError(f"segmented clipping optimizer step: {name} must be one fp32 element on the table's device")
+    return (None if grad_scale is None else P(grad_scale)), (None if found_inf is None else P(found_inf)), P(clip_coef)
+
+
+def grad_sumsq_seg(g, table, partials):
+    """vbg_grad_sumsq_seg: partials[c] = sum of squares of row c of `table` (a ChunkTable) over g, c in [0, table.n); one launch, plain
+    stores in a fixed order (the same code in deterministic mode)"""
+    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
+        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
+    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
+        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
+    check(lib.vbg_grad_sumsq_seg(P(g), P(table.rows), table.n, P(partials), _stream()), "vbg_grad_sumsq_seg")
+    return partials
+
+
+def clip_coef(partials, n, max_norm, norm_scale=1.0, grad_scale=None, out=None):
+    """vbg_clip_coef: -> out (2 fp32: total norm, clip coefficient) from partials[0 .. n); grad_scale: a device scalar when the gradients
+    still hold scaled values.  One small launch, no host sync"""
+    if partials.dtype != f32 or not partials.is_contiguous() or not 0 <= n <= partials.numel():
+        raise ValueError("clip coefficient: partials must be contiguous fp32 with at least n elements")
+    if out is None:
+        out = torch.empty((2,), device=partials.device, dtype=f32)
+    if out.dtype != f32 or not out.is_contiguous() or out.numel() < 2 or out.device != partials.device:
+        raise ValueError("clip coefficient: out must be two contiguous fp32 elements on the partials' device")
+    if grad_scale is not None and (not isinstance(grad_scale, torch.Tensor) or grad_scale.dtype != f32 or grad_scale.numel() != 1
+                                   or grad_scale.device != partials.device):
+        raise ValueError("clip coefficient: grad_scale must be one fp32 element on the partials' device")
+    check(lib.vbg_clip_coef(P(partials), int(n), float(max_norm), float(norm_scale), None if grad_scale is None else P(grad_scale), P(out),
+                            _stream()), "vbg_clip_coef")
+    return out
+
+
+def sgd_step_seg_clip(p, g, mom, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0, keep_mom=False):
+    """vbg_sgd_step_seg_clip: sgd_step_seg_amp with the clip coefficient (a device scalar, required) applied to g after the unscale;
+    found_inf may be None (no scaler); host_scale: the host float of sgd_step_seg_opt; keep_mom: momentum-0 groups write `mom` as in
+    sgd_step_seg.  g is overwritten with the unscaled, clipped gradient"""
+    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
+    if mom is None and (keep_mom or any(float(h[1]) != 0.0 for h in groups)):
+        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
+    sc, fi, cc = _clip_scalars(table, grad_scale, found_inf, clip_coef)
+    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
+    check(lib.vbg_sgd_step_seg_clip(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), sc, fi, cc,
+                                    float(host_scale), int(bool(keep_mom)), _stream()), "vbg_sgd_step_seg_clip")
+
+
+def adam_step_seg_clip(p, g, m, v, vmax, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0):
+    """vbg_adam_step_seg_clip: adam_step_seg_amp with the clip coefficient, under the same rules (see sgd_step_seg_clip)"""
+    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
+    if vmax is None and any(int(h[6]) & 1 for h in groups):
+        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
+    sc, fi, cc = _clip_scalars(table, grad_scale, found_inf, clip_coef)
+    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
+                                        for h in groups])
+    check(lib.vbg_adam_step_seg_clip(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), sc, fi,
+                                     cc, float(host_scale), _stream()), "vbg_adam_step_seg_clip")

@@ -520,8 +520,20 @@ class _FlatOptimizer(torch.optim.Optimizer):
             self.runs = run_table(self.group, group_of)
             self.chunk_rows = chunk_rows(self.runs, int(seg_chunk or SEG_CHUNK))
             self.table = ops.chunk_table(self.chunk_rows, len(dicts), self.group.total, self.group.pflat.device)
+        self._vbg_clip = None               # the device coefficient clip_in_step left for the next step()
+        self._clip_tbl = None
         import weakref
         self.group._vbg_optimizer = weakref.ref(self)          # (ViBERTgridNet._home: a group a live optimizer steps is never silently replaced)
+
+    def _clip_table(self):
+        """the chunk table clip_in_step's norm pass and the clipping step walk: the param groups' own table, or -- one param group, whose
+        plain step is the whole-range launch -- one kernel group over the whole layout, built once"""
+        if self.segmented:
+            return self.table
+        if self._clip_tbl is None:
+            g = self.group
+            self._clip_tbl = ops.chunk_table(chunk_rows([(0, g.total, 0)], SEG_CHUNK), 1, g.total, g.pflat.device)
+        return self._clip_tbl
 
     @staticmethod
     def _check_options(opts: Dict):
@@ -537,6 +549,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         super().add_param_group(param_group)
 
     def zero_grad(self, set_to_none: bool = False):
+        self._vbg_clip = None               # (a pending clip coefficient belongs to the gradients it was computed from)
         self.group.zero_grad()
 
     # ---- checkpoint format of torch.optim ---------------------------------------------------------------------------
@@ -611,7 +624,13 @@ class FusedSGD(_FlatOptimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if self.segmented:
+        clip = _take_clip(self)
+        if clip is not None:
+            first = ops.SGD_FIRST if self.steps == 0 else 0
+            ops.sgd_step_seg_clip(self.group.pflat, self.group.gflat, self.mom, self._clip_table(),
+                                  [(g["lr"], g["momentum"], 0.0, g["weight_decay"], first) for g in self.param_groups], None, None, clip,
+                                  self.grad_scale, keep_mom=True)
+        elif self.segmented:
             ops.sgd_step_seg(self.group.pflat, self.group.gflat, self.mom, self.table,
                              [(g["lr"], g["momentum"], g["weight_decay"]) for g in self.param_groups], self.steps == 0, self.grad_scale)
         else:
@@ -638,7 +657,12 @@ class FusedAdamW(_FlatOptimizer):
     @torch.no_grad()
     def step(self, closure=None):
         self.steps += 1
-        if self.segmented:
+        clip = _take_clip(self)
+        if clip is not None:
+            ops.adam_step_seg_clip(self.group.pflat, self.group.gflat, self.m, self.v, None, self._clip_table(),
+                                   [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.steps, 0) for g in self.param_groups],
+                                   None, None, clip, self.grad_scale)
+        elif self.segmented:
             ops.adamw_step_seg(self.group.pflat, self.group.gflat, self.m, self.v, self.table,
                                [(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in self.param_groups],
                                self.steps, self.grad_scale)
@@ -652,6 +676,17 @@ class FusedAdamW(_FlatOptimizer):
 # ---- stock torch.optim objects on the fused kernels --------------------------------------------------------------------------
 class _Fallback(Exception):
     """this step() call goes to torch's own step (the reason is the message)"""
+
+
+class _NoGradients(_Fallback):
+    pass
+
+
+def _take_clip(optimizer):
+    """the clip coefficient clip_in_step left on the optimizer (one fp32 element of device memory) or None; a step consumes it"""
+    clip = getattr(optimizer, "_vbg_clip", None)
+    optimizer._vbg_clip = None
+    return clip
 
 
 class _FusedState:
@@ -727,7 +762,7 @@ class _FusedState:
             undo()
             self.skipped += 1
 
-    def table(self, assign, ngroups):
+    def table(self, assign, ngroups, note=True):
         t = self.tables.get(assign)
         if t is None:
             g = self.group
@@ -736,7 +771,8 @@ class _FusedState:
                 self.tables.pop(next(iter(self.tables)))
             t = self.tables[assign] = ops.chunk_table(rows, ngroups, g.total, g.pflat.device)
             t.chunk_rows = rows
-        self.rows = t.chunk_rows
+        if note:
+            self.rows = t.chunk_rows
         return t
 
 
@@ -756,6 +792,7 @@ class _FusedStock:
     def step(self, closure=None):
         fs = self._vbg_fused
         fs.reconcile()
+        clip = _take_clip(self)          # (consumed by this call whatever becomes of it: launch, skipped step, fallback)
         # GradScaler's protocol (fuse(amp_scaling=True)): for the length of this call the scaler has put two device scalars on the
         # object, `found_inf` and `grad_scale` (None: the caller has run scaler.unscale_ already)
         found_inf = getattr(self, "found_inf", None) if fs.amp else None
@@ -771,9 +808,9 @@ class _FusedStock:
                 fs.last_fallback = str(e)
             else:
                 if amp is None:
-                    self._vbg_launch(fs, *plan)
+                    self._vbg_launch(fs, *plan, clip=clip)
                 else:
-                    undo = self._vbg_launch(fs, *plan, amp=amp)
+                    undo = self._vbg_launch(fs, *plan, amp=amp, clip=clip)
                     created = [p for p in self.state if p not in known]
                     fs.defer(found_inf, lambda: self._vbg_undo(undo, created))
                 fs.launches += 1
@@ -789,6 +826,7 @@ class _FusedStock:
                 fs.skipped += 1
                 return None
             self._vbg_unscale(amp[0])
+            self._vbg_clip_grads(clip)
             # (torch's single-tensor and foreach steps read the two attributes themselves and refuse them: out of sight for the call,
             # back for GradScaler to delete)
             hidden = {k: self.__dict__.pop(k) for k in ("grad_scale", "found_inf") if k in self.__dict__}
@@ -796,7 +834,12 @@ class _FusedStock:
                 return _parent_step(self._vbg_parent)(self, closure)
             finally:
                 self.__dict__.update(hidden)
+        self._vbg_clip_grads(clip)
         return _parent_step(self._vbg_parent)(self, closure)
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._vbg_clip = None               # (a pending clip coefficient belongs to the gradients it was computed from)
+        return super().zero_grad(set_to_none)
 
     @staticmethod
     def _vbg_amp_check(fs, grad_scale, found_inf):
@@ -818,6 +861,19 @@ class _FusedStock:
         if grad_scale is None:
             return
         inv = grad_scale.double().reciprocal().float()
+        for (dev, _), grads in self._vbg_grads().items():
+            torch._amp_foreach_non_finite_check_and_unscale_(grads, torch.zeros(1, device=dev), inv.to(dev))
+
+    def _vbg_clip_grads(self, clip):
+        """a pending clip coefficient for a step that falls back to torch's own: the present gradients times the device scalar, in
+        place, as torch.nn.utils.clip_grad_norm_ applies it"""
+        if clip is None:
+            return
+        for (dev, _), grads in self._vbg_grads().items():
+            torch._foreach_mul_(grads, clip.reshape(()).to(dev))
+
+    def _vbg_grads(self):
+        """(device, dtype) -> the present gradients (the values of a sparse one)"""
         by = {}
         for pg in self.param_groups:
             for p in pg["params"]:
@@ -827,8 +883,7 @@ class _FusedStock:
                 if g.is_sparse:
                     g = g._values()
                 by.setdefault((g.device, g.dtype), []).append(g)
-        for (dev, _), grads in by.items():
-            torch._amp_foreach_non_finite_check_and_unscale_(grads, torch.zeros(1, device=dev), inv.to(dev))
+        return by
 
     def _vbg_present(self, fs):
         """[(param group index, parameter, slot index)] of the parameters with a gradient, after the checks that decide whether this
@@ -853,11 +908,18 @@ class _FusedStock:
                     raise _Fallback("a .grad is not the flat gradient view (sparse, replaced or cast)")
                 present.append((k, p, i))
         if group is None:
-            raise _Fallback("no parameter has a gradient")
+            raise _NoGradients("no parameter has a gradient")
         if not group.valid():
             raise _Fallback("the parameters moved away from their flat buffer (Module.to / a fresh .data)")
         fs.adopt(group)
         return present
+
+    def _vbg_norm_table(self):
+        """clip_in_step: (FlatGroup, chunk table over the rows of the parameters with a gradient); the table is the step's own whenever
+        that has one kernel group"""
+        fs = self._vbg_fused
+        have = {i for _, _, i in self._vbg_present(fs)}
+        return fs.group, fs.table(tuple(0 if i in have else -1 for i in range(len(fs.group.params))), 1, note=False)
 
     def state_dict(self):
         """torch's checkpoint, with the state tensors cloned: the views would drag the whole flat buffers into the file"""
@@ -901,7 +963,7 @@ class _StockSGD(_FusedStock, torch.optim.SGD):
         assign, combos = _combos(fs, keys)
         return assign, combos, homes
 
-    def _vbg_launch(self, fs, assign, combos, homes, amp=None):
+    def _vbg_launch(self, fs, assign, combos, homes, amp=None, clip=None):
         undo = []
         for st, p, i, first in homes:
             if amp is not None and first:          # skipped: the slot was never written (and home() does not zero it), the key goes again
@@ -914,7 +976,9 @@ class _StockSGD(_FusedStock, torch.optim.SGD):
             flags = ops.SGD_NESTEROV * bool(pg["nesterov"]) + ops.SGD_MAXIMIZE * bool(pg["maximize"]) + ops.SGD_FIRST * first
             hp.append((float(pg["lr"]), float(pg["momentum"]), float(pg["dampening"]), float(pg["weight_decay"]), flags))
         g = fs.group
-        if amp is None:
+        if clip is not None:
+            ops.sgd_step_seg_clip(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, *(amp or (None, None)), clip)
+        elif amp is None:
             ops.sgd_step_seg_opt(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, 1.0)
         else:
             ops.sgd_step_seg_amp(g.pflat, g.gflat, fs.flat.get("momentum_buffer"), fs.table(assign, len(hp)), hp, *amp)
@@ -936,7 +1000,7 @@ class _AdamStep(_FusedStock):
         assign, combos = _combos(fs, keys)
         return assign, combos, homes
 
-    def _vbg_launch(self, fs, assign, combos, homes, amp=None):
+    def _vbg_launch(self, fs, assign, combos, homes, amp=None, clip=None):
         steps, undo = [], []
         for st, p, i, fresh, ams in homes:
             if fresh and amp is not None:          # skipped: an entry that was empty is empty again
@@ -957,10 +1021,13 @@ class _AdamStep(_FusedStock):
             hp.append((float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), float(pg["weight_decay"]), step, flags))
         g = fs.group
         bufs = (g.pflat, g.gflat, fs.buffer("exp_avg"), fs.buffer("exp_avg_sq"), fs.buffer("max_exp_avg_sq") if any_ams else None, fs.table(assign, len(hp)), hp)
-        if amp is None:
+        if clip is not None:
+            ops.adam_step_seg_clip(*bufs, *(amp or (None, None)), clip)
+        elif amp is None:
             ops.adam_step_seg_opt(*bufs, 1.0)
         else:
             ops.adam_step_seg_amp(*bufs, *amp)
+        if amp is not None:
             undo.insert(0, lambda: torch._foreach_sub_(steps, 1))          # (bias corrections always come from the true step count)
         torch._foreach_add_(steps, 1)
         return undo
@@ -1016,6 +1083,7 @@ def fuse(optimizer, seg_chunk=None, amp_scaling=False):
                          "schedulers, so that they wrap the fused step")
     optimizer.__class__ = _STOCK[cls]
     optimizer._vbg_fused = _FusedState(seg_chunk, amp_scaling)
+    optimizer._vbg_clip = None
     if amp_scaling:
         optimizer._step_supports_amp_scaling = True
     optimizer._patch_step_function()          # the step pre / post hooks of torch.optim.Optimizer, around the new step
@@ -1034,6 +1102,75 @@ def clip_grad_norm_(optimizers, max_norm: float, norm_scale: float = 1.0) -> flo
         for o in optimizers:
             ops.scale_(o.group.gflat, coef)
     return total
+
+
+_CLIP_PARTIALS = {}          # device -> the partials buffer clip_in_step's norm launches share (grown, never shrunk)
+
+
+def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (norm type 2) folded into the optimizer step, with no host sync and no pass of its own over the
+    gradients beyond the norm: one `vbg_grad_sumsq_seg` launch per optimizer over its chunk table, one `vbg_clip_coef`, and the
+    coefficient stays in device memory, pending on every listed optimizer until its next `step()` (or `scaler.step(optimizer)`), whose
+    launch multiplies the gradients by it -- stored back to `.grad`, as torch leaves them -- right before the rule reads them
+    (`vbg_sgd_step_seg_clip` / `vbg_adam_step_seg_clip`).  Returns the total norm as a 0-dim device tensor.
+
+        total = vbg.optim.clip_in_step([optimizer_cnn, optimizer_bert], max_norm=2)          # pipeline/train_val_utils.py:281-282
+        optimizer_cnn.step(); optimizer_bert.step()
+
+    optimizers: any mix of FusedSGD / FusedAdamW and fuse()d stock optimizers -- all those whose gradients count towards the one norm.
+    A stock optimizer contributes the parameters whose `.grad` is not None (torch's clip skips the others too), a FusedSGD / FusedAdamW
+    its whole layout.  norm_scale multiplies the norm (FlatReducer's 1 / world), as in clip_grad_norm_.  scaler: pass the GradScaler
+    when the gradients still hold scaled values (no `scaler.unscale_` call): the norm is divided by its scale on the device, and
+    `scaler.step(optimizer)` on a `fuse(optimizer, amp_scaling=True)` object unscales, clips and steps in the one launch; on any other
+    optimizer the scaler unscales as it always does and the launch only clips.
+    A step that falls back to torch's own (fuse(): a closure, ...) multiplies the present gradients by the coefficient first
+    (`torch._foreach_mul_`); a step skipped by found_inf consumes the coefficient; `zero_grad()` before the step drops it; a second call
+    while one is pending raises.  (A GradScaler that finds an inf never calls step() on an optimizer fused without amp_scaling: the
+    coefficient then waits for the loop's zero_grad().)"""
+    optimizers = list(optimizers)
+    if not optimizers:
+        raise ValueError("clip_in_step: no optimizers")
+    work = []
+    for o in optimizers:
+        if not isinstance(o, (_FlatOptimizer, _FusedStock)):
+            raise TypeError("clip_in_step takes FusedSGD / FusedAdamW and optimizers made by fuse(), not " + type(o).__qualname__)
+        if getattr(o, "_vbg_clip", None) is not None:
+            raise RuntimeError("clip_in_step: a clip coefficient is still pending on an optimizer (step() consumes it, zero_grad() drops it)")
+        if isinstance(o, _FlatOptimizer):
+            work.append((o.group, o._clip_table()))
+            continue
+        try:
+            work.append(o._vbg_norm_table())
+        except _NoGradients:
+            pass          # (nothing to count; its step will fall back, with nothing to multiply)
+        except _Fallback as e:
+            raise RuntimeError(f"clip_in_step: the gradients of a fuse()d optimizer are not one flat buffer ({e})") from None
+    if not work:
+        raise RuntimeError("clip_in_step: no listed optimizer has a gradient")
+    dev = work[0][0].gflat.device
+    if any(g.gflat.device != dev for g, _ in work):
+        raise ValueError("clip_in_step: the optimizers' flat buffers live on more than one device")
+    grad_scale = None
+    if scaler is not None and scaler.is_enabled():
+        from torch.amp.grad_scaler import OptState
+        if any(scaler._per_optimizer_states[id(o)]["stage"] is OptState.UNSCALED for o in optimizers):
+            raise RuntimeError("clip_in_step(scaler=...) after scaler.unscale_(optimizer): the gradients are unscaled already, leave scaler out")
+        grad_scale = scaler._scale
+        if grad_scale is None:
+            raise RuntimeError("clip_in_step(scaler=...): the scaler has not scaled a loss yet")
+    n = sum(t.n for _, t in work)
+    partials = _CLIP_PARTIALS.get(dev)
+    if partials is None or partials.numel() < n:
+        partials = _CLIP_PARTIALS[dev] = torch.empty((max(n, 1024),), device=dev, dtype=torch.float32)
+    at = 0
+    for g, t in work:
+        ops.grad_sumsq_seg(g.gflat, t, partials[at:at + t.n])
+        at += t.n
+    out = ops.clip_coef(partials, n, max_norm, norm_scale, grad_scale)
+    coef = out[1:]
+    for o in optimizers:
+        o._vbg_clip = coef
+    return out[0]
 
 
 class FlatReducer:

@@ -427,7 +427,8 @@ int vbg_dropout_add_ln_bwd_pair(const float* dy, const float* xhat, const float*
                                 void* stream);
 /* attention probabilities, in place on the grouped score buffer: for group g (= seq*heads + head)
  * rows L=len[g/heads], row stride ldp[g/heads], block offset off[g]; P = softmax(S*scale);
- * dropped entries are stored NEGATED (sign bit = dropped), kept entries unscaled; pad columns = 0. */
+ * dropped entries are stored NEGATED (sign bit = dropped), kept entries unscaled; pad columns = 0.
+ * maxlen <= 1024 (an argument error beyond). */
 int vbg_softmax_fwd(float* s, const long long* off, const int* len, const int* ldp, int ngroups, int heads,
                     int maxlen, float scale, float drop_p, unsigned long long seed, unsigned long long stream_id,
                     void* stream);

@@ -1,9 +1,11 @@
 """Fused attention kernels (csrc/attn.hip, through the C-ABI) against a plain fp64 statement of transformers' BertSelfAttention
-(softmax(Q K^T / sqrt(dh)) -> dropout -> P V, model/BERTgrid_generator.py:134) and torch autograd of it, on packed variable-length
-sequences.  Tolerances are written at each assert (fp32-grade: the kernels split every operand exactly into three bf16 pieces)."""
+(softmax(Q K^T / sqrt(dh)) -> dropout -> P V, model/BERTgrid_generator.py:134) and its gradient (tests/attn_restate.py, held to torch
+autograd by tests/test_attn_restate_host.py), on packed variable-length sequences.  Tolerances are written at each assert (fp32-grade: the kernels split every operand exactly into three bf16 pieces)."""
 import numpy as np
 import pytest
 import torch
+
+import attn_restate as R
 
 pytestmark = pytest.mark.gpu
 
@@ -24,14 +26,6 @@ def _meta(seq_len, heads):
     m.tasks = torch.from_numpy(tasks.reshape(-1)).int().to(dev)
     m.ntok_pad, m.mask_words, m.ntasks = ntok_pad, mask_words, int(tasks.shape[0])
     return m, row0, pad_off, mask_off
-
-
-def _keep_matrix(words, off, head, L):
-    """mask words [L_pad, nkb] of one (sequence, head) -> bool [L, L] (query, key)"""
-    nkb = (L + 31) // 32
-    w = words[off + head * nkb * 32 * nkb: off + (head + 1) * nkb * 32 * nkb].reshape(nkb * 32, nkb).astype(np.uint32)
-    bits = ((w[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & 1).reshape(nkb * 32, nkb * 32)
-    return bits[:L, :L].astype(bool)
 
 
 def _run(seq_len, heads, p, seed=0, form=0, dscale=1.0):
@@ -75,36 +69,22 @@ def _run(seq_len, heads, p, seed=0, form=0, dscale=1.0):
     ops.set_amp(False)
     torch.cuda.synchronize()
     assert int(slot.max().item()) == int(dqkv.abs().max().view(torch.int32).item())
-    # ---- reference: fp64, per (sequence, head) --------------------------------------------------------------------
+    # ---- reference: the fp64 statement of tests/attn_restate.py, per (sequence, head) ------------------------------------------------
     ks = ops.attn_keep_scale(p) if p > 0 else 1.0
-    mq = masks[0].cpu().numpy().view(np.uint32) if p > 0 else None
-    mk = masks[1].cpu().numpy().view(np.uint32) if p > 0 else None
-    x = qkv.double().requires_grad_(True)
-    Oref = torch.zeros(ntok, hid, dtype=torch.float64)
-    lse_ref = torch.zeros(heads, meta.ntok_pad, dtype=torch.float64)
-    outs = []
+    keeps = None
     keep_frac = []
-    for s, L in enumerate(seq_len):
-        r0 = int(row0[s])
-        for h in range(heads):
-            q = x[r0:r0 + L, h * 64:(h + 1) * 64]
-            k = x[r0:r0 + L, hid + h * 64:hid + (h + 1) * 64]
-            v = x[r0:r0 + L, 2 * hid + h * 64:2 * hid + (h + 1) * 64]
-            sc = (q @ k.t()) * scale
-            pr = torch.softmax(sc, -1)
-            lse_ref[h, int(pad_off[s]):int(pad_off[s]) + L] = torch.logsumexp(sc, -1).detach()
-            if p > 0:
-                keep = _keep_matrix(mq, int(mask_off[s]), h, L)
-                keep_t = _keep_matrix(mk, int(mask_off[s]), h, L)
-                assert (keep == keep_t.T).all(), "the two mask orientations disagree"
-                keep_frac.append(keep.mean() if L >= 128 else None)
-                pr = pr * torch.from_numpy(keep).double() * ks
-            outs.append((r0, L, h, pr @ v))
-    for r0, L, h, o in outs:
-        Oref[r0:r0 + L, h * 64:(h + 1) * 64] = o.detach()
-    loss = sum((o * dO[r0:r0 + L, h * 64:(h + 1) * 64].double()).sum() for r0, L, h, o in outs)
-    loss.backward()
-    return dict(O=O.cpu().double(), Oref=Oref, lse=torch.where(lse[1] > 0, lse[0] - torch.log(lse[1].clamp_min(1e-30)), torch.zeros_like(lse[0])).cpu().double(), lse_ref=lse_ref, dqkv=dqkv.cpu().double(), dref=x.grad,
+    if p > 0:
+        mq, mk = masks[0].cpu().numpy().view(np.uint32), masks[1].cpu().numpy().view(np.uint32)
+        keeps = R.keep_matrices(mq, mask_off, seq_len, heads)
+        for (s, h), keep in keeps.items():
+            assert (keep == R.keep_matrix(mk, int(mask_off[s]), h, seq_len[s]).T).all(), "the two mask orientations disagree"
+            keep_frac.append(keep.mean() if seq_len[s] >= 128 else None)
+    ref = R.statement(qkv, dO, seq_len, heads, scale, keeps, ks)
+    Oref = ref["O"]
+    lse_ref = torch.zeros(heads, meta.ntok_pad, dtype=torch.float64)
+    lse_ref[:, meta.tok_pad.cpu().long()] = ref["lse"]
+    dref = torch.cat([ref["dq"], ref["dk"], ref["dv"]], 1)
+    return dict(O=O.cpu().double(), Oref=Oref, lse=torch.where(lse[1] > 0, lse[0] - torch.log(lse[1].clamp_min(1e-30)), torch.zeros_like(lse[0])).cpu().double(), lse_ref=lse_ref, dqkv=dqkv.cpu().double(), dref=dref,
                 keep_frac=[f for f in keep_frac if f is not None], hid=hid)
 
 

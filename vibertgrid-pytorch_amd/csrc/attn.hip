@@ -11,7 +11,7 @@
 // rows (LDS-DMA, two stages):
 //   FWD : own = queries, stream = (K, V).  S^T = K Q^T (lane = query, registers = keys: the softmax statistics are lane-local),
 //         online softmax, O^T += V^T Pd^T (V^T fragments by ds_read_b64_tr_b16).  Writes O and the row statistics (m, 1 / l).
-//   DQ  : own = queries, stream = (K, V).  delta = rowsum(dO o O) in the prologue; P^T = exp(S^T - m) / l, dP^T = V dO^T,
+//   DQ  : own = queries, stream = (K, V).  delta = rowsum(dO o O) in the prologue; P^T = exp(S^T - m) / l (0 for keys past L), dP^T = V dO^T,
 //         dS^T = P^T o (dP^T - delta), dQ^T += K^T dS^T; writes the rows' own sum P dP as the delta of the DKV pass.
 //   DKV : own = keys,    stream = (Q, dO). P = exp(S - m) / l (lane = key, registers = queries), dP = dO V^T,
 //         dV^T += dO^T Pd, dK^T += Q^T dS.
@@ -589,6 +589,14 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const vbg_attn_desc p) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) pr[r] = __expf(s[r] * (scale * cinv[0]) - m_own) * il_own;
                     sprod(im1, st[1], dp);
+                    // the tail tile: keys past the sequence are zero rows with the score 0, i.e. the "probability" exp(-m) / l -- inf once
+                    // m < -88.7 (then 0 inf = NaN in dsum), and past fp16's range behind the dS scale of FORM 1 / 2 for a few units already
+                    // (inf times the zero K row = NaN in the product).  They carry none, as in the forward pass.
+                    if (t * 32 + 32 > L) {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh >= L) pr[r] = 0.f;
+                    }
                     const float dmul = dinv * cinv[1];
                     float gmax = 0.f;
 #pragma unroll
@@ -670,6 +678,9 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const vbg_attn_desc p) {
     const long long orow = (long long)(row0 + own0 + lr) * p.ldo;
     const long long krow = (long long)(row0 + own0 + lr) * p.ldk;
     float vmax = 0.f;                                          // max |value stored into p.out| of this lane (backward, p.out_amax)
+    // a softmax over ONE key is constant (P = 1): dS = P (dP - delta) = 0, so dQ and dK are zero -- stored as exact zeros, as torch and the
+    // unfused route give them, not as the rounding residue of dP - delta (delta is summed from dO o O, dP by the matrix cores)
+    const bool one_key = L == 1;
     auto store = [&](const f32x16 (&acc)[2], float mul, int col, float* dst) {
 #pragma unroll
         for (int db = 0; db < 2; ++db)
@@ -742,12 +753,12 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const vbg_attn_desc p) {
                 acc0[db][4 * j] = acc0[db][4 * j] * dsi - c * kb.x; acc0[db][4 * j + 1] = acc0[db][4 * j + 1] * dsi - c * kb.y;
                 acc0[db][4 * j + 2] = acc0[db][4 * j + 2] * dsi - c * kb.z; acc0[db][4 * j + 3] = acc0[db][4 * j + 3] * dsi - c * kb.w;
             }
-        store(acc0, scale, head * 64, p.out);
+        store(acc0, one_key ? 0.f : scale, head * 64, p.out);
         if (lh == 0) p.delta[lsoff + own0 + lr] = dnew;
       }
     } else {
       if (live) {
-        store(acc0, scale * dsi, hid + head * 64, p.out);
+        store(acc0, one_key ? 0.f : scale * dsi, hid + head * 64, p.out);
         store(acc1, dinv * IESC, 2 * hid + head * 64, p.out);
       }
     }

@@ -430,10 +430,12 @@ __global__ __launch_bounds__(1024) void ln_fold_rows_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------
-// attention softmax: one wave per (group, row); L <= 512 -> 8 elements per lane
+// attention softmax: one wave per (group, row); SM_PER elements per lane: 8 for L <= 512, 16 up to L = 1024 (the unfused route is the one
+// that takes sequences past the fused kernels' 512)
 // ------------------------------------------------------------------------------------------
-constexpr int SM_PER = 8;
+constexpr int SM_MAXLEN = 1024;
 
+template <int SM_PER>
 __global__ __launch_bounds__(64) void softmax_fwd_kernel(float* s, const long long* __restrict__ off,
                                                          const int* __restrict__ len, const int* __restrict__ ldp,
                                                          int heads, int maxlen, float scale, uint32_t drop_thr,
@@ -476,6 +478,7 @@ __global__ __launch_bounds__(64) void softmax_fwd_kernel(float* s, const long lo
     }
 }
 
+template <int SM_PER>
 __global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* __restrict__ pbuf, float* dpbuf,
                                                          const long long* __restrict__ off, const int* __restrict__ len,
                                                          const int* __restrict__ ldp, int heads, float scale,
@@ -785,20 +788,28 @@ extern "C" int vbg_softmax_fwd(float* s, const long long* off, const int* len, c
                                int maxlen, float scale, float drop_p, unsigned long long seed, unsigned long long sid,
                                void* stream) {
     VBG_CHECK_ARG(s && off && len && ldp && heads > 0 && ngroups >= 0 && ngroups % heads == 0);
-    VBG_CHECK_ARG(maxlen >= 0 && maxlen <= 64 * SM_PER && drop_p >= 0.f && drop_p < 1.f);
+    VBG_CHECK_ARG(maxlen >= 0 && maxlen <= SM_MAXLEN && drop_p >= 0.f && drop_p < 1.f);
     if (ngroups == 0 || maxlen == 0) return VBG_OK;
-    VBG_LAUNCH(softmax_fwd_kernel, dim3(maxlen, ngroups), dim3(64), 0, (hipStream_t)stream, s, off, len, ldp, heads,
-                       maxlen, scale, drop_threshold(drop_p), seed, sid);
+#define SM_GO(PER)                                                                                                              \
+    VBG_LAUNCH(softmax_fwd_kernel<PER>, dim3(maxlen, ngroups), dim3(64), 0, (hipStream_t)stream, s, off, len, ldp, heads, \
+               maxlen, scale, drop_threshold(drop_p), seed, sid)
+    if (maxlen <= 512) SM_GO(8);
+    else SM_GO(16);
+#undef SM_GO
     VBG_LAUNCH_RET();
 }
 
 extern "C" int vbg_softmax_bwd(const float* p, float* dp, const long long* off, const int* len, const int* ldp, int ngroups,
                                int heads, int maxlen, float scale, float drop_p, void* stream) {
     VBG_CHECK_ARG(p && dp && off && len && ldp && heads > 0 && ngroups >= 0 && ngroups % heads == 0);
-    VBG_CHECK_ARG(maxlen >= 0 && maxlen <= 64 * SM_PER && drop_p >= 0.f && drop_p < 1.f);
+    VBG_CHECK_ARG(maxlen >= 0 && maxlen <= SM_MAXLEN && drop_p >= 0.f && drop_p < 1.f);
     if (ngroups == 0 || maxlen == 0) return VBG_OK;
-    VBG_LAUNCH(softmax_bwd_kernel, dim3(maxlen, ngroups), dim3(64), 0, (hipStream_t)stream, p, dp, off, len, ldp,
-                       heads, scale, 1.0f / (1.0f - drop_p));
+#define SM_GO(PER)                                                                                                              \
+    VBG_LAUNCH(softmax_bwd_kernel<PER>, dim3(maxlen, ngroups), dim3(64), 0, (hipStream_t)stream, p, dp, off, len, ldp, \
+               heads, scale, 1.0f / (1.0f - drop_p))
+    if (maxlen <= 512) SM_GO(8);
+    else SM_GO(16);
+#undef SM_GO
     VBG_LAUNCH_RET();
 }
 

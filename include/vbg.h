@@ -714,6 +714,20 @@ int vbg_sgd_step_seg_clip(float* p, float* g, float* mom, const vbg_optim_chunk*
 int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, float* vmax, const vbg_optim_chunk* chunks, int nchunks,
                            const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf,
                            const float* clip_coef, float host_scale, void* stream);
+/* torch.amp.GradScaler's own pass over the gradients (GradScaler._unscale_grads_: a loop over every parameter and several
+ * _amp_foreach_non_finite_check_and_unscale_ launches per optimizer and step) on the row walk above, for gradients that are views of one
+ * flat buffer (vbg.optim.fuse_scaler).  Same table and alignment contract as vbg_grad_sumsq_seg: the group field is ignored, what no row
+ * covers is neither read nor written, nchunks == 0 is a no-op.  found_inf and inv_scale are device scalars, required (also with
+ * nchunks == 0) and 4-byte aligned.  found_inf is only ever SET: *found_inf = 1.0f when a covered element is inf or NaN (a plain store
+ * of the same value from every block that saw one: no atomics, the same code in deterministic mode), left alone otherwise -- the caller
+ * hands in a zero, as torch's op expects.
+ * vbg_grad_unscale_check_seg: that torch op over the rows.  *inv_scale == 1.0f (GradScaler._check_inf_per_device): g is only read,
+ *   4 B per element.  Otherwise every covered element becomes g * *inv_scale, one rounded fp32 product, non-finite elements included
+ *   (as torch stores them): 8 B per element.
+ * vbg_grad_sumsq_seg_inf: vbg_grad_sumsq_seg (same partials, bit for bit) with the per-element test in its loop.  The flag comes from
+ *   the elements, not from the sums: finite gradients whose squares overflow leave an inf partial and no flag. */
+int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunks, int nchunks, const float* inv_scale, float* found_inf, void* stream);
+int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

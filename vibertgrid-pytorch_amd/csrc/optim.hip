@@ -10,7 +10,9 @@
 // case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.  vbg_sgd_step_seg_amp / vbg_adam_step_seg_amp
 // are the AMP instantiation of the same two kernels (SegScale below), and vbg_sgd_step_seg_clip / vbg_adam_step_seg_clip the same
 // instantiation with one more device scalar, the coefficient of a gradient-norm clip that vbg_grad_sumsq_seg (per-row sums of squares
-// over the same chunk table) and vbg_clip_coef (their sum in double, torch's coefficient) leave in device memory.
+// over the same chunk table) and vbg_clip_coef (their sum in double, torch's coefficient) leave in device memory.  The same row walk
+// carries GradScaler's own pass over the gradients: vbg_grad_unscale_check_seg (its inf check and unscale_) and vbg_grad_sumsq_seg_inf
+// (the norm pass with that check riding along).
 #include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
@@ -273,10 +275,32 @@ __global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict
 // atomics, nothing to zero beforehand, the same bits on every call).  A thread sums the squares of its own float4s in fp32 (a row of
 // 4096 elements: 4 float4s, 16 products), block_sum adds the 256 thread sums: a short fp32 chain per row, the long sum over rows is
 // left to clip_coef_kernel, in double.  The group field of a row is ignored; what no row covers is not read.
+// GradScaler's test of four elements, carried as a sum: x * 0 is a zero for a finite x and NaN for an inf or a NaN, so z stays a zero
+// exactly as long as everything folded into it was finite (torch's isfinite, element by element) -- one fused multiply-add per element,
+// the arithmetic of the norm pass's own loop, and nothing to branch on.  IEEE semantics: this library is not built with finite-math
+// flags (csrc/Makefile), and tests/test_gpu_fused_scaler.py plants each of +inf, -inf and NaN at every place of the walk.
+__device__ __forceinline__ void fold_finite4(float& z, const float4& v) {
+    z = __fmaf_rn(v.x, 0.f, z);
+    z = __fmaf_rn(v.y, 0.f, z);
+    z = __fmaf_rn(v.z, 0.f, z);
+    z = __fmaf_rn(v.w, 0.f, z);
+}
+
+// What a block learnt about its rows, told to GradScaler's flag: set, never cleared (the caller hands in a zero, as torch's
+// _amp_foreach_non_finite_check_and_unscale_ expects one).  One block-wide OR after the walk, then a plain store of 1.0f from one lane;
+// several blocks may store the same value (no atomics on device memory, the same code in deterministic mode).  Every thread of the block calls this.
+__device__ __forceinline__ void raise_found_inf(bool bad, float* __restrict__ found_inf) {
+    if (__syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.f;
+}
+
+// CHECK (vbg_grad_sumsq_seg_inf): the same walk, sums and stores, with GradScaler's inf check riding in the loop -- decided per ELEMENT
+// (a row of finite values whose squares overflow leaves an inf partial and the flag alone).  found_inf is not read without CHECK.
+template <bool CHECK>
 __global__ void __launch_bounds__(SEG_THREADS) grad_sumsq_seg_kernel(const float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
-                                                                      float* __restrict__ partials) {
+                                                                      float* __restrict__ partials, float* __restrict__ found_inf) {
     __shared__ float sh[16];
     int c = blockIdx.x;
+    float z = 0.f;
     walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
         const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
         const int n4 = ch.length >> 2;
@@ -284,6 +308,7 @@ __global__ void __launch_bounds__(SEG_THREADS) grad_sumsq_seg_kernel(const float
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
         for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
             const float4 gv = g4[i];
+            if constexpr (CHECK) fold_finite4(z, gv);
             acc += gv.x * gv.x;
             acc += gv.y * gv.y;
             acc += gv.z * gv.z;
@@ -293,6 +318,34 @@ __global__ void __launch_bounds__(SEG_THREADS) grad_sumsq_seg_kernel(const float
         if (threadIdx.x == 0) partials[c] = r;
         c += (int)gridDim.x;
     });
+    if constexpr (CHECK) raise_found_inf(!(z == 0.f), found_inf);
+}
+
+// torch._amp_foreach_non_finite_check_and_unscale_ over the rows of a chunk table (GradScaler._unscale_grads_ on gradients that are views
+// of one flat buffer): every covered element is tested, then replaced by g * inv, one rounded product, non-finite ones included -- unless
+// inv is exactly 1 (GradScaler's check-only call), when g is only read: 4 B per element instead of 8.  inv is uniform over the launch.
+__global__ void __launch_bounds__(SEG_THREADS) grad_unscale_check_seg_kernel(float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
+                                                                              const float* __restrict__ inv_scale, float* __restrict__ found_inf) {
+    const float inv = *inv_scale;
+    const bool store = inv != 1.f;
+    float z = 0.f;
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        float4* g4 = reinterpret_cast<float4*>(g + ch.start);
+        const int n4 = ch.length >> 2;
+        if (store) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+                float4 gv = g4[i];
+                fold_finite4(z, gv);
+                gv.x = __fmul_rn(gv.x, inv); gv.y = __fmul_rn(gv.y, inv); gv.z = __fmul_rn(gv.z, inv); gv.w = __fmul_rn(gv.w, inv);
+                g4[i] = gv;
+            }
+        } else {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) fold_finite4(z, g4[i]);
+        }
+    });
+    raise_found_inf(!(z == 0.f), found_inf);
 }
 
 // The finish: partials[0 .. n) summed in double in a fixed order (thread t takes t, t + T, ...; then a fixed tree), and the two fp32
@@ -496,7 +549,28 @@ extern "C" int vbg_grad_sumsq_seg(const float* g, const vbg_optim_chunk* chunks,
     VBG_CHECK_ARG(nchunks >= 0);
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
-    VBG_LAUNCH(grad_sumsq_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials);
+    VBG_LAUNCH(grad_sumsq_seg_kernel<false>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials,
+               (float*)nullptr);
+    VBG_LAUNCH_RET();
+}
+
+// GradScaler's hooks (vbg.optim.fuse_scaler).  The two device scalars are required and 4-byte aligned, whatever nchunks is; the flag is
+// only ever set.
+extern "C" int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, void* stream) {
+    VBG_CHECK_ARG(nchunks >= 0 && found_inf && (uintptr_t)found_inf % 4 == 0);
+    if (nchunks == 0) return VBG_OK;
+    VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
+    VBG_LAUNCH(grad_sumsq_seg_kernel<true>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials,
+               found_inf);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunks, int nchunks, const float* inv_scale, float* found_inf, void* stream) {
+    VBG_CHECK_ARG(nchunks >= 0 && inv_scale && found_inf && (uintptr_t)inv_scale % 4 == 0 && (uintptr_t)found_inf % 4 == 0);
+    if (nchunks == 0) return VBG_OK;
+    VBG_CHECK_ARG(g && chunks && ALIGNED16(g) && ALIGNED16(chunks));
+    VBG_LAUNCH(grad_unscale_check_seg_kernel, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, inv_scale,
+               found_inf);
     VBG_LAUNCH_RET();
 }
 

@@ -234,6 +234,8 @@ SIGNATURES = {
     "vbg_clip_coef": (c_int, [c_vp, c_int, c_f, c_f, c_vp, c_vp, c_vp]),
     "vbg_sgd_step_seg_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroupOpt), c_int, c_vp, c_vp, c_vp, c_f, c_int, c_vp]),
     "vbg_adam_step_seg_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamGroupOpt), c_int, c_vp, c_vp, c_vp, c_f, c_vp]),
+    "vbg_grad_unscale_check_seg": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "vbg_grad_sumsq_seg_inf": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
     "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_sum_det_ws_elems": (c_int, []),

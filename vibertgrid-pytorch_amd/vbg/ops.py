@@ -2441,6 +2441,37 @@ def grad_sumsq_seg(g, table, partials):
     return partials
 
 
+def _scaler_scalars(table, **scalars):
+    """the device scalars of GradScaler's hooks: fp32, one element each, on the table's device, all required"""
+    for name, t in scalars.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
+            raise ValueError(f"segmented inf check: {name} must be one fp32 element on the table's device")
+
+
+def grad_unscale_check_seg(g, table, inv_scale, found_inf):
+    """vbg_grad_unscale_check_seg: torch._amp_foreach_non_finite_check_and_unscale_ over the rows of `table` (a ChunkTable) of g; one launch.
+    found_inf (a device scalar the caller zeroed) becomes 1.0 when a covered element is inf or NaN and is left alone otherwise;
+    inv_scale (a device scalar): exactly 1.0 -> g is only read, anything else -> every covered element is overwritten with g * inv_scale"""
+    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
+        raise ValueError("segmented inf check: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
+    _scaler_scalars(table, inv_scale=inv_scale, found_inf=found_inf)
+    _untag(g)          # (written through the raw pointer: torch's version counter does not move)
+    check(lib.vbg_grad_unscale_check_seg(P(g), P(table.rows), table.n, P(inv_scale), P(found_inf), _stream()), "vbg_grad_unscale_check_seg")
+    return found_inf
+
+
+def grad_sumsq_seg_inf(g, table, partials, found_inf):
+    """vbg_grad_sumsq_seg_inf: grad_sumsq_seg (the same partials, bit for bit) with GradScaler's inf check in the same pass over g:
+    found_inf as in grad_unscale_check_seg, decided by the elements, not by the sums"""
+    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
+        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
+    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
+        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
+    _scaler_scalars(table, found_inf=found_inf)
+    check(lib.vbg_grad_sumsq_seg_inf(P(g), P(table.rows), table.n, P(partials), P(found_inf), _stream()), "vbg_grad_sumsq_seg_inf")
+    return partials
+
+
 def clip_coef(partials, n, max_norm, norm_scale=1.0, grad_scale=None, out=None):
     """vbg_clip_coef: -> out (2 fp32: total norm, clip coefficient) from partials[0 .. n); grad_scale: a device scalar when the gradients
     still hold scaled values.  One small launch, no host sync"""

@@ -1122,7 +1122,9 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
     its whole layout.  norm_scale multiplies the norm (FlatReducer's 1 / world), as in clip_grad_norm_.  scaler: pass the GradScaler
     when the gradients still hold scaled values (no `scaler.unscale_` call): the norm is divided by its scale on the device, and
     `scaler.step(optimizer)` on a `fuse(optimizer, amp_scaling=True)` object unscales, clips and steps in the one launch; on any other
-    optimizer the scaler unscales as it always does and the launch only clips.
+    optimizer the scaler unscales as it always does and the launch only clips.  With a scaler made by fuse_scaler() the norm launches are
+    `vbg_grad_sumsq_seg_inf`: they leave the scaler's inf flag for each optimizer as well, and its `scaler.step(optimizer)` under the
+    amp_scaling protocol launches no check of its own.
     A step that falls back to torch's own (fuse(): a closure, ...) multiplies the present gradients by the coefficient first
     (`torch._foreach_mul_`); a step skipped by found_inf consumes the coefficient; `zero_grad()` before the step drops it; a second call
     while one is pending raises.  (A GradScaler that finds an inf never calls step() on an optimizer fused without amp_scaling: the
@@ -1137,18 +1139,18 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
         if getattr(o, "_vbg_clip", None) is not None:
             raise RuntimeError("clip_in_step: a clip coefficient is still pending on an optimizer (step() consumes it, zero_grad() drops it)")
         if isinstance(o, _FlatOptimizer):
-            work.append((o.group, o._clip_table()))
+            work.append((o, o.group, o._clip_table()))
             continue
         try:
-            work.append(o._vbg_norm_table())
+            work.append((o, *o._vbg_norm_table()))
         except _NoGradients:
             pass          # (nothing to count; its step will fall back, with nothing to multiply)
         except _Fallback as e:
             raise RuntimeError(f"clip_in_step: the gradients of a fuse()d optimizer are not one flat buffer ({e})") from None
     if not work:
         raise RuntimeError("clip_in_step: no listed optimizer has a gradient")
-    dev = work[0][0].gflat.device
-    if any(g.gflat.device != dev for g, _ in work):
+    dev = work[0][1].gflat.device
+    if any(g.gflat.device != dev for _, g, _ in work):
         raise ValueError("clip_in_step: the optimizers' flat buffers live on more than one device")
     grad_scale = None
     if scaler is not None and scaler.is_enabled():
@@ -1158,19 +1160,131 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
         grad_scale = scaler._scale
         if grad_scale is None:
             raise RuntimeError("clip_in_step(scaler=...): the scaler has not scaled a loss yet")
-    n = sum(t.n for _, t in work)
+    n = sum(t.n for _, _, t in work)
     partials = _CLIP_PARTIALS.get(dev)
     if partials is None or partials.numel() < n:
         partials = _CLIP_PARTIALS[dev] = torch.empty((max(n, 1024),), device=dev, dtype=torch.float32)
+    # a fuse_scaler()ed scaler: its inf check rides in the norm launches, one flag per optimizer (torch skips per optimizer: a joint flag
+    # would skip an optimizer whose own gradients are finite), fresh for this call
+    flags = torch.zeros((len(work),), device=dev, dtype=torch.float32).unbind(0) if grad_scale is not None and isinstance(scaler, _FusedScaler) else None
     at = 0
-    for g, t in work:
-        ops.grad_sumsq_seg(g.gflat, t, partials[at:at + t.n])
+    for j, (_, g, t) in enumerate(work):
+        if flags is None:
+            ops.grad_sumsq_seg(g.gflat, t, partials[at:at + t.n])
+        else:
+            ops.grad_sumsq_seg_inf(g.gflat, t, partials[at:at + t.n], flags[j])
         at += t.n
     out = ops.clip_coef(partials, n, max_norm, norm_scale, grad_scale)
     coef = out[1:]
     for o in optimizers:
         o._vbg_clip = coef
+    if flags is not None:
+        # kept beside GradScaler's own per-optimizer record, which update() discards, and with the coefficient of this call: the flag
+        # speaks for the gradients that coefficient was computed from, and for no others (_FusedScaler._check_inf_per_device)
+        for j, (o, _, _) in enumerate(work):
+            scaler._per_optimizer_states[id(o)][_CLIP_FLAG] = (flags[j], coef)
     return out[0]
+
+
+# ---- torch.amp.GradScaler on the fused kernels ---------------------------------------------------------------------------------
+_CLIP_FLAG = "_vbg_clip_found_inf"          # key of clip_in_step's (flag, coefficient) in GradScaler._per_optimizer_states[id(optimizer)]
+
+
+class _ScalerState:
+    """what fuse_scaler() keeps on the scaler instance (`_vbg_fused`)"""
+
+    def __init__(self):
+        self.launches = 0          # inf checks / unscale passes that were one vbg_grad_unscale_check_seg launch
+        self.reused = 0            # inf checks that launched nothing: clip_in_step's norm pass had left the flag
+        self.fallbacks = 0         # passes that went to torch's own _unscale_grads_
+        self.last_fallback = None
+
+
+def _scaler_target(optimizer):
+    """(FlatGroup, chunk table) of the gradients GradScaler would visit on `optimizer`, when they are one flat buffer"""
+    if isinstance(optimizer, _FusedStock):
+        return optimizer._vbg_norm_table()          # (the table clip_in_step uses: the rows of the parameters with a gradient)
+    if isinstance(optimizer, _FlatOptimizer):
+        g = optimizer.group
+        if not g.valid():
+            raise _Fallback("the parameters moved away from their flat buffer (Module.to / a fresh .data)")
+        # (a parameter without a gradient keeps its zeroed slot of the buffer, which the step reads with the rest)
+        if any(p.grad is not None and p.grad is not gv for p, gv in zip(g.params, g.gviews)):
+            raise _Fallback("a .grad is not the flat gradient view (sparse, replaced or cast)")
+        return g, optimizer._clip_table()
+    raise _Fallback("not a fuse()d torch.optim optimizer, FusedSGD or FusedAdamW")
+
+
+class _FusedScaler:
+    """the two methods of the classes fuse_scaler() switches a GradScaler instance to.  Everything else -- scale(), step(), unscale_(),
+    update(), the scale and its growth tracker, state_dict() -- is torch's."""
+
+    def _unscale_grads_(self, optimizer, inv_scale, found_inf, allow_fp16):
+        """torch's pass (a Python loop over every parameter, a multi-tensor launch per device and dtype) as ONE launch over the chunk
+        table of the optimizer's flat gradient buffer.  Both of torch's callers land here: unscale_ with the real inverse scale,
+        _check_inf_per_device with 1.0, which makes the launch read-only"""
+        fs = self._vbg_fused
+        try:
+            group, table = _scaler_target(optimizer)
+            dev = group.gflat.device
+            for t in (inv_scale, found_inf):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != dev:
+                    raise _Fallback("inv_scale / found_inf is not one fp32 element on the flat buffers' device")
+        except _Fallback as e:
+            fs.fallbacks += 1
+            fs.last_fallback = str(e)
+            return super()._unscale_grads_(optimizer, inv_scale, found_inf, allow_fp16)
+        ops.grad_unscale_check_seg(group.gflat, table, inv_scale, found_inf)
+        fs.launches += 1
+        return {found_inf.device: found_inf}
+
+    def _check_inf_per_device(self, optimizer):
+        """the inf check of `scaler.step(optimizer)` under the `_step_supports_amp_scaling` protocol: nothing to launch when
+        clip_in_step(scaler=self) read these very gradients for the norm -- its coefficient is still pending on the optimizer -- and
+        left the flag"""
+        state = self._per_optimizer_states[id(optimizer)]
+        left = state.pop(_CLIP_FLAG, None)
+        if left is not None and left[1] is getattr(optimizer, "_vbg_clip", None):
+            self._vbg_fused.reused += 1
+            state["found_inf_per_device"] = {left[0].device: left[0]}
+            return state["found_inf_per_device"]
+        return super()._check_inf_per_device(optimizer)
+
+
+class _FusedGradScaler(_FusedScaler, torch.amp.GradScaler):
+    pass
+
+
+class _FusedCudaGradScaler(_FusedScaler, torch.cuda.amp.GradScaler):
+    pass
+
+
+_SCALERS = {torch.amp.GradScaler: _FusedGradScaler, torch.cuda.amp.GradScaler: _FusedCudaGradScaler}
+
+
+def fuse_scaler(scaler):
+    """Make a torch.amp.GradScaler (or the torch.cuda.amp.GradScaler the reference constructs, train_SROIE.py) run its pass over the
+    gradients -- the inf check of every `scaler.step(optimizer)`, the unscale of `scaler.unscale_(optimizer)` -- as ONE HIP launch per
+    optimizer (`vbg_grad_unscale_check_seg`) instead of a Python loop over every parameter and several multi-tensor launches.  Returns
+    the SAME object, its class switched to a subclass that overrides two private methods; the scale, the growth tracker, update(),
+    state_dict() and every public method stay torch's:
+
+        scaler = vbg.optim.fuse_scaler(torch.cuda.amp.GradScaler(enabled=amp))
+
+    The launch serves fuse()d torch.optim optimizers whose present gradients are the flat views of one group (the check-only call of the
+    `amp_scaling=True` protocol reads the gradients, 4 B per element, and writes nothing) and FusedSGD / FusedAdamW (the generic route:
+    gradients times the inverse scale, stored back).  After `clip_in_step(optimizers, max_norm, scaler=scaler)` the check of
+    `scaler.step(optimizer)` launches nothing at all: the norm pass has tested every element it read (`vbg_grad_sumsq_seg_inf`) and left
+    one flag per optimizer.  Everything else goes to torch's own pass for that call: an optimizer of any other class, parameters that
+    are not homed (yet) or moved away, a `.grad` that is not the flat view, no gradient at all, a scaler on another device than the
+    buffers.  `scaler._vbg_fused` counts `launches`, `reused` and `fallbacks` and keeps the reason of the last one."""
+    cls = type(scaler)
+    if cls not in _SCALERS:
+        raise ValueError(f"fuse_scaler() takes instances of exactly torch.amp.GradScaler or torch.cuda.amp.GradScaler, not "
+                         f"{cls.__module__}.{cls.__qualname__}")
+    scaler.__class__ = _SCALERS[cls]
+    scaler._vbg_fused = _ScalerState()
+    return scaler
 
 
 class FlatReducer:

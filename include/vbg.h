@@ -638,6 +638,29 @@ int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const 
                     int stop_tag, int* backptr, int* path, float* score, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Field decoding of the returned class scores (csrc/decode.hip).  Replaces the per-segment loop every caller of the reference runs
+ * over `pred_label` [N, C]: pipeline/train_val_utils.py:440-493 (with strcmp_tresh), eval_SROIE.py:119-169, eval_EPHOIE.py,
+ * deployment/inference_SROIE.py:65-124, deployment/inference_EPHOIE.py:31-81 -- `.softmax(0)`, `.argmax(0)`, `.item()` per segment, the
+ * grouping into runs of equal class, the mean score of every run and the best run of every class.  ONE launch, one workgroup per
+ * document; document d owns the rows h_doc_off[d] .. h_doc_off[d + 1] of x.  `h_doc_off` is HOST memory (ndoc + 1 entries, not
+ * decreasing, first >= 0), copied into the kernel arguments -- no device copy, no sync -- 512 documents to a launch.
+ *   per row   p = softmax(x[i]) with vbg_row_softmax's arithmetic (same bits); cls[i] = first index of max p, score[i] = p[cls[i]];
+ *             use_thresh != 0 and (double)score[i] < thresh: cls[i] = 0 (the comparison is made in double; the score stays);
+ *   runs      maximal stretches of equal cls inside a document: (start, len, mean), start relative to the document's first row,
+ *             mean = the fp64 sum of the run's scores / len -- the reference's sequential double sum bit for bit (every partial sum is
+ *             exact for C <= 64 and fewer than 2^20 rows per document: csrc/decode.hip; both limits are argument errors beyond);
+ *   filing    every run but the last under its own class; the last run under the class of the document's row n - 2 (the reference's
+ *             `prev_class` quirk: the class of the run in front of it when it has a single row), under class C - 1 when n == 1;
+ *   best      best[d * C + c] = the first filed record of class c, in filing order, with the strictly greatest mean;
+ *             start = -1, len = 0, mean = 0 for a class without a record (every class of an empty document).
+ * cls int32 [N], score fp32 [N] with N = h_doc_off[ndoc].  Rows holding NaN or infinities are outside the contract (their document's
+ * records are meaningless; nothing faults).  No atomics on global memory: deterministic.  ndoc == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vbg_decode_rec { int start; int len; double mean; } vbg_decode_rec;      /* 16 bytes */
+int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls, float* score,
+                     vbg_decode_rec* best, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a15. optimizers on flat fp32 ranges  (torch.optim.SGD / AdamW; train_SROIE.py:223-235)
  * ------------------------------------------------------------------------------------------ */
 int vbg_sgd_step(float* p, const float* g, float* mom, long long n, float lr, float momentum, float wd,

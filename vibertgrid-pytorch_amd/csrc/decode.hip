@@ -1,0 +1,184 @@
+// Field decoding of the returned class scores: what every caller of the reference does with `pred_label` [N, C] one segment at a
+// time (pipeline/train_val_utils.py:440-493, eval_SROIE.py:119-169, eval_EPHOIE.py, deployment/inference_SROIE.py:65-124,
+// deployment/inference_EPHOIE.py:31-81) -- softmax, argmax, threshold, grouping into runs of equal class, the fp64 mean score of every
+// run and the best run of every class -- in ONE launch, one 256-thread workgroup per document.  The strings stay on the host
+// (vbg/decode.py joins them for the winning runs only).
+//
+// The document is walked in chunks of 256 rows, one row per thread, with four barriers per chunk:
+//   rows      each thread forms its row's softmax with the helper row_softmax_kernel uses (vbg_common.h: same bits), takes the first
+//             index of the largest probability and applies the threshold in DOUBLE (the reference compares two Python floats);
+//   run heads a row whose left neighbour has another class starts a run.  Wave ballots give every head the head in front of it;
+//   run sums  P = the prefix sum of the scores in fp64 (wave scan + wave totals + the carry of the chunks before); the run between two
+//             consecutive heads h1 < h2 has the sum P(h2 - 1) - P(h1 - 1), and the head h2 files it under the class of row h2 - 1;
+//   winner    per class, in LDS only: a 64-bit max over the bit pattern of the mean (positive doubles order like their bit patterns),
+//             a barrier, a 64-bit min over (start << 20 | len) among the runs that equal it, a barrier, and one thread per class folds
+//             the chunk's winner into the running one (strictly greater only: earlier chunks hold earlier runs).
+// Scores live in registers for the one chunk that needs them; nothing the block wrote is read back.  No global atomics, no
+// cross-block traffic: the result does not depend on scheduling, with or without the deterministic mode.
+//
+// WHY THE ORDER OF THE SUMS DOES NOT MATTER.  The reference adds a run's scores one after the other in double.  A score is
+// expf(0) * (1 / s) = the fp32 value 1 / s, where s is the fp32 sum of C <= 64 terms expf(x - max) in (0, 1], one of them expf(0) == 1:
+// 1 <= s <= 64, so the score lies in [2^-7, 1] and is a multiple of 2^-30 (fp32 keeps 24 bits below its leading one).  A sum of fewer
+// than 2^20 such scores is a multiple of 2^-30 below 2^20: at most 50 bits, which a double holds exactly.  Hence every partial sum the
+// reference forms is exact, every prefix sum P is exact, the difference of two prefix sums is exact, and sum / len is rounded once:
+// the means are the reference's bit for bit, for any grouping of the additions.  That is what the entry's limits (C <= 64, fewer than
+// 2^20 rows per document) buy.  Rows with NaN or infinite scores are outside this contract: they give meaningless records for their
+// document (the prefix sum is NaN from there on) but every loop below is bounded by the row count, not by data.
+//
+// The filing quirk of the reference is reproduced, not repaired: its loop files the LAST run under the class of row N - 2 (`prev_class`
+// is updated after the append at :472-477) -- the run's own class if it has two or more rows, the class of the run before it if it
+// has one, and class C - 1 for N == 1 (prev_class == -1 indexes the list from the back).
+#include "vbg_common.h"
+#include "../../include/vbg.h"
+
+namespace vbg {
+
+constexpr int DEC_THREADS = 256;            // rows per chunk
+constexpr int DEC_WAVES = DEC_THREADS / 64;
+constexpr int DEC_MAX_C = 64;
+constexpr int DEC_ROW_BITS = 20;            // a document has fewer than 2^20 rows (see the argument above)
+constexpr int DEC_DOCS = 512;               // documents per launch: their row ranges travel in the kernel arguments
+
+struct dec_docs { int off[DEC_DOCS + 1]; };
+
+__device__ __forceinline__ int highest_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
+
+__global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* __restrict__ x, dec_docs docs, int doc0, int C,
+                                                                   int use_thresh, double thresh, int* __restrict__ cls_out,
+                                                                   float* __restrict__ score_out, vbg_decode_rec* __restrict__ best) {
+    __shared__ int s_cls[DEC_THREADS];                      // class of the chunk's rows
+    __shared__ double s_pb[DEC_THREADS];                    // sum of the document's scores in front of the row
+    __shared__ double s_wtot[DEC_WAVES];
+    __shared__ int s_whead[DEC_WAVES];                      // last run head inside the wave's rows, or -1
+    __shared__ unsigned long long s_cmax[DEC_MAX_C], s_ckey[DEC_MAX_C];     // per class, this chunk: largest mean, then smallest (start, len)
+    __shared__ unsigned long long s_bmean[DEC_MAX_C], s_bkey[DEC_MAX_C];    // per class, so far (mean bits 0: no record)
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int r0 = docs.off[blockIdx.x], n = docs.off[blockIdx.x + 1] - r0;
+    if (t < DEC_MAX_C) { s_cmax[t] = 0ull; s_ckey[t] = ~0ull; s_bmean[t] = 0ull; s_bkey[t] = ~0ull; }
+    __syncthreads();
+
+    // carried from chunk to chunk, the same in every thread
+    double total = 0.0;      // sum of the scores of the rows in front of the chunk
+    int open_head = -1;      // first row of the run that is open at the chunk's start
+    double open_pb = 0.0;    // sum of the scores in front of that row
+    int prev_last = -1;      // class of the row in front of the chunk (-1: none, so row 0 is a head)
+    int cls_nm2 = -1;        // class of row n - 2
+    for (int base = 0; base < n; base += DEC_THREADS) {
+        const int g = base + t;
+        const bool valid = g < n;
+        int c = -1;
+        float sc = 0.f;
+        if (valid) {
+            const float* p = x + (long long)(r0 + g) * C;
+            float mx;
+            const float inv = row_softmax_norm(p, C, mx);
+            c = 0;
+            sc = row_softmax_prob(p[0], mx, inv);
+            for (int k = 1; k < C; ++k) {
+                const float v = row_softmax_prob(p[k], mx, inv);
+                if (v > sc) { sc = v; c = k; }
+            }
+            if (use_thresh && (double)sc < thresh) c = 0;
+            cls_out[r0 + g] = c;
+            score_out[r0 + g] = sc;
+        }
+        double incl = (double)sc;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        s_cls[t] = c;
+        if (lane == 63) s_wtot[w] = incl;
+        __syncthreads();                                                            // 1: classes and wave totals of the chunk
+        double pb = total + (incl - (double)sc), chunk_total = 0.0;
+#pragma unroll
+        for (int k = 0; k < DEC_WAVES; ++k) {
+            const double wt = s_wtot[k];
+            if (k < w) pb += wt;
+            chunk_total += wt;
+        }
+        const int left = t > 0 ? s_cls[t - 1] : prev_last;
+        const bool head = valid && c != left;
+        if (base + DEC_THREADS >= n) cls_nm2 = n - 2 >= base ? s_cls[n - 2 - base] : prev_last;
+        const int chunk_last = s_cls[DEC_THREADS - 1];
+        s_pb[t] = pb;
+        const unsigned long long hm = __ballot(head);
+        if (lane == 0) s_whead[w] = hm ? base + w * 64 + highest_bit(hm) : -1;
+        __syncthreads();                                                            // 2: prefix sums and wave heads
+        // a head closes the run in front of it and files it under that run's class
+        unsigned long long bits = 0ull, key = 0ull;
+        int fc = -1;
+        if (head && g > 0) {
+            const unsigned long long lower = hm & ((1ull << lane) - 1ull);
+            int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
+            for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
+            double ppb;
+            if (ph >= 0) ppb = s_pb[ph - base];
+            else { ph = open_head; ppb = open_pb; }
+            const int len = g - ph;
+            bits = (unsigned long long)__double_as_longlong((pb - ppb) / (double)len);
+            key = ((unsigned long long)ph << DEC_ROW_BITS) | (unsigned long long)len;
+            fc = left;
+            atomicMax(&s_cmax[fc], bits);
+        }
+        int lh = -1;
+        for (int k = DEC_WAVES - 1; k >= 0 && lh < 0; --k) lh = s_whead[k];
+        if (lh >= 0) { open_head = lh; open_pb = s_pb[lh - base]; }
+        total += chunk_total;
+        prev_last = chunk_last;
+        __syncthreads();                                                            // 3: the chunk's largest mean per class
+        if (fc >= 0 && s_cmax[fc] == bits) atomicMin(&s_ckey[fc], key);
+        __syncthreads();                                                            // 4: and its first run among those
+        if (t < C) {
+            if (s_cmax[t] > s_bmean[t]) { s_bmean[t] = s_cmax[t]; s_bkey[t] = s_ckey[t]; }
+            s_cmax[t] = 0ull;
+            s_ckey[t] = ~0ull;
+        }
+    }
+    __syncthreads();
+    if (n > 0 && t == 0) {                                  // the last run, filed the reference's way (last in its class's list)
+        const int fc = n == 1 ? C - 1 : cls_nm2;
+        const int len = n - open_head;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong((total - open_pb) / (double)len);
+        if (bits > s_bmean[fc]) {
+            s_bmean[fc] = bits;
+            s_bkey[fc] = ((unsigned long long)open_head << DEC_ROW_BITS) | (unsigned long long)len;
+        }
+    }
+    __syncthreads();
+    if (t < C) {
+        vbg_decode_rec r;
+        const unsigned long long m = s_bmean[t], key = s_bkey[t];
+        r.start = m ? (int)(key >> DEC_ROW_BITS) : -1;
+        r.len = m ? (int)(key & ((1ull << DEC_ROW_BITS) - 1ull)) : 0;
+        r.mean = m ? __longlong_as_double((long long)m) : 0.0;
+        best[(long long)(doc0 + blockIdx.x) * C + t] = r;
+    }
+}
+
+}  // namespace vbg
+
+using namespace vbg;
+
+extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
+                                float* score, vbg_decode_rec* best, void* stream) {
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
+    VBG_CHECK_ARG(h_doc_off[0] >= 0);
+    for (int d = 0; d < ndoc; ++d) {
+        const long long nd = (long long)h_doc_off[d + 1] - h_doc_off[d];
+        VBG_CHECK_ARG(nd >= 0 && nd < (1ll << DEC_ROW_BITS));
+    }
+    if (ndoc == 0) return VBG_OK;
+    VBG_CHECK_ARG(best);
+    if (h_doc_off[ndoc] > h_doc_off[0]) VBG_CHECK_ARG(x && cls && score);
+    for (int d0 = 0; d0 < ndoc; d0 += DEC_DOCS) {
+        const int nd = ndoc - d0 < DEC_DOCS ? ndoc - d0 : DEC_DOCS;
+        dec_docs docs;
+        for (int i = 0; i <= nd; ++i) docs.off[i] = h_doc_off[d0 + i];
+        for (int i = nd + 1; i <= DEC_DOCS; ++i) docs.off[i] = docs.off[nd];
+        VBG_LAUNCH(field_decode_kernel, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, docs, d0, C, use_thresh, thresh, cls, score,
+                   best);
+    }
+    VBG_LAUNCH_RET();
+}

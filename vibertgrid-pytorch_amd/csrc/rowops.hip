@@ -646,12 +646,9 @@ __global__ void row_softmax_kernel(const float* __restrict__ x, int rows, int co
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     const float* p = x + (long long)r * cols;
-    float mx = p[0];
-    for (int c = 1; c < cols; ++c) mx = fmaxf(mx, p[c]);
-    float s = 0.f;
-    for (int c = 0; c < cols; ++c) s += expf(p[c] - mx);
-    const float inv = 1.f / s;
-    for (int c = 0; c < cols; ++c) y[(long long)r * cols + c] = expf(p[c] - mx) * inv;
+    float mx;
+    const float inv = row_softmax_norm(p, cols, mx);
+    for (int c = 0; c < cols; ++c) y[(long long)r * cols + c] = row_softmax_prob(p[c], mx, inv);
 }
 
 static inline int ew_grid(long long n, int block) {

@@ -52,6 +52,19 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return r;
 }
 
+// ---- softmax of one short row ([rows, cols] class scores, cols small): the ONE statement of its arithmetic, shared by
+// row_softmax_kernel (rowops.hip) and field_decode_kernel (decode.hip) so that both give the same bits.
+// row_softmax_norm: the row's maximum and 1 / (sum in column order of expf(x - max)); row_softmax_prob: one probability.
+__device__ __forceinline__ float row_softmax_norm(const float* __restrict__ p, int cols, float& mx_out) {
+    float mx = p[0];
+    for (int c = 1; c < cols; ++c) mx = fmaxf(mx, p[c]);
+    float s = 0.f;
+    for (int c = 0; c < cols; ++c) s += expf(p[c] - mx);
+    mx_out = mx;
+    return 1.f / s;
+}
+__device__ __forceinline__ float row_softmax_prob(float v, float mx, float inv) { return expf(v - mx) * inv; }
+
 // ---- counter-based RNG for dropout: one 32-bit draw per (seed, stream, index) ----------
 // (splitmix64-style finaliser; deterministic, so backward regenerates the forward mask)
 __host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t stream, uint64_t idx) {

@@ -1753,6 +1753,25 @@ def row_softmax(x):
     return y
 
 
+def field_decode(x, doc_off=None, thresh=None):
+    """x [N, C] fp32 class scores (device) -> (cls int32 [N], score fp32 [N], best float64 [ndoc * C, 2]) in ONE launch
+    (vbg_field_decode, include/vbg.h).  doc_off: HOST row ranges, ndoc + 1 ints (None: one document, all rows); thresh: a Python
+    float compared in double, or None.  A row of `best` is one 16-byte vbg_decode_rec (int32 start, int32 len, float64 mean) carried as
+    two doubles: vbg.decode views it after its one copy to the host."""
+    _chk_f32(x)
+    N, ncls = x.shape
+    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
+    ndoc = len(off) - 1
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"vbg_field_decode: doc_off {off[:4]}... does not fit {N} rows")
+    cls = torch.empty(N, dtype=i32, device=x.device)
+    score = torch.empty(N, dtype=f32, device=x.device)
+    best = torch.empty(ndoc * ncls, 2, dtype=torch.float64, device=x.device)
+    check(lib.vbg_field_decode(P(x.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, int(thresh is not None),
+                               0.0 if thresh is None else float(thresh), P(cls), P(score), P(best), _stream()), "vbg_field_decode")
+    return cls, score, best
+
+
 def gelu_bwd_(h, dg):
     _untag(dg)
     check(lib.vbg_gelu_bwd(P(h), P(dg), dg.numel(), _stream()), "vbg_gelu_bwd")

@@ -605,6 +605,13 @@ int vbg_ce_fwd(const float* logits, long long ld, int ncls, const int* elem, con
 int vbg_ce_bwd(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n,
                const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W,
                float* dlogits_accum, void* stream);
+/* the same two with the element count in device memory: the first min(*n_dev, n_cap) elements of a list of capacity n_cap (the grid
+ * is sized by n_cap); nothing at or beyond the count is read or written.  (The lists of vbg_sample_select / vbg_ohem_topk.) */
+int vbg_ce_fwd_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                   const int* n_dev, const float* weight, int up_shift, int H, int W, float* loss, void* stream);
+int vbg_ce_bwd_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                   const int* n_dev, const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W,
+                   float* dlogits_accum, void* stream);
 /* order-preserving compaction: out_idx = ascending i with (labels[i] == value) == eq; *out_count_dev = how many */
 long long vbg_compact_ws_bytes(long long n);
 int vbg_compact(const int* labels, long long n, int value, int eq, int* out_idx, int* out_count_dev, void* ws,
@@ -659,6 +666,40 @@ int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const 
 typedef struct vbg_decode_rec { int start; int len; double mean; } vbg_decode_rec;      /* 16 bytes */
 int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls, float* score,
                      vbg_decode_rec* best, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * a13b. sampling and hard-example selection on the device  (csrc/sample.hip)
+ *
+ * vbg_sample_select replaces, for up to four label categories of one label array, the reference's `ce_loss[mask]` compaction plus
+ * `random.sample(range(n), k)` (pipeline/custom_loss.py:62-88 CrossEntropyLossRandomSample, :143-163 the `random` pre-sample of
+ * CrossEntropyLossOHEM) without the host knowing n.  Category c = {i : (labels[i] == value_c) == (eq_c != 0)}, n_c elements,
+ * keep_c = min(k_c, n_c).  The key of element i is rng_u64(seed, stream0 + c, i) (vbg_common.h; distinct for distinct i).
+ *   n_c >  k_c : the k_c elements of the category with the smallest keys, written in ascending key order -- a uniformly random ordered
+ *                sample (take_order_c == 0: the same k_c elements; their order is unspecified but a function of the inputs alone);
+ *   n_c <= k_c : every element, in ascending element index.
+ * out_idx[off_c ... off_c + keep_c), off_c = k_0 + ... + k_{c-1}; slots beyond keep_c are not written.  out_keep[c] = keep_c,
+ * out_n[c] = n_c (device memory).  Exact and deterministic for every input: a function of (labels, cats, seed, stream0) alone.  No host
+ * read, three launches.  Integer atomics only where their order cannot show (histogram sums, slot claims of a set that is sorted later).
+ * N < 2^31, 1 <= ncat <= 4, 1 <= k_c <= 4096; ws >= vbg_sample_ws_bytes(N, ncat, ksum) bytes (a function of N and the k's only).
+ * ------------------------------------------------------------------------------------------ */
+#define VBG_SAMPLE_MAX_CATS 4
+#define VBG_SAMPLE_MAX_K 4096
+typedef struct vbg_sample_cat { int value; int eq; int k; int take_order; } vbg_sample_cat;
+typedef struct vbg_sample_cats { vbg_sample_cat c[VBG_SAMPLE_MAX_CATS]; } vbg_sample_cats;
+long long vbg_sample_ws_bytes(long long N, int ncat, long long ksum);
+int vbg_sample_select(const int* labels, long long N, int ncat, vbg_sample_cats cats, unsigned long long seed,
+                      unsigned long long stream0, int* out_idx, int* out_keep, int* out_n, void* ws, long long ws_bytes, void* stream);
+/* vbg_ohem_topk: CrossEntropyLossOHEM's hard-example choice for ncat bounded lists in one launch, one workgroup per list
+ * (pipeline/custom_loss.py:165-190: per-element CE of the category, `torch.sort(descending=True)`, `sorted_loss[sorted_index[:k]]`).
+ * List c is elem[off_c ... off_c + m_c), off_c = cap_0 + ... + cap_{c-1} (vbg_sample_select's layout with k = cap), m_c =
+ * min(m_dev[c], cap_c); its losses are vbg_ce_fwd's, bit for bit.  keep_c = min(m_c, k_c).  keep_c < m_c: si = the list's positions
+ * ordered by (loss descending, position ascending) in the total order of vbg_sort_desc's radix keys (the NaN of an out-of-range label
+ * first; every zero loss is +0); out[off_c + r] = elem[off_c + si[si[r]]] for r < keep_c -- the reference's quirk, literally.
+ * Otherwise the list is copied through.  out_keep[c] = keep_c.  1 <= ncat <= 4, 1 <= cap_c <= 4096, k_c >= 1. */
+typedef struct vbg_ohem_cat { int cap; int k; } vbg_ohem_cat;
+typedef struct vbg_ohem_cats { vbg_ohem_cat c[VBG_SAMPLE_MAX_CATS]; } vbg_ohem_cats;
+int vbg_ohem_topk(const float* logits, long long ld, int ncls, const int* elem, const int* m_dev, int ncat, vbg_ohem_cats cats,
+                  const int* labels, const float* weight, int up_shift, int H, int W, int* out, int* out_keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * a15. optimizers on flat fp32 ranges  (torch.optim.SGD / AdamW; train_SROIE.py:223-235)
@@ -776,6 +817,11 @@ int vbg_segment_rows_add(const float* src, long long lds, const int* perm, const
 int vbg_ce_bwd_rows(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n,
                     const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W, float* grow, int* keys,
                     void* stream);
+/* ... with the count in device memory (vbg_ce_bwd_dyn's deterministic form): slots at and beyond *n_dev are not read, their rows are
+ * zero with key -1 */
+int vbg_ce_bwd_rows_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                        const int* n_dev, const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W,
+                        float* grow, int* keys, void* stream);
 /* RoIAlign backward, one owner per feature row: RoIs added in RoI order (out <= 8, out * W * 4 <= 48 KB) */
 int vbg_roi_align_bwd_det(const float* dy, int B, int H, int W, int C, const int* boxes, const int* box_doc, int nroi, int out,
                           float scale, float* dfeat_accum, void* stream);

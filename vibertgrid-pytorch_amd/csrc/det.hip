@@ -95,14 +95,16 @@ __device__ __forceinline__ long long ce_row_det(long long e, int up_shift, int H
     return (b * (H >> up_shift) + (y >> up_shift)) * (W >> up_shift) + (x >> up_shift);
 }
 __global__ void ce_bwd_rows_kernel(const float* __restrict__ logits, long long ld, int ncls, const int* __restrict__ elem,
-                                   const int* __restrict__ labels, long long n, const float* __restrict__ weight,
-                                   const float* __restrict__ gdev, float gmul, int up_shift, int H, int W, float* __restrict__ grow,
-                                   int* __restrict__ keys) {
+                                   const int* __restrict__ labels, long long n, const int* __restrict__ n_dev,
+                                   const float* __restrict__ weight, const float* __restrict__ gdev, float gmul, int up_shift, int H, int W,
+                                   float* __restrict__ grow, int* __restrict__ keys) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     const float g0 = gmul * (gdev ? gdev[0] : 1.f);
+    // n_dev: the list's count lives on the device (n is its capacity); slots at and beyond it are not read and become skipped rows
+    const long long cnt = n_dev ? (long long)n_dev[0] : n;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const long long e = elem ? elem[i] : i;
-        const int t = labels[e];
+        const long long e = i < cnt ? (elem ? elem[i] : i) : 0;
+        const int t = i < cnt ? labels[e] : -1;
         float* gr = grow + i * ncls;
         if ((unsigned)t >= (unsigned)ncls) {
             keys[i] = -1;
@@ -291,8 +293,19 @@ extern "C" int vbg_ce_bwd_rows(const float* logits, long long ld, int ncls, cons
     VBG_CHECK_ARG(n >= 0 && ncls > 0 && up_shift >= 0);
     if (n == 0) return VBG_OK;
     VBG_CHECK_ARG(logits && labels && grow && keys);
-    VBG_LAUNCH(ce_bwd_rows_kernel, dim3(det_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, weight, gscale_dev, gmul,
-               up_shift, H, W, grow, keys);
+    VBG_LAUNCH(ce_bwd_rows_kernel, dim3(det_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, (const int*)nullptr, weight,
+               gscale_dev, gmul, up_shift, H, W, grow, keys);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_ce_bwd_rows_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                                   const int* n_dev, const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W,
+                                   float* grow, int* keys, void* stream) {
+    VBG_CHECK_ARG(n_cap >= 0 && ncls > 0 && up_shift >= 0 && n_dev);
+    if (n_cap == 0) return VBG_OK;
+    VBG_CHECK_ARG(logits && labels && grow && keys);
+    VBG_LAUNCH(ce_bwd_rows_kernel, dim3(det_grid(n_cap, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n_cap, n_dev, weight,
+               gscale_dev, gmul, up_shift, H, W, grow, keys);
     VBG_LAUNCH_RET();
 }
 

@@ -4,7 +4,8 @@
 // model/semantic_segmentation_head.py:73 is folded into the row index, so the 268 MB/doc
 // upsampled activation never exists), order-preserving category compaction, a STABLE descending
 // radix sort (rocPRIM device primitive, <1 % of the step), gathers and sums.
-// The host-RNG driven index selection (python `random.sample`) stays on the host, as in the reference.
+// The host-RNG driven index selection (python `random.sample`) stays on the host, as in the reference; the opt-in route that draws and
+// selects on the device is csrc/sample.hip, and the *_dyn entries below serve its lists (capacity on the host, count on the device).
 #include "vbg_common.h"
 #include "../../include/vbg.h"
 #include <cstring>
@@ -20,42 +21,26 @@ static inline int ew_grid(long long n, int block) {
     return (int)g;
 }
 
-__device__ __forceinline__ long long ce_row(long long e, int up_shift, int H, int W) {
-    if (H <= 0) return e;
-    const int x = (int)(e % W);
-    const long long t = e / W;
-    const int y = (int)(t % H);
-    const long long b = t / H;
-    return (b * (H >> up_shift) + (y >> up_shift)) * (W >> up_shift) + (x >> up_shift);
-}
-
+// n_dev != nullptr: the element count is read from device memory (the sampled / OHEM lists of csrc/sample.hip: capacity known to the
+// host, count not); the grid is sized by the capacity `n` and nothing at or beyond the count is touched
 __global__ void ce_fwd_kernel(const float* __restrict__ logits, long long ld, int ncls, const int* __restrict__ elem,
-                              const int* __restrict__ labels, long long n, const float* __restrict__ weight, int up_shift,
-                              int H, int W, float* __restrict__ loss) {
+                              const int* __restrict__ labels, long long n, const int* __restrict__ n_dev,
+                              const float* __restrict__ weight, int up_shift, int H, int W, float* __restrict__ loss) {
     const long long stride = (long long)gridDim.x * blockDim.x;
+    if (n_dev) n = min(n, (long long)max(n_dev[0], 0));
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const long long e = elem ? elem[i] : i;
-        const int t = labels[e];
-        // a label outside [0, ncls) (num_classes / tag_to_idx misconfiguration) must not index logits or weights: the loss
-        // becomes NaN -- visible to the caller like torch's device assert -- and backward skips the element
-        if ((unsigned)t >= (unsigned)ncls) { loss[i] = __int_as_float(0x7fc00000); continue; }
-        const float* x = logits + ce_row(e, up_shift, H, W) * ld;
-        float mx = x[0];
-        for (int c = 1; c < ncls; ++c) mx = fmaxf(mx, x[c]);
-        float s = 0.f;
-        for (int c = 0; c < ncls; ++c) s += expf(x[c] - mx);
-        const float lp = (x[t] - mx) - logf(s);
-        // lp <= 0, its zero is +0: `0 - w * lp` makes every zero loss +0.  `-w * lp` gave -0 for a saturated row and +0 for a class of weight
-        // 0; the OHEM selection must tie them as torch's comparison sort does, whether or not the radix sort folds the two zeros together
-        loss[i] = 0.f - (weight ? weight[t] : 1.f) * lp;
+        loss[i] = ce_elem_loss(logits, ld, ncls, e, labels[e], weight, up_shift, H, W);
     }
 }
 
 __global__ void ce_bwd_kernel(const float* __restrict__ logits, long long ld, int ncls, const int* __restrict__ elem,
-                              const int* __restrict__ labels, long long n, const float* __restrict__ weight,
-                              const float* __restrict__ gdev, float gmul, int up_shift, int H, int W, float* dlogits) {
+                              const int* __restrict__ labels, long long n, const int* __restrict__ n_dev,
+                              const float* __restrict__ weight, const float* __restrict__ gdev, float gmul, int up_shift, int H, int W,
+                              float* dlogits) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     const float g0 = gmul * (gdev ? gdev[0] : 1.f);
+    if (n_dev) n = min(n, (long long)max(n_dev[0], 0));
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const long long e = elem ? elem[i] : i;
         const int t = labels[e];
@@ -118,8 +103,18 @@ extern "C" int vbg_ce_fwd(const float* logits, long long ld, int ncls, const int
     VBG_CHECK_ARG(n >= 0 && ncls > 0 && up_shift >= 0);
     if (n == 0) return VBG_OK;
     VBG_CHECK_ARG(logits && labels && loss);
-    VBG_LAUNCH(ce_fwd_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, weight, up_shift,
-                       H, W, loss);
+    VBG_LAUNCH(ce_fwd_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, (const int*)nullptr, weight,
+               up_shift, H, W, loss);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_ce_fwd_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                              const int* n_dev, const float* weight, int up_shift, int H, int W, float* loss, void* stream) {
+    VBG_CHECK_ARG(n_cap >= 0 && ncls > 0 && up_shift >= 0 && n_dev);
+    if (n_cap == 0) return VBG_OK;
+    VBG_CHECK_ARG(logits && labels && loss);
+    VBG_LAUNCH(ce_fwd_kernel, dim3(ew_grid(n_cap, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n_cap, n_dev, weight, up_shift,
+               H, W, loss);
     VBG_LAUNCH_RET();
 }
 
@@ -129,8 +124,19 @@ extern "C" int vbg_ce_bwd(const float* logits, long long ld, int ncls, const int
     VBG_CHECK_ARG(n >= 0 && ncls > 0 && up_shift >= 0);
     if (n == 0) return VBG_OK;
     VBG_CHECK_ARG(logits && labels && dlogits_accum);
-    VBG_LAUNCH(ce_bwd_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, weight,
-                       gscale_dev, gmul, up_shift, H, W, dlogits_accum);
+    VBG_LAUNCH(ce_bwd_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n, (const int*)nullptr, weight,
+               gscale_dev, gmul, up_shift, H, W, dlogits_accum);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_ce_bwd_dyn(const float* logits, long long ld, int ncls, const int* elem, const int* labels, long long n_cap,
+                              const int* n_dev, const float* weight, const float* gscale_dev, float gmul, int up_shift, int H, int W,
+                              float* dlogits_accum, void* stream) {
+    VBG_CHECK_ARG(n_cap >= 0 && ncls > 0 && up_shift >= 0 && n_dev);
+    if (n_cap == 0) return VBG_OK;
+    VBG_CHECK_ARG(logits && labels && dlogits_accum);
+    VBG_LAUNCH(ce_bwd_kernel, dim3(ew_grid(n_cap, 256)), dim3(256), 0, S_, logits, ld, ncls, elem, labels, n_cap, n_dev, weight,
+               gscale_dev, gmul, up_shift, H, W, dlogits_accum);
     VBG_LAUNCH_RET();
 }
 

@@ -65,14 +65,46 @@ __device__ __forceinline__ float row_softmax_norm(const float* __restrict__ p, i
 }
 __device__ __forceinline__ float row_softmax_prob(float v, float mx, float inv) { return expf(v - mx) * inv; }
 
+// ---- per-element cross entropy from (possibly low-resolution) logits: the ONE statement of its arithmetic, shared by ce_fwd_kernel
+// (loss.hip) and ohem_topk_kernel (sample.hip) so that both give the same bits.
+// ce_row: logits row of full-resolution element e (H > 0: [B, H, W] elements over [B, H >> s, W >> s] rows; H <= 0: row e)
+__device__ __forceinline__ long long ce_row(long long e, int up_shift, int H, int W) {
+    if (H <= 0) return e;
+    const int x = (int)(e % W);
+    const long long t = e / W;
+    const int y = (int)(t % H);
+    const long long b = t / H;
+    return (b * (H >> up_shift) + (y >> up_shift)) * (W >> up_shift) + (x >> up_shift);
+}
+__device__ __forceinline__ float ce_elem_loss(const float* __restrict__ logits, long long ld, int ncls, long long e, int t,
+                                              const float* __restrict__ weight, int up_shift, int H, int W) {
+    // a label outside [0, ncls) (num_classes / tag_to_idx misconfiguration) must not index logits or weights: the loss
+    // becomes NaN -- visible to the caller like torch's device assert -- and backward skips the element
+    if ((unsigned)t >= (unsigned)ncls) return __int_as_float(0x7fc00000);
+    const float* x = logits + ce_row(e, up_shift, H, W) * ld;
+    float mx = x[0];
+    for (int c = 1; c < ncls; ++c) mx = fmaxf(mx, x[c]);
+    float s = 0.f;
+    for (int c = 0; c < ncls; ++c) s += expf(x[c] - mx);
+    const float lp = (x[t] - mx) - logf(s);
+    // lp <= 0, its zero is +0: `0 - w * lp` makes every zero loss +0.  `-w * lp` gave -0 for a saturated row and +0 for a class of weight
+    // 0; the OHEM selection must tie them as torch's comparison sort does, whether or not the radix sort folds the two zeros together
+    return 0.f - (weight ? weight[t] : 1.f) * lp;
+}
+
 // ---- counter-based RNG for dropout: one 32-bit draw per (seed, stream, index) ----------
 // (splitmix64-style finaliser; deterministic, so backward regenerates the forward mask)
-__host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t stream, uint64_t idx) {
+// rng_u64: the whole finalised state.  For a fixed (seed, stream) it is injective in idx (idx * odd + const, then bijective steps), so
+// it serves as a tie-free random sort key (csrc/sample.hip); rng_u32 is its bits 16 ... 47
+__host__ __device__ __forceinline__ uint64_t rng_u64(uint64_t seed, uint64_t stream, uint64_t idx) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (stream + 1) + idx * 0xBF58476D1CE4E5B9ull;
     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
     z ^= z >> 27; z *= 0x94D049BB133111EBull;
     z ^= z >> 31;
-    return (uint32_t)(z >> 16);
+    return z;
+}
+__host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t stream, uint64_t idx) {
+    return (uint32_t)(rng_u64(seed, stream, idx) >> 16);
 }
 // keep with probability 1-p: threshold on a 32-bit draw
 __host__ __device__ __forceinline__ bool rng_keep(uint64_t seed, uint64_t stream, uint64_t idx, uint32_t drop_thresh) {

@@ -374,14 +374,19 @@ class ViBERTgridNet(nn.Module):
             pos_neg, cls_map = seg_head.make_labels(packed, classes, B, H, W)
             label_class, label_pn = cls_head.make_labels(segment_classes)
             plans = seg_head.plans(pos_neg, cls_map) + cls_head.plans(label_class, label_pn)
-            pending = PendingCounts(plans)          # counts travel to the host while the trunk below is being enqueued / running
+            # counts travel to the host while the trunk below is being enqueued / running.  Device plans (vbg.ops.set_device_sampling)
+            # have drawn their lists already and need no count on the host: with all four in that form nothing is copied and
+            # nothing is waited for
+            host_plans = [pl for pl in plans if not pl.device]
+            pending = PendingCounts(host_plans) if host_plans else None
         if hs_on:
             ops.reserve_for(hs, *packed, *[t for t in segment_classes if torch.is_tensor(t)])
 
         emb_cat, p_fuse = self._features(batch, packed, B, H, W, seg_indices, corpus, mask)
         labels_ready = None
         with (torch.cuda.stream(hs) if hs_on else contextlib.nullcontext()):
-            pending.finish()
+            if pending is not None:
+                pending.finish()
             if hs_on:
                 labels_ready = torch.cuda.Event()
                 labels_ready.record(hs)
@@ -399,8 +404,7 @@ class ViBERTgridNet(nn.Module):
                 loss_c, gt_label, pred_label = cls_head(fuse, segment_classes, prepared=(label_class, label_pn, plans[2:]))
             ops.reserve_for(hs, p_fuse, emb_cat)
             main.wait_event(labels_ready)   # (the label work only -- not the RoI branch enqueued behind it)
-            seg_t = [pos_neg, cls_map] + [t for pl in plans[:2] for t in [pl.labels] + [x for c in pl.cats for x in (c.idx, c.cnt_dev, getattr(c, "elem", None))]]
-            ops.reserve_for(main, *[t for t in seg_t if torch.is_tensor(t)])
+            ops.reserve_for(main, pos_neg, cls_map, *[t for pl in plans[:2] for t in pl.tensors()])
             loss_aux, pred_mask, pred_ss = seg_head(p_fuse, segment_classes, icoors, prepared=(pos_neg, cls_map, plans[:2]),
                                                     materialize=not train_only)
             main.wait_stream(hs)
@@ -408,8 +412,8 @@ class ViBERTgridNet(nn.Module):
         else:
             if hs_on:                       # (labels on the heads' stream, but no joining node in this graph: everything else on one stream)
                 main.wait_stream(hs)
-                every = [pos_neg, cls_map, label_class, label_pn] + [t for pl in plans for t in [pl.labels] + [x for c in pl.cats for x in (c.idx, c.cnt_dev, getattr(c, "elem", None))]]
-                ops.reserve_for(main, *[t for t in every if torch.is_tensor(t)])
+                ops.reserve_for(main, *[t for t in (pos_neg, cls_map, label_class, label_pn) if torch.is_tensor(t)],
+                                *[t for pl in plans for t in pl.tensors()])
             loss_aux, pred_mask, pred_ss = seg_head(p_fuse, segment_classes, icoors, prepared=(pos_neg, cls_map, plans[:2]),
                                                     materialize=not train_only)
             roi = self.grid_roi_align_net(p_fuse, icoors, None, packed=packed)

@@ -111,6 +111,9 @@ class SemanticSegmentationClassifier(nn.Module):
         self.num_classes = num_classes
         self.ss_encoder = SemanticSegmentationEncoder(p_fuse_channel, num_classes)
         self.aux_loss_1 = CrossEntropyLossRandomSample(sample_list=loss_1_sample_list)
+        # the two-stage heads read prediction-dependent sizes on the host anyway and draw in the reference's order: device sampling
+        # (vbg.ops.set_device_sampling) has no effect on classifier_mode "full" / "crf"
+        self.aux_loss_1.allow_device = False
         for idx in range(num_classes - 1):
             self.add_module(f"ss_binary_classifier_{idx}", SemanticSegmentationBinaryClassifier(in_channels=num_classes))
             self.add_module(f"aux_loss_2_{idx}", BCELossOHEM(num_hard_positive=num_hard_positive, num_hard_negative=num_hard_negative,

@@ -16,6 +16,13 @@ reference.
 
 A "plan" holds everything that depends on LABELS only (category compactions, counts, host random
 draws).  Plans for several losses are resolved with ONE device->host copy (`resolve_plans`).
+
+Device plans (opt-in: `VBG_DEVICE_SAMPLING=1` / `vbg.ops.set_device_sampling(True)`).  Where every list a loss builds is bounded
+by a number the host knows -- k for a sampled category, 2k for an OHEM category with the random pre-sample -- the plan is a
+DEVICE plan: one `ops.sample_select` call per label array draws the lists, their counts stay in device memory, and the loss runs
+over capacity-sized lists with device counts and device denominators.  No count travels to the host (`count_tensors()` is empty),
+`random.sample` is not called: the draws come from the counter-based hash of csrc/vbg_common.h keyed by `ops.next_sample_seed()`,
+NOT from python's `random` -- a pinned `random.seed` does not select the reference's elements on this route.
 """
 import random
 from typing import List, Optional, Sequence
@@ -31,12 +38,27 @@ class _Cat:
     __slots__ = ("idx", "cnt_dev", "n", "elem")
 
 
-class RandomSamplePlan:
-    """label-only part of CrossEntropyLossRandomSample."""
+def _device_ks_ok(ks) -> bool:
+    return 1 <= len(ks) <= ops.SAMPLE_MAX_CATS and all(1 <= int(k) <= ops.SAMPLE_MAX_K for k in ks)
 
-    def __init__(self, labels_i32: torch.Tensor, ncls_logits: int, sample_list: Optional[Sequence[int]]):
+
+def _plan_tensors(plan):
+    """every tensor a plan holds (the model reserves them for the stream that reads them): a device plan's tensor attributes, a host
+    plan's labels and per-category tensors"""
+    ts = [v for v in vars(plan).values() if torch.is_tensor(v)]
+    for c in plan.cats:
+        ts += [x for x in (c.idx, c.cnt_dev, getattr(c, "elem", None)) if torch.is_tensor(x)]
+    return ts
+
+
+class RandomSamplePlan:
+    """label-only part of CrossEntropyLossRandomSample.  `device=True` asks for the device form (taken when the list is bounded:
+    `sample_list` given, at most 4 categories, 1 <= k <= 4096)."""
+
+    def __init__(self, labels_i32: torch.Tensor, ncls_logits: int, sample_list: Optional[Sequence[int]], device: bool = False):
         self.labels = labels_i32
         self.cats: List[_Cat] = []
+        self.device = False
         self.plain = sample_list is None          # reference :36-44: plain (weighted) mean CE over every element
         self.num_keep_total = 0
         if self.plain:
@@ -49,6 +71,13 @@ class RandomSamplePlan:
         else:
             assert ncat == ncls_logits, f"shape mismatch, number of elements in sample_list must be 2 or equals dimensions of input, {ncat} and {ncls_logits} given"
             spec = [(c, True) for c in range(ncat)]
+        if device and labels_i32.is_cuda and _device_ks_ok(self.sample_list):
+            # the whole label-only work in one call; the order inside a sampled list is free (the loss is a sum)
+            self.device = True
+            self.idx, self.keep, self.n = ops.sample_select(labels_i32, [(v, eq, k, 0) for (v, eq), k in zip(spec, self.sample_list)],
+                                                            ops.next_sample_seed())
+            self.keep_total = self.keep.sum()
+            return
         for value, eq in spec:
             c = _Cat()
             c.idx, c.cnt_dev = ops.compact(labels_i32, value, eq)
@@ -57,11 +86,22 @@ class RandomSamplePlan:
     def count_tensors(self):
         return [c.cnt_dev for c in self.cats]
 
+    def tensors(self):
+        return _plan_tensors(self)
+
+    def lists(self):
+        """device form: [(elements int32 [k] -- the first `keep` are the list --, keep int32 [1])] per category"""
+        o, out = 0, []
+        for j, k in enumerate(self.sample_list):
+            out.append((self.idx[o:o + k], self.keep[j:j + 1]))
+            o += k
+        return out
+
     def draw(self, counts: Sequence[int]):
         """host half of the selection: the random draws in the reference's order -> [(category, positions or None)]"""
         self.num_keep_total = 0
         out = []
-        if self.plain:
+        if self.plain or self.device:
             return out
         for c, n, k in zip(self.cats, counts, self.sample_list):
             c.n = int(n)
@@ -78,21 +118,50 @@ class OhemPlan:
     """label-only part of CrossEntropyLossOHEM (positives = label != 0).  `keyed`: labels are 1 (positive) / 0 (negative) /
     anything else = not part of the loss (BCE-OHEM over a predicted-positive subset, semantic_segmentation_head.py:216-226)."""
 
-    def __init__(self, labels_i32: torch.Tensor, num_pos: int, num_neg: int, rand: bool, keyed: bool = False):
+    def __init__(self, labels_i32: torch.Tensor, num_pos: int, num_neg: int, rand: bool, keyed: bool = False, device: bool = False):
         self.labels, self.num_pos, self.num_neg, self.rand = labels_i32, num_pos, num_neg, rand
         self.plain = (num_pos == -1 and num_neg == -1)
         self.cats: List[_Cat] = []
+        self.device = self.bounded = False
         if not self.plain:
-            for value, eq in (((1, True), (0, True)) if keyed else ((0, False), (0, True))):          # positives first, like the reference
+            spec = ((1, True), (0, True)) if keyed else ((0, False), (0, True))          # positives first, like the reference
+            if device and rand and labels_i32.is_cuda and num_pos >= 1 and num_neg >= 1 and _device_ks_ok([2 * num_pos, 2 * num_neg]):
+                # the random pre-sample of 2k per category (everything, in compaction order, when the category has no more): the
+                # order of these lists matters -- the OHEM quirk indexes positions
+                self.device = self.bounded = True
+                self.caps = [2 * num_pos, 2 * num_neg]
+                self.idx, self.keep, self.n = ops.sample_select(labels_i32, [(v, eq, cap, 1) for (v, eq), cap in zip(spec, self.caps)],
+                                                                ops.next_sample_seed())
+                return
+            # without the pre-sample the sort runs over the whole category: the compactions below are all the label-only work, and
+            # their counts stay on the device (the loss sorts at the capacity, see CrossEntropyLossOHEM.forward)
+            self.device, self.bounded = bool(device and not rand and labels_i32.is_cuda and num_pos >= 1 and num_neg >= 1), False
+            for value, eq in spec:
                 c = _Cat()
                 c.idx, c.cnt_dev = ops.compact(labels_i32, value, eq)
                 self.cats.append(c)
 
     def count_tensors(self):
-        return [c.cnt_dev for c in self.cats]
+        return [] if self.device else [c.cnt_dev for c in self.cats]
+
+    def tensors(self):
+        return _plan_tensors(self)
+
+    def lists(self):
+        """device form: [(candidate elements int32 -- the pre-sample of 2k, or the whole category --, count int32 [1])] for positives,
+        negatives; after the loss ran `chosen` holds the same for the hard examples it kept"""
+        if not self.bounded:
+            return [(c.idx, c.cnt_dev) for c in self.cats]
+        o, out = 0, []
+        for j, cap in enumerate(self.caps):
+            out.append((self.idx[o:o + cap], self.keep[j:j + 1]))
+            o += cap
+        return out
 
     def draw(self, counts: Sequence[int]):
         out = []
+        if self.device:
+            return out
         for c, n, k in zip(self.cats, counts, (self.num_pos, self.num_neg)):
             c.n = int(n)
             out.append((c, random.sample(range(c.n), 2 * k) if self.rand and 2 * k < c.n else None))
@@ -150,8 +219,10 @@ class PendingCounts:
 
 
 def resolve_plans(plans):
-    """One D2H copy for the category counts of all plans, then the host-side random draws in order."""
-    PendingCounts(plans).finish()
+    """One D2H copy for the category counts of all plans, then the host-side random draws in order (device plans need neither)."""
+    plans = [p for p in plans if not p.device]
+    if plans:
+        PendingCounts(plans).finish()
 
 
 def plain_mean_ce(logits2d: torch.Tensor, labels_i32: torch.Tensor, weight: Optional[torch.Tensor], up_shift: int, H: int,
@@ -175,9 +246,10 @@ class CrossEntropyLossRandomSample(torch.nn.Module):
         if sample_list is not None:
             assert len(sample_list) >= 2, f"sample list must contains at least two elements, {len(sample_list)} given"
         self.register_buffer("weight", weight)
+        self.allow_device = True          # (False in the two-stage segmentation head: classifier_mode "full" / "crf" keep the host route)
 
     def plan(self, labels_i32, ncls_logits):
-        return RandomSamplePlan(labels_i32, ncls_logits, self.sample_list)
+        return RandomSamplePlan(labels_i32, ncls_logits, self.sample_list, device=self.allow_device and ops.device_sampling_enabled())
 
     def forward(self, logits2d: torch.Tensor, labels_i32: torch.Tensor, plan: RandomSamplePlan = None, up_shift: int = 0,
                 H: int = 0, W: int = 0) -> torch.Tensor:
@@ -187,6 +259,14 @@ class CrossEntropyLossRandomSample(torch.nn.Module):
             resolve_plans([plan])
         if plan.plain:
             return plain_mean_ce(logits2d, labels_i32, self.weight, up_shift, H, W)
+        if plan.device:
+            # one node per category over its capacity-sized list; the denominator is the device's sum of the keeps (0 / 0 = NaN with
+            # nothing kept, as on the host route)
+            total = None
+            for elem, keep in plan.lists():
+                t = Fn.SelectedCEDynFn.apply(logits2d, elem, keep, labels_i32, self.weight, None, up_shift, H, W)
+                total = t if total is None else total + t
+            return total.double().reshape(1) / plan.keep_total
         # (round 6: ONE selected-CE node over the categories' concatenated element lists instead of one per category -- the same sum, the
         #  same per-element gradient scale, a third of the small launches in the forward's tail and the backward's head)
         elems = [c.elem for c in plan.cats if c.elem.numel()]
@@ -204,9 +284,11 @@ class CrossEntropyLossOHEM(torch.nn.Module):
         assert reduction == "mean", "only the reduction the model uses is implemented"
         self.num_hard_positive, self.num_hard_negative, self.random = num_hard_positive, num_hard_negative, random
         self.register_buffer("weight", weight)
+        self.allow_device = True          # (BCELossOHEM: False -- the binary losses keep the host route)
 
     def plan(self, labels_i32, keyed: bool = False):
-        return OhemPlan(labels_i32, self.num_hard_positive, self.num_hard_negative, self.random, keyed)
+        return OhemPlan(labels_i32, self.num_hard_positive, self.num_hard_negative, self.random, keyed,
+                        device=self.allow_device and ops.device_sampling_enabled())
 
     def forward(self, logits2d: torch.Tensor, labels_i32: torch.Tensor, plan: OhemPlan = None, up_shift: int = 0, H: int = 0,
                 W: int = 0) -> torch.Tensor:
@@ -215,6 +297,34 @@ class CrossEntropyLossOHEM(torch.nn.Module):
             resolve_plans([plan])
         if plan.plain:
             return plain_mean_ce(logits2d, labels_i32, self.weight, up_shift, H, W)
+        if plan.device:
+            ks = (self.num_hard_positive, self.num_hard_negative)
+            plan.chosen = []
+            if plan.bounded:
+                sel, sel_keep = ops.ohem_topk(logits2d.detach(), plan.idx, plan.keep, plan.caps, ks, labels_i32, self.weight, up_shift, H, W)
+                o = 0
+                for j, cap in enumerate(plan.caps):
+                    plan.chosen.append((sel[o:o + cap], sel_keep[j:j + 1]))
+                    o += cap
+            else:
+                # today's route at the category's CAPACITY: losses of the first cnt members, -inf behind them (it sorts last), one
+                # stable descending sort, the two gathers; which of the two answers holds -- the double indexing, or the whole
+                # category when it has at most k members -- is chosen on the device
+                for c, k in zip(plan.cats, ks):
+                    cap = int(c.idx.numel())
+                    v = torch.full((cap,), float("-inf"), device=logits2d.device, dtype=torch.float32)
+                    ops.ce_fwd_dyn(logits2d.detach(), c.idx, labels_i32, c.cnt_dev, self.weight, up_shift, H, W, out=v)
+                    _, si = ops.sort_desc(v)
+                    kk = min(k, cap)
+                    hard = ops.gather_i32(c.idx, ops.gather_i32(si, si[:kk].contiguous()))
+                    plan.chosen.append((torch.where(c.cnt_dev > k, hard, c.idx[:kk]), c.cnt_dev.clamp(max=k)))
+            denom = sum(keep for _, keep in plan.chosen).reshape(())
+            inv = (1.0 / denom.clamp(min=1).to(torch.float32)).reshape(1)
+            loss = None
+            for elem, keep in plan.chosen:
+                t = Fn.SelectedCEDynFn.apply(logits2d, elem.contiguous(), keep, labels_i32, self.weight, inv, up_shift, H, W)
+                loss = t if loss is None else loss + t
+            return torch.where(denom > 0, loss, logits2d.sum() * 0.0)          # nothing kept: the host route's `logits.sum() * 0.0`
         elems, keeps = [], []
         for c, k in zip(plan.cats, (self.num_hard_positive, self.num_hard_negative)):
             m = int(c.elem.numel())
@@ -289,6 +399,7 @@ class BCELossOHEM(torch.nn.Module):
         if weight is not None:
             raise NotImplementedError(_BCE_WEIGHT_MSG)
         self.ce = CrossEntropyLossOHEM(num_hard_positive, num_hard_negative, None, reduction, random)
+        self.ce.allow_device = False          # prediction-dependent sizes are read on the host here anyway
 
     def forward(self, input: torch.Tensor, target: torch.Tensor = None, keyed_labels: torch.Tensor = None, up_shift: int = 0,
                 H: int = 0, W: int = 0) -> torch.Tensor:

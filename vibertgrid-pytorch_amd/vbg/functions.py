@@ -1196,6 +1196,32 @@ class SelectedCEFn(torch.autograd.Function):
         return dl, None, None, None, None, None, None, None
 
 
+class SelectedCEDynFn(torch.autograd.Function):
+    """SelectedCEFn over the first `count` elements of a capacity-sized list: `count` is an int32 device tensor (a list of
+    ops.sample_select / ops.ohem_topk), nothing at or beyond it is read.  `gscale` (optional, fp32 [1] device tensor, no gradient)
+    multiplies the result -- the 1 / keep of a denominator that only the device knows.  Returns a 0-dim fp32 tensor."""
+
+    @staticmethod
+    def forward(ctx, logits2d, elem, count, labels, weight, gscale, up_shift, H, W):
+        loss = ops.ce_fwd_dyn(logits2d, elem, labels, count, weight, up_shift, H, W)      # zeros beyond the count
+        out = torch.zeros((1,), device=logits2d.device, dtype=f32)
+        ops.sum_f32(loss, out)
+        ctx.cfg = (up_shift, H, W)
+        ctx.save_for_backward(logits2d, elem, count, labels, weight, gscale)
+        return (out if gscale is None else out * gscale).view(())
+
+    @staticmethod
+    def backward(ctx, dout):
+        logits2d, elem, count, labels, weight, gscale = ctx.saved_tensors
+        up_shift, H, W = ctx.cfg
+        dl = torch.zeros_like(logits2d)
+        g = _c(dout).to(f32).view(1)
+        if gscale is not None:
+            g = g * gscale
+        ops.ce_bwd_dyn(logits2d, elem, labels, count, weight, g, 1.0, up_shift, H, W, dl)
+        return dl, None, None, None, None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------------------------
 # The arithmetic form (amp latch, split / fp32 precision) a Function's FORWARD ran with is the one its BACKWARD runs with:
 # both are recorded on ctx and re-established around backward, so an eval / inference forward of this or another model between

@@ -118,9 +118,26 @@ class AdamGroupOpt(C.Structure):             # include/vbg.h vbg_adam_group_opt
     _fields_ = [("lr", c_f), ("b1", c_f), ("b2", c_f), ("eps", c_f), ("wd", c_f), ("step", c_int), ("flags", c_int)]
 
 
+class SampleCat(C.Structure):                # include/vbg.h vbg_sample_cat
+    _fields_ = [("value", c_int), ("eq", c_int), ("k", c_int), ("take_order", c_int)]
+
+
+class SampleCats(C.Structure):               # include/vbg.h vbg_sample_cats (passed by value)
+    _fields_ = [("c", SampleCat * 4)]
+
+
+class OhemCat(C.Structure):                  # include/vbg.h vbg_ohem_cat
+    _fields_ = [("cap", c_int), ("k", c_int)]
+
+
+class OhemCats(C.Structure):                 # include/vbg.h vbg_ohem_cats (passed by value)
+    _fields_ = [("c", OhemCat * 4)]
+
+
 SGD_NESTEROV, SGD_MAXIMIZE, SGD_FIRST = 1, 2, 4          # vbg_sgd_group_opt.flags
 ADAM_AMSGRAD, ADAM_MAXIMIZE, ADAM_COUPLED = 1, 2, 4      # vbg_adam_group_opt.flags
 OPTIM_MAX_GROUPS = 32                        # include/vbg.h VBG_OPTIM_MAX_GROUPS
+SAMPLE_MAX_CATS, SAMPLE_MAX_K = 4, 4096                 # include/vbg.h VBG_SAMPLE_MAX_CATS / VBG_SAMPLE_MAX_K
 ATTN_FWD, ATTN_DQ, ATTN_DKV = 0, 1, 2
 OP_DENSE_K, OP_DENSE_R, OP_CONV_K, OP_CONV_R, OP_WT_R = 0, 1, 2, 3, 4
 EPI_NONE, EPI_RELU, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD = 0, 1, 2, 3
@@ -209,6 +226,11 @@ SIGNATURES = {
     "vbg_roi_align_hw_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_ce_fwd": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     "vbg_ce_bwd": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp]),
+    "vbg_ce_fwd_dyn": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "vbg_ce_bwd_dyn": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp]),
+    "vbg_sample_ws_bytes": (c_ll, [c_ll, c_int, c_ll]),
+    "vbg_sample_select": (c_int, [c_vp, c_ll, c_int, SampleCats, c_ull, c_ull, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]),
+    "vbg_ohem_topk": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_int, OhemCats, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "vbg_compact_ws_bytes": (c_ll, [c_ll]),
     "vbg_compact": (c_int, [c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_vp]),
     "vbg_sort_ws_bytes": (c_ll, [c_ll]),
@@ -245,6 +267,7 @@ SIGNATURES = {
     "vbg_sort_i32": (c_int, [c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp]),
     "vbg_segment_rows_add": (c_int, [c_vp, c_ll, c_vp, c_vp, c_ll, c_int, c_vp, c_ll, c_vp]),
     "vbg_ce_bwd_rows": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "vbg_ce_bwd_rows_dyn": (c_int, [c_vp, c_ll, c_int, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_f, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "vbg_roi_align_bwd_det": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_roi_align_hw_bwd_det": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp]),
     "vbg_bn_det_ws_rows": (c_int, [c_ll, c_int]),

@@ -8,7 +8,7 @@ import os
 import torch
 
 from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AdamGroupOpt, AdamwGroup, AttnDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
+                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -2170,6 +2170,99 @@ def ce_bwd(logits2d, elem, labels, n, weight, gscale_dev, gmul, up_shift, H, W, 
     _seen("fatomic:ce_bwd")
     check(lib.vbg_ce_bwd(P(logits2d), logits2d.stride(0), logits2d.shape[1], P(elem), P(labels), n, P(weight), P(gscale_dev), float(gmul), up_shift,
                          H, W, P(dlogits), _stream()), "vbg_ce_bwd")
+
+
+def ce_fwd_dyn(logits2d, elem, labels, n_dev, weight=None, up_shift=0, H=0, W=0, out=None):
+    """losses of the first n_dev[0] elements of the list `elem` (its length is the capacity); slots beyond the count keep what `out`
+    held (zeros when it is allocated here)"""
+    cap = int(elem.numel())
+    loss = torch.zeros((cap,), device=logits2d.device, dtype=f32) if out is None else out
+    assert n_dev.dtype == i32 and elem.dtype == i32
+    check(lib.vbg_ce_fwd_dyn(P(logits2d), logits2d.stride(0), logits2d.shape[1], P(elem), P(labels), cap, P(n_dev), P(weight), up_shift, H, W,
+                             P(loss), _stream()), "vbg_ce_fwd_dyn")
+    return loss
+
+
+def ce_bwd_dyn(logits2d, elem, labels, n_dev, weight, gscale_dev, gmul, up_shift, H, W, dlogits):
+    cap = int(elem.numel())
+    assert n_dev.dtype == i32 and elem.dtype == i32
+    if _DET[0]:
+        # as ce_bwd: gradient rows (zero, key -1 beyond the count), added in sorted row order
+        ncls = logits2d.shape[1]
+        grow = torch.empty((max(cap, 1), ncls), device=logits2d.device, dtype=f32)
+        keys = torch.empty((max(cap, 1),), device=logits2d.device, dtype=i32)
+        check(lib.vbg_ce_bwd_rows_dyn(P(logits2d), logits2d.stride(0), ncls, P(elem), P(labels), cap, P(n_dev), P(weight), P(gscale_dev),
+                                      float(gmul), up_shift, H, W, P(grow), P(keys), _stream()), "vbg_ce_bwd_rows_dyn")
+        rows_add_sorted(grow[:cap], keys[:cap], dlogits, ldd=logits2d.stride(0))
+        _seen("det:ce_bwd")
+        return
+    _seen("fatomic:ce_bwd")
+    check(lib.vbg_ce_bwd_dyn(P(logits2d), logits2d.stride(0), logits2d.shape[1], P(elem), P(labels), cap, P(n_dev), P(weight), P(gscale_dev),
+                             float(gmul), up_shift, H, W, P(dlogits), _stream()), "vbg_ce_bwd_dyn")
+
+
+# ---- sampling on the device (csrc/sample.hip): no category size ever reaches the host -------------------------------------------------
+_DEVICE_SAMPLING = [os.environ.get("VBG_DEVICE_SAMPLING", "0") not in ("", "0")]
+_SAMPLE_COUNTER = [0]
+SAMPLE_STREAM0 = 0x10000          # stream ids 0x10000 + category index: disjoint from dropout's (layer * 8 + {0, 1, 2}, and 1000)
+
+
+def set_device_sampling(on: bool):
+    """the sampled / OHEM cross-entropy losses of classifier_mode "simp" draw and select on the device (pipeline/custom_loss.py device
+    plans): no device->host copy, no host wait in the training forward.  Off by default: the host route is the one whose draws follow
+    the reference's `random.seed`."""
+    _DEVICE_SAMPLING[0] = bool(on)
+
+
+def device_sampling_enabled() -> bool:
+    return _DEVICE_SAMPLING[0]
+
+
+def reset_sample_counter(n: int = 0):
+    """(tests, resumed runs) the next plan takes the seed of call number n; the counter is not part of any checkpoint"""
+    _SAMPLE_COUNTER[0] = int(n)
+
+
+def next_sample_seed() -> int:
+    """one seed per device plan -- the dropout rule of model/BERTgrid_generator.py (_step_seed): counter * 0x9E3779B1 + the low word of
+    torch.initial_seed() + rank * 0x85EBCA6B"""
+    rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+    seed = _SAMPLE_COUNTER[0] * 0x9E3779B1 + (torch.initial_seed() & 0xFFFFFFFF) + rank * 0x85EBCA6B
+    _SAMPLE_COUNTER[0] += 1
+    return seed
+
+
+def sample_select(labels, cats, seed, stream0=SAMPLE_STREAM0, ws=None):
+    """cats: [(value, eq, k, take_order)], at most 4 -> (out_idx int32 [sum k], out_keep int32 [ncat], out_n int32 [ncat]); category c
+    owns out_idx[off_c : off_c + k_c], off_c the prefix of the k's, of which the first out_keep[c] are defined (include/vbg.h a13b)"""
+    assert labels.dtype == i32 and labels.is_contiguous()
+    N, ncat = labels.numel(), len(cats)
+    sc = SampleCats()
+    for j, (value, eq, k, order) in enumerate(cats[:SAMPLE_MAX_CATS]):
+        sc.c[j].value, sc.c[j].eq, sc.c[j].k, sc.c[j].take_order = int(value), int(bool(eq)), int(k), int(bool(order))
+    ksum = sum(int(c[2]) for c in cats)
+    out_idx = torch.empty((max(ksum, 1),), device=labels.device, dtype=i32)
+    meta = torch.empty((2, max(ncat, 1)), device=labels.device, dtype=i32)
+    if ws is None:
+        wsb = int(lib.vbg_sample_ws_bytes(N, ncat, ksum))
+        ws = torch.empty((max(wsb, 0),), device=labels.device, dtype=torch.uint8)
+    check(lib.vbg_sample_select(P(labels), N, ncat, sc, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream0), P(out_idx), P(meta[0]), P(meta[1]),
+                                P(ws), ws.numel(), _stream()), "vbg_sample_select")
+    return out_idx[:ksum], meta[0, :ncat], meta[1, :ncat]
+
+
+def ohem_topk(logits2d, elem, m_dev, caps, ks, labels, weight=None, up_shift=0, H=0, W=0):
+    """lists c = elem[off_c : off_c + m_dev[c]] (off_c the prefix of caps) -> (out int32 like elem, out_keep int32 [ncat]); include/vbg.h"""
+    ncat = len(caps)
+    assert elem.dtype == i32 and m_dev.dtype == i32 and m_dev.numel() >= ncat and elem.numel() >= sum(caps) and len(ks) == ncat
+    oc = OhemCats()
+    for j, (cap, k) in enumerate(list(zip(caps, ks))[:SAMPLE_MAX_CATS]):
+        oc.c[j].cap, oc.c[j].k = int(cap), int(k)
+    out = torch.empty_like(elem)
+    out_keep = torch.empty((max(ncat, 1),), device=elem.device, dtype=i32)
+    check(lib.vbg_ohem_topk(P(logits2d), logits2d.stride(0), logits2d.shape[1], P(elem), P(m_dev), ncat, oc, P(labels), P(weight), up_shift, H, W,
+                            P(out), P(out_keep), _stream()), "vbg_ohem_topk")
+    return out, out_keep[:ncat]
 
 
 def compact(labels, value, eq):

@@ -475,6 +475,57 @@ typedef struct vbg_bert_layer_fwd_desc {
 } vbg_bert_layer_fwd_desc;
 int vbg_bert_layer_fwd(const vbg_bert_layer_fwd_desc* desc, void* stream);
 
+/* The backward of that layer in ONE call (csrc/encoder.hip): the all-pair backward (every product on fp16-pair planes, forms 1 / 2) on
+ * the bound route -- hidden % 256 == 0, the Q/K/V weights, biases and their gradients stacked back to back, every parameter gradient
+ * accumulated straight into its destination.  Replaces the autograd of one transformers BertLayer (model/BERTgrid_generator.py:134) = the
+ * ten launches
+ *   vbg_dropout_add_ln_bwd_pair (LayerNorm 2: dy -> qdfo, dx1, dg2 / db2, dbo2) ->
+ *   vbg_plane_gemm (qdfo Wo2^T o gelu'(h) -> qdh by the bound cq_mul_dh, column sums -> dbi) -> vbg_plane_gemm (dx1 += qdh Wi^T) ->
+ *   vbg_dropout_add_ln_bwd_pair (LayerNorm 1: dx1 -> qdao, dx, dg1 / db1, dbo) -> vbg_plane_gemm (qdao Wo^T -> pdctx by the bound cq_mul_dctx) ->
+ *   vbg_attn (DQ) -> vbg_attn (DKV) -> vbg_split_planes_pair (dqkv -> qdqkv, column sums -> dbqkv) -> vbg_plane_gemm (dx += qdqkv Wqkv^T) ->
+ *   grouped TN vbg_plane_gemm (dwo2 += qdfo^T qg, dwi += qdh^T qx1, dwo += qdao^T qctx, dwqkv += qdqkv^T qx)
+ * with exactly the descriptors the caller would have passed one by one (bit-identical results); what it saves is host time per launch.
+ *   form: of the products (1, or 2 inside an autocast region); form_attn: of the two attention passes (1 or 2).
+ *   Every vbg_planes_ref is fp16-pair planes [2][rows][ld].  w*_t: planes of the TRANSPOSED weights (wqkv_t [hidden][3 hidden], wo_t
+ *   [hidden][hidden], wi_t [hidden][inter], wo2_t [inter][hidden]); l1_wo2 / l1_wo: their vbg_col_l1_max words.
+ *   s_dy: the amax slot of dy (input).  The nine slots behind it are zeroed by the caller and distinct: s_dfo / s_dao receive max |dfo| /
+ *   max |dao|, s_dfo_ref / s_dao_ref / s_dh / s_dctx the bounds their planes were scaled with, s_dx1 / s_dqkv / s_dx the maxima of those tensors.
+ *   ln_ws: fp32 [vbg_ln_bwd_ws_rows(ntok)][3][hidden].  delta: fp32 [heads][ntok_pad], zero in the padding rows (vbg_attn).
+ *   deterministic != 0: no float atomics -- the column sums of launch 2 are taken from its stored fp32 output det_scratch
+ *   [ntok][roundup(inter, 4)] by vbg_colsum_det behind the product, those of dqkv by vbg_colsum_det in front of the split; det_ws:
+ *   max(vbg_colsum_det_ws_elems(ntok, inter), vbg_colsum_det_ws_elems(ntok, 3 hidden)) doubles; the flag without both is an argument error.
+ *   Dropout streams: stream_id0 + 2 (LayerNorm 2), + 1 (LayerNorm 1); attention keeps from mask_q / mask_k (NULL = none).
+ *   Gradient destinations are accumulated into (+=); dx1, dqkv and the five q* / pdctx plane tensors are caller scratch that is written. */
+typedef struct vbg_bert_layer_bwd_desc {
+    int ntok, hidden, inter, heads;
+    float drop_p; unsigned long long seed, stream_id0;
+    int form, form_attn, deterministic;
+    int tile_dh, tile_dx1, tile_dctx, tile_dx, tile_wgrad;   /* launches 2, 3, 5, 9, 10 */
+    float cq_mul_dh, cq_mul_dctx;                            /* vbg_plane_gemm_desc.cq_mul of launches 2 and 5 */
+    /* packed sequences: the fields of vbg_attn_desc */
+    int ntasks, max_len; const int* tasks; const int* seq_len; const int* seq_row0; const int* pad_off; long long ntok_pad;
+    const unsigned* mask_q; const unsigned* mask_k; const long long* mask_off; float attn_scale, keep_scale;
+    /* inputs: the output gradient, what the forward saved, the weights */
+    const float* dy; const unsigned* s_dy;
+    const float* xhat2; const float* rstd2; const float* g2; const float* xhat1; const float* rstd1; const float* g1;
+    const float* h; const float* ctx; float* kbar; float* lse;
+    vbg_planes_ref pqkv, qx, qctx, qx1, qg;                  /* planes of q / k / v, x, the attention output, x1, gelu(h) */
+    vbg_planes_ref wqkv_t, wo_t, wi_t, wo2_t;
+    const unsigned* l1_wo2; const unsigned* l1_wo;
+    /* amax slots (zero on entry) */
+    unsigned* s_dfo; unsigned* s_dfo_ref; unsigned* s_dh; unsigned* s_dx1; unsigned* s_dao; unsigned* s_dao_ref; unsigned* s_dctx;
+    unsigned* s_dqkv; unsigned* s_dx;
+    /* workspaces and intermediates */
+    float* ln_ws; float* delta; float* det_scratch; double* det_ws;
+    vbg_planes_ref qdfo, qdh, qdao, pdctx, qdqkv;
+    float* dx1; float* dqkv;                                 /* [ntok][hidden], [ntok][3 hidden] */
+    /* gradients: dx [ntok][hidden] is written, the rest accumulated into */
+    float* dx;
+    float* dg2; float* db2; float* dbo2; float* dbi; float* dg1; float* db1; float* dbo; float* dbqkv;
+    float* dwo2; float* dwi; float* dwo; float* dwqkv;       /* [hidden][inter], [inter][hidden], [hidden][hidden], [3 hidden][hidden] */
+} vbg_bert_layer_bwd_desc;
+int vbg_bert_layer_bwd(const vbg_bert_layer_bwd_desc* desc, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * a4. token -> segment aggregation  (model/BERTgrid_generator.py:148-191)
  * ------------------------------------------------------------------------------------------ */

@@ -677,6 +677,7 @@ class _LayerRoute(NamedTuple):
     ao_pair: bool       # the attention-output projection runs the pair form (autocast region, all-pair path)
     keep3: bool         # the bf16 planes of x1 / gelu(h) / y are written: operands of the six-product backward
     entry: bool         # the forward leaves from ONE library call (ops.bert_layer_fwd), else ops.bert_layer_launches
+    entry_bwd: bool     # ... and the all-pair backward on the bound route (ops.bert_layer_bwd), else ops.bert_layer_bwd_launches
     grad: bool
 
     @property
@@ -684,10 +685,10 @@ class _LayerRoute(NamedTuple):
         return ("pair" if self.pair_bwd else "fused" if self.flash else "unfused") if self.planes else "dense"
 
 
-def _layer_route(hid, inter, dh, maxlen, ntok, grad, qkv_fused, sunk, carrier) -> _LayerRoute:
+def _layer_route(hid, inter, dh, maxlen, ntok, grad, qkv_fused, sunk, carrier, ln_sunk=False) -> _LayerRoute:
     """qkv_fused: the Q/K/V weights and biases are stored back to back; sunk: every weight / bias gradient of the layer goes into the flat
     buffers; carrier: what came with x from the layer below -- None, "bf16" (its bf16 planes), "bf16+pair" (and its fp16-pair planes) or
-    "pair" (the fp16-pair planes alone: the layer below ran the all-pair path)."""
+    "pair" (the fp16-pair planes alone: the layer below ran the all-pair path); ln_sunk: so do the affine gradients of both LayerNorms."""
     planes = ops.planes_enabled() and hid % 32 == 0 and inter % 32 == 0
     flash = ops.flash_ok(hid, inter, dh, maxlen)
     # forward products whose operands are LayerNorm / GELU outputs and weights run on two fp16 pieces per operand once the problem fills
@@ -705,7 +706,10 @@ def _layer_route(hid, inter, dh, maxlen, ntok, grad, qkv_fused, sunk, carrier) -
     return _LayerRoute(planes=planes, flash=flash, pair=pair, pair_bwd=pair_bwd, one_qkv=one_qkv, pair_qkv=pair_qkv, split_xq=split_xq,
                        px=planes and not pair_bwd and not (pair_qkv and not grad), attn_pair=flash and pair_qkv and (pair_bwd or not grad),
                        ao_pair=pair_bwd and ops.amp_one_product(), keep3=not pair_bwd and not (pair and not grad),
-                       entry=flash and one_qkv and ops.layer_entry_ok(), grad=grad)
+                       entry=flash and one_qkv and ops.layer_entry_ok(),
+                       # (the bound route: both LayerNorm backwards write pair planes scaled by a bound -- csrc/rowops.hip takes hidden sizes
+                       #  that are multiples of 256 there -- and every gradient of the layer has a flat destination)
+                       entry_bwd=pair_bwd and ln_sunk and hid % 256 == 0 and ops.layer_bwd_entry_ok(), grad=grad)
 
 
 # what forward saves for backward, per _LayerRoute.saved (planes are saved as their buffers)
@@ -784,7 +788,7 @@ class BertLayerFn(torch.autograd.Function):
         sunk = grad and all(sinks(t) for t in (wq, wk, wv, bq, bk, bv, wo, bo, wi, bi, wo2, bo2))
         # (the pair planes of x arrive as an attribute of the previous layer's bf16 planes, or alone after an all-pair layer)
         carrier = None if xpl is None else "pair" if xpl.shape[0] == 2 else "bf16+pair" if hasattr(xpl, "_vbg_pair") else "bf16"
-        r = _layer_route(hid, inter, meta.dh, meta.maxlen, ntok, grad, fused_qkv, sunk, carrier)
+        r = _layer_route(hid, inter, meta.dh, meta.maxlen, ntok, grad, fused_qkv, sunk, carrier, ln_sunk=sunk and all(sinks(t) for t in (g1, b1, g2, b2)))
         sid = layer * 8
         ctx.route, ctx.meta, ctx.cfg = r, meta, (eps, p, seed, sid)
         ctx.w_refs = (wq, wk, wv, wo, wi, wo2)
@@ -880,12 +884,74 @@ class BertLayerFn(torch.autograd.Function):
         r = ctx.route
         s = SimpleNamespace(**dict(zip(_SAVED[r.saved], ctx.saved_tensors)))
         if r.pair_bwd:
-            return BertLayerFn._backward_pair(ctx, s, dy)
+            # the bound route: both LayerNorm backwards deliver their dx as pair planes scaled by a bound (hidden a multiple of 256, their
+            # affine gradients sunk) -- one keyword set, handed to the one-call entry or to the per-launch sequence
+            bound = s.xh1.shape[1] % 256 == 0 and all(wgrad_dest(t) is not None for t in ctx.b_refs[6:])
+            return (BertLayerFn._backward_pair_bound if bound else BertLayerFn._backward_pair)(ctx, s, dy)
         return (BertLayerFn._backward_planes if r.planes else BertLayerFn._backward_dense)(ctx, s, dy)
 
     @staticmethod
+    def _backward_pair_bound(ctx, s, dy):
+        """backward of the all-pair path on the bound route: every product on two fp16 pieces, every gradient operand written as pair
+        planes by its producer -- scaled by a rigorous bound (LayerNorm backward, the bounded epilogues of the data-gradient products) or by
+        its measured maximum (d(qkv): one split pass) -- products scale back (exact).  Host bookkeeping first, then ONE keyword set for
+        ops.bert_layer_bwd (one library call) or ops.bert_layer_bwd_launches (the same launches one by one), then the notifications."""
+        meta = ctx.meta
+        eps, p, seed, sid = ctx.cfg
+        (ntok, inter), hid = s.h.shape, s.xh1.shape[1]
+        dev = s.h.device
+        mk = lambda buf, cols: ops.Planes(buf, ntok, cols, buf.shape[2])
+        rbq, rbk, rbv, rbo, rbi, rbo2, rg1, rb1, rg2, rb2 = ctx.b_refs
+        rq, rk, rv, ro, ri, ro2 = ctx.w_refs
+        assert s.pqkv.shape[0] == 2, "the all-pair backward's q / k / v are fp16-pair planes"
+        # ---- gradient destinations: flat views, Q/K/V stacked
+        dg2, db2, sunk2 = _affine_dest(rg2, rb2)
+        dg1, db1, sunk1 = _affine_dest(rg1, rb1)
+        gq = [wgrad_dest(t) for t in (rq, rk, rv, rbq, rbk, rbv)]
+        dests = dict(dg2=dg2, db2=db2, dbo2=wgrad_dest(rbo2), dbi=wgrad_dest(rbi), dg1=dg1, db1=db1, dbo=wgrad_dest(rbo), dbqkv=_stack3(gq[3]),
+                     dwo2=wgrad_dest(ro2), dwi=wgrad_dest(ri), dwo=wgrad_dest(ro), dwqkv=_stack3(gq[0]))
+        # ---- operands: the transposed weight planes and the column-L1 words (a cache miss launches the weight split / the norms here, in
+        #      front of the layer's launches on the same stream), the amax slot of dy, the planes of the saved activations
+        wts = dict(wo2_t=ops.weight_planes(ro2, True, view=s.wo2, pair=True), wi_t=ops.weight_planes(ri, True, view=s.wi, pair=True),
+                   wo_t=ops.weight_planes(ro, True, view=s.wo, pair=True),
+                   wqkv_t=ops.weight_planes(rq, True, view=_stack3(s.wq), also=(rk, rv), pair=True),
+                   l1_wo2=ops.weight_col_l1max(ro2, view=s.wo2), l1_wo=ops.weight_col_l1max(ro, view=s.wo))
+        dyc = _c(dy)
+        s_dy = _amax_tag(dy)
+        if s_dy is None:
+            s_dy = ops.amax(dyc)                  # (the top layer: its output gradient is a sum autograd formed)
+        # (the attention output as the B operand of the output projection's weight gradient: pair planes written by the forward kernel)
+        qctx = mk(s.pctxq, hid) if s.pctxq is not None else ops.split_planes_pair(s.ctxv)
+        # ---- the nine amax slots: max |dfo| / |dao| (the next bounds' inputs), the bounds the planes of dfo / dh / dao / d(context) are
+        #      scaled with, max |dx1| / |d(qkv)| / |dx| riding on the launches that complete those tensors
+        slots = ops.amax_slots(dev, 9)
+        empty = lambda n: torch.empty((ntok, n), device=dev, dtype=f32)
+        tile = lambda n, wide=False: ops.pair_tile(ntok, n, wide)
+        dx = empty(hid)
+        kw = dict(p=p, seed=seed, sid=sid, scale=1.0 / (meta.dh ** 0.5), masks=ctx.masks, dy=dyc, s_dy=s_dy, xh2=s.xh2, rs2=s.rs2, g2=s.g2, xh1=s.xh1,
+                  rs1=s.rs1, g1=s.g1, h=s.h, ctxv=s.ctxv, kbar=s.kbar, lse=s.lse, delta=ctx.delta_buf, pqkv=mk(s.pqkv, 3 * hid), qx=mk(s.xq, hid),
+                  qctx=qctx, qx1=mk(s.px1q, hid), qg=mk(s.pgq, inter), tile_dh=tile(inter, True), tile_h=tile(hid),
+                  tile_wgrad=ops.grouped_wgrad_tile(((hid, inter), (inter, hid), (hid, hid), (3 * hid, hid)), dev), slots=slots,
+                  qdfo=ops.pair_empty(ntok, hid, dev), dx1=empty(hid), qdh=ops.pair_empty(ntok, inter, dev), qdao=ops.pair_empty(ntok, hid, dev),
+                  dx=dx, pdctx=ops.pair_empty(ntok, hid, dev), dqkv=empty(3 * hid), qdqkv=ops.pair_empty(ntok, 3 * hid, dev),
+                  # (deterministic mode: the fp32 dL/dh the fixed-order column sums are taken from)
+                  det_scratch=empty((inter + 3) // 4 * 4) if ops.deterministic_active() else None, **wts, **dests)
+        (ops.bert_layer_bwd if ctx.route.entry_bwd else ops.bert_layer_bwd_launches)(meta, **kw)
+        # ---- every gradient of the layer is enqueued: tell the reducer, in the order the launches completed them
+        dg2, db2 = _affine_done(rg2, rb2, dg2, db2, sunk2)
+        wgrad_done(rbo2)
+        wgrad_done(rbi)
+        dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
+        wgrad_done(rbo)
+        for t in (ro2, ri, ro, rq, rk, rv, rbq, rbk, rbv):
+            wgrad_done(t)
+        dx._vbg_amax = (slots[8], dx._version)          # (max |dx| for the layer below: its LayerNorm 2 bound)
+        return _grads(dx, dg1=dg1, db1=db1, dg2=dg2, db2=db2)
+
+    @staticmethod
     def _backward_pair(ctx, s, dy):
-        """backward of the all-pair path: every product on two fp16 pieces.  A gradient operand is split by a pass of its own once its
+        """backward of the all-pair path off the bound route (a LayerNorm whose affine gradients are not sunk, or a hidden size the bound
+        kernels do not take): every product on two fp16 pieces.  A gradient operand is split by a pass of its own once its
         largest magnitude is known (LayerNorm backward -> fp32 -> vbg_amax -> scaled split with the bias column sums; the GELU-gradient
         product reports the maximum of what it stores), scaled by the power of two of that maximum; products scale back (exact)."""
         meta = ctx.meta
@@ -925,22 +991,17 @@ class BertLayerFn(torch.autograd.Function):
         s_dh = ops.amax_slot(dev)
         qdh = ops.pair_empty(ntok, inter, dev)
         ops.plane_gemm(qdfo, ops.weight_planes(ro2, True, view=s.wo2, pair=True), None, epi=EPI_MUL_GELU_GRAD, C2=s.h, tile=tile(inter, True), form=1,
-                       a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=s.wo2), q_mul=1.13 * 1.01, q_ref_out=s_dh,
+                       a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo, q_l1=ops.weight_col_l1max(ro2, view=s.wo2), q_mul=ops.Q_MUL_GELU_GRAD, q_ref_out=s_dh,
                        colsum_out=wgrad_dest(rbi))
         wgrad_done(rbi)
         s_dx1 = ops.amax_slot(dev) if bound else None           # (max |dx1| rides on the product that completes it: LayerNorm 1's bound)
         ops.plane_gemm(qdh, ops.weight_planes(ri, True, view=s.wi, pair=True), dx1, accumulate=True, tile=tile(hid), form=1, a_amax=s_dh, c_amax=s_dx1)
-        # ---- LayerNorm 1 backward -> dao (pair planes by the same bound, or fp32 + split)
+        # ---- LayerNorm 1 backward -> dao: fp32 + split (with both LayerNorms on the bound the layer runs _backward_pair_bound)
         dg1, db1, sunk1 = _affine_dest(rg1, rb1)
-        s_dao = ops.amax_slot(dev)
-        if bound and sunk1:
-            s_dao_ref = ops.amax_slot(dev)
-            qdao, dx = ops.dropout_add_ln_bwd_pair(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1, wgrad_dest(rbo), s_dx1, s_dao, s_dao_ref)
-        else:
-            s_dao_ref = s_dao
-            dao, dx = ops.dropout_add_ln_bwd(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1, dx_amax=s_dao)
-            qdao = ops.split_planes_pair(dao, amax_slot_=s_dao, colsum_out=wgrad_dest(rbo))
-            del dao
+        s_dao = s_dao_ref = ops.amax_slot(dev)
+        dao, dx = ops.dropout_add_ln_bwd(dx1, s.xh1, s.rs1, s.g1, p, seed, sid + 1, dg1, db1, dx_amax=s_dao)
+        qdao = ops.split_planes_pair(dao, amax_slot_=s_dao, colsum_out=wgrad_dest(rbo))
+        del dao
         dg1, db1 = _affine_done(rg1, rb1, dg1, db1, sunk1)
         wgrad_done(rbo)
         # ---- d(context), the dO operand of the fused attention backward: fp16-pair planes like the forward's q / k / v planes, scaled by a
@@ -950,7 +1011,7 @@ class BertLayerFn(torch.autograd.Function):
         pdctx = ops.pair_empty(ntok, hid, dev)
         s_dctx = ops.amax_slot(dev)
         ops.plane_gemm(qdao, ops.weight_planes(ro, True, view=s.wo, pair=True), None, tile=tile(hid), form=1, a_amax=s_dao_ref, out_pair=pdctx,
-                       q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=s.wo), q_mul=1.01, q_ref_out=s_dctx)
+                       q_ref_in=s_dao, q_l1=ops.weight_col_l1max(ro, view=s.wo), q_mul=ops.Q_MUL_LINEAR, q_ref_out=s_dctx)
         delta = ctx.delta_buf
         dqkv = torch.empty((ntok, 3 * hid), device=dev, dtype=f32)
         sc = 1.0 / (meta.dh ** 0.5)

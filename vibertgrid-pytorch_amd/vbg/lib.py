@@ -98,6 +98,30 @@ class BertLayerFwdDesc(C.Structure):         # include/vbg.h vbg_bert_layer_fwd_
                 ("fo", c_vp), ("y", c_vp), ("xhat2", c_vp), ("rstd2", c_vp), ("py", PlanesRef), ("pyq", PlanesRef)]
 
 
+class BertLayerBwdDesc(C.Structure):         # include/vbg.h vbg_bert_layer_bwd_desc
+    _fields_ = [("ntok", c_int), ("hidden", c_int), ("inter", c_int), ("heads", c_int),
+                ("drop_p", c_f), ("seed", c_ull), ("stream_id0", c_ull),
+                ("form", c_int), ("form_attn", c_int), ("deterministic", c_int),
+                ("tile_dh", c_int), ("tile_dx1", c_int), ("tile_dctx", c_int), ("tile_dx", c_int), ("tile_wgrad", c_int),
+                ("cq_mul_dh", c_f), ("cq_mul_dctx", c_f),
+                ("ntasks", c_int), ("max_len", c_int), ("tasks", c_vp), ("seq_len", c_vp), ("seq_row0", c_vp), ("pad_off", c_vp), ("ntok_pad", c_ll),
+                ("mask_q", c_vp), ("mask_k", c_vp), ("mask_off", c_vp), ("attn_scale", c_f), ("keep_scale", c_f),
+                ("dy", c_vp), ("s_dy", c_vp),
+                ("xhat2", c_vp), ("rstd2", c_vp), ("g2", c_vp), ("xhat1", c_vp), ("rstd1", c_vp), ("g1", c_vp),
+                ("h", c_vp), ("ctx", c_vp), ("kbar", c_vp), ("lse", c_vp),
+                ("pqkv", PlanesRef), ("qx", PlanesRef), ("qctx", PlanesRef), ("qx1", PlanesRef), ("qg", PlanesRef),
+                ("wqkv_t", PlanesRef), ("wo_t", PlanesRef), ("wi_t", PlanesRef), ("wo2_t", PlanesRef),
+                ("l1_wo2", c_vp), ("l1_wo", c_vp),
+                ("s_dfo", c_vp), ("s_dfo_ref", c_vp), ("s_dh", c_vp), ("s_dx1", c_vp), ("s_dao", c_vp), ("s_dao_ref", c_vp), ("s_dctx", c_vp),
+                ("s_dqkv", c_vp), ("s_dx", c_vp),
+                ("ln_ws", c_vp), ("delta", c_vp), ("det_scratch", c_vp), ("det_ws", c_vp),
+                ("qdfo", PlanesRef), ("qdh", PlanesRef), ("qdao", PlanesRef), ("pdctx", PlanesRef), ("qdqkv", PlanesRef),
+                ("dx1", c_vp), ("dqkv", c_vp),
+                ("dx", c_vp),
+                ("dg2", c_vp), ("db2", c_vp), ("dbo2", c_vp), ("dbi", c_vp), ("dg1", c_vp), ("db1", c_vp), ("dbo", c_vp), ("dbqkv", c_vp),
+                ("dwo2", c_vp), ("dwi", c_vp), ("dwo", c_vp), ("dwqkv", c_vp)]
+
+
 class OptimChunk(C.Structure):               # include/vbg.h vbg_optim_chunk
     _fields_ = [("start", c_ll), ("length", c_int), ("group", c_int)]
 
@@ -161,6 +185,7 @@ SIGNATURES = {
     "vbg_split_planes_pair_t_batched": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_vp]),
     "vbg_attn": (c_int, [C.POINTER(AttnDesc), c_vp]),
     "vbg_bert_layer_fwd": (c_int, [C.POINTER(BertLayerFwdDesc), c_vp]),
+    "vbg_bert_layer_bwd": (c_int, [C.POINTER(BertLayerBwdDesc), c_vp]),
     "vbg_attn_drop_thr16": (C.c_uint, [c_f]),
     "vbg_attn_mask": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_f, c_ull, c_ull, c_vp, c_vp, c_vp]),
     "vbg_attn_mask_layers": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_f, c_ull, c_ull, c_ull, c_int, c_ll, c_vp, c_vp, c_vp]),

@@ -7,8 +7,8 @@ import os
 
 import torch
 
-from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_FWD, EPI_GELU_DUAL, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
+from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_DKV, ATTN_DQ, ATTN_FWD, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
+                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -466,17 +466,21 @@ def plane_gemm(a: Planes, b: Planes, out=None, *, bias=None, epi=EPI_NONE, C2=No
     return out
 
 
+def grouped_wgrad_tile(shapes, device):
+    """tile of a grouped TN launch whose problems write [m, n] outputs, shapes = [(m, n), ...]: 256 x 128 output tiles move a third fewer
+    operand bytes per product (csrc/gemm_planes.hip: the kernels are bound by what a CU ingests); worth it once they still cover most of
+    the chip (the four weight gradients of a bert-base layer: 216 tiles).  0: the library's choice"""
+    t256 = sum(((m + 255) // 256) * ((n + 127) // 128) for m, n in shapes)
+    return 256128 if t256 >= 0.6 * torch.cuda.get_device_properties(device).multi_processor_count else 0
+
+
 def plane_gemm_grouped(problems, *, trans=True, accumulate=True, tile=0, alpha=1.0, form=0, a_amax=None):
     """several independent plane products of ONE reduction length in one launch: problems = [(a: Planes, b: Planes, out), ...]
     (trans: out[a.cols, b.cols] (+)= a^T b, the weight gradients of a layer).  form=1: fp16-pair planes, a_amax = [slot or None per
     problem] (the scale of each problem's A operand)"""
     assert 1 <= len(problems) <= 4
     if trans and tile == 0:
-        # 256 x 128 output tiles move a third fewer operand bytes per product (csrc/gemm_planes.hip: the kernels are bound by what a CU
-        # ingests); worth it once they still cover most of the chip (the four weight gradients of a bert-base layer: 216 tiles)
-        t256 = sum(((a.cols + 255) // 256) * ((b.cols + 127) // 128) for a, b, _ in problems)
-        if t256 >= 0.6 * torch.cuda.get_device_properties(problems[0][2].device).multi_processor_count:
-            tile = 256128
+        tile = grouped_wgrad_tile([(a.cols, b.cols) for a, b, _ in problems], problems[0][2].device)
     d = PlaneGemmDesc()
     d.ngroups, d.trans, d.accumulate, d.tile, d.alpha, d.splitk = len(problems), int(trans), int(bool(accumulate)), int(tile), float(alpha), 1
     k = None
@@ -945,6 +949,22 @@ def amax_slot(device):
     i = ent[1]
     ent[1] = i + 1
     return ent[0][i]
+
+
+def amax_slots(device, k):
+    """k fresh zero amax slots in one call (a layer's backward takes nine): the same pools as amax_slot, never rewound; where the current
+    pool ends before the k-th slot the rest come from a fresh one"""
+    key = (device.type, device.index, raw_stream(device) if device.type == "cuda" else 0)
+    out = []
+    while len(out) < k:
+        ent = _AMAX_POOL.get(key)
+        if ent is None or ent[1] >= ent[0].shape[0]:
+            ent = _AMAX_POOL[key] = [torch.zeros((_AMAX_POOL_SLOTS[0], AMAX_WORDS * AMAX_STRIDE), device=device, dtype=torch.int32), 0]
+        i = ent[1]
+        n = min(k - len(out), ent[0].shape[0] - i)
+        ent[1] = i + n
+        out.extend(ent[0][i:i + n].unbind(0))
+    return out
 
 
 def amax(x, slot=None):
@@ -1486,16 +1506,15 @@ def dropout_add_ln_bwd_planes(dy, xhat, rstd, gamma, p, seed, sid, dgamma, dbeta
     return pdx, dres
 
 
-def dropout_add_ln_bwd_pair(dy, xhat, rstd, gamma, p, seed, sid, dgamma, dbeta, dbias, dy_amax, dx_amax, dx_bound):
+def dropout_add_ln_bwd_pair(dy, xhat, rstd, gamma, p, seed, sid, dgamma, dbeta, dbias, dy_amax, dx_amax, dx_bound, out=None):
     """LayerNorm backward with dx as fp16-pair planes scaled by a BOUND (-> Planes, dres): dy_amax = amax slot of dy (in), dx_amax = zeroed
     slot for max |dx| (out), dx_bound = zeroed slot that receives the bound (out: pass it as a_amax of the products that read the planes);
-    dbias += column sums of dx"""
+    dbias += column sums of dx.  out: (the pair Planes, dres) to write instead of fresh ones"""
     rows, hidden = xhat.shape
     dev = xhat.device
     ws = _ln_workspace(dev, hidden, rows, 3)
-    qdx = pair_empty(rows, hidden, dev)
+    qdx, dres = out if out is not None else (pair_empty(rows, hidden, dev), torch.empty_like(xhat))
     assert qdx.ld == hidden
-    dres = torch.empty_like(xhat)
     check(lib.vbg_dropout_add_ln_bwd_pair(P(dy), P(xhat), P(rstd), rows, hidden, P(gamma), p, seed, sid, P(qdx.buf), qdx.ld, qdx.plane, P(dres),
                                           P(dgamma), P(dbeta), P(dbias), P(ws), P(dy_amax), P(dx_amax), P(dx_bound), _stream()),
           "vbg_dropout_add_ln_bwd_pair")
@@ -1744,6 +1763,122 @@ def bert_layer_launches(meta, *, eps, p, seed, sid, x, xa, pair_qkv, wqkv, bqkv,
     plane_gemm(px1q if pair_ffn else px1, wi, h, bias=bi, epi=EPI_GELU_DUAL, out_planes=pg, out_pair=pgq, tile=tile_ffn1, form=int(pair_ffn))
     plane_gemm(pgq if pair_ffn else pg, wo2, fo, bias=bo2, tile=tile_ffn2, form=int(pair_ffn))
     dropout_add_ln_fwd(fo, x1, g2, b2, eps, p, seed, sid + 2, out_planes=py, out_pair=pyq, out=(y, xh2, rs2))
+
+
+# ----------------------------------------------------------------------------------------------
+# The layer's backward as ONE library call (csrc/encoder.hip, include/vbg.h vbg_bert_layer_bwd): the all-pair backward on the bound route
+# (vbg.functions.BertLayerFn._backward_pair), ten launches -- twelve in deterministic mode -- with the descriptors plane_gemm / attn /
+# dropout_add_ln_bwd_pair / split_planes_pair / plane_gemm_grouped would build one by one: bit-identical results.  Its own switch, so
+# that either half of the layer can be compared alone: `VBG_LAYER_BWD_ENTRY=0` is the per-launch path.
+# ----------------------------------------------------------------------------------------------
+_LAYER_BWD_ENTRY = [os.environ.get("VBG_LAYER_BWD_ENTRY", "1") != "0"]
+# cq_mul of the two bounded pair outputs (include/vbg.h cq_ref_in): the largest slope of the GELU (1.129) on dL/dh, and 1 % of rounding margin
+Q_MUL_GELU_GRAD = 1.13 * 1.01
+Q_MUL_LINEAR = 1.01
+_LAYER_BWD_WS = {}
+
+
+def set_layer_bwd_entry(on: bool):
+    _LAYER_BWD_ENTRY[0] = bool(on)
+
+
+def layer_bwd_entry_ok() -> bool:
+    """the measurement hooks time single launches: they stay on the per-launch path"""
+    return _LAYER_BWD_ENTRY[0] and _GEMM_PROF is None
+
+
+def _det_colsum_ws(device, elems):
+    """fp64 scratch of the entry's two fixed-order column sums (one per device and stream: the launches that use it are ordered by it)"""
+    key = (device, raw_stream(device))
+    ws = _LAYER_BWD_WS.get(key)
+    if ws is None or ws.numel() < elems:
+        ws = _LAYER_BWD_WS[key] = torch.empty((elems,), device=device, dtype=torch.float64)
+    return ws
+
+
+def bert_layer_bwd(meta, *, p, seed, sid, scale, masks, dy, s_dy, xh2, rs2, g2, xh1, rs1, g1, h, ctxv, kbar, lse, delta, pqkv, qx, qctx, qx1, qg,
+                   wqkv_t, wo_t, wi_t, wo2_t, l1_wo2, l1_wo, tile_dh, tile_h, tile_wgrad, slots, qdfo, dx1, qdh, qdao, dx, pdctx, dqkv, qdqkv,
+                   det_scratch, dg2, db2, dbo2, dbi, dg1, db1, dbo, dbqkv, dwo2, dwi, dwo, dwqkv):
+    """Every Planes argument is fp16-pair planes.  slots: the nine zeroed amax slots (s_dfo, s_dfo_ref, s_dh, s_dx1, s_dao, s_dao_ref, s_dctx,
+    s_dqkv, s_dx); s_dy: the slot of dy; w*_t: planes of the transposed weights; tile_dh: of the GELU-gradient product, tile_h: of the
+    three products with `hidden` columns, tile_wgrad: of the grouped weight gradients; det_scratch: fp32 [ntok, roundup(inter, 4)] in
+    deterministic mode, else None; d* behind it: the gradient destinations (accumulated into; dbqkv / dwqkv: the stacked Q/K/V views).
+    The layer's backward leaves from ONE library call (csrc/encoder.hip); bert_layer_bwd_launches issues the same launches one by one."""
+    d = BertLayerBwdDesc()
+    ntok, inter = h.shape
+    hid = xh1.shape[1]
+    dev = h.device
+    det = _DET[0]
+    assert all(t.is_contiguous() for t in (dy, dx1, dx, dqkv, ctxv, kbar, dwo2, dwi, dwo, dwqkv)) and (det_scratch is not None) == det
+    d.ntok, d.hidden, d.inter, d.heads = ntok, hid, inter, meta.heads
+    d.drop_p, d.seed, d.stream_id0 = p, seed, sid
+    d.form, d.form_attn, d.deterministic = 2 if _AMP[0] else 1, 2 if amp_one_product() else 1, int(det)
+    d.tile_dh, d.tile_dx1, d.tile_dctx, d.tile_dx, d.tile_wgrad = tile_dh, tile_h, tile_h, tile_h, tile_wgrad
+    d.cq_mul_dh, d.cq_mul_dctx = Q_MUL_GELU_GRAD, Q_MUL_LINEAR
+    d.ntasks, d.max_len, d.ntok_pad = meta.ntasks, meta.maxlen, meta.ntok_pad
+    d.tasks, d.seq_len, d.seq_row0, d.pad_off = meta.tasks.data_ptr(), meta.lens.data_ptr(), meta.seq_row0.data_ptr(), meta.pad_off.data_ptr()
+    if masks is not None:
+        d.mask_q, d.mask_k, d.mask_off = masks[0].data_ptr(), masks[1].data_ptr(), meta.mask_off.data_ptr()
+        d.keep_scale = attn_keep_scale(p)
+    else:
+        d.keep_scale = 1.0
+    d.attn_scale = scale
+    d.dy, d.s_dy = dy.data_ptr(), s_dy.data_ptr()
+    d.xhat2, d.rstd2, d.g2, d.xhat1, d.rstd1, d.g1 = xh2.data_ptr(), rs2.data_ptr(), g2.data_ptr(), xh1.data_ptr(), rs1.data_ptr(), g1.data_ptr()
+    d.h, d.ctx, d.kbar, d.lse = h.data_ptr(), ctxv.data_ptr(), kbar.data_ptr(), lse.data_ptr()
+    _pref(d.pqkv, pqkv); _pref(d.qx, qx); _pref(d.qctx, qctx); _pref(d.qx1, qx1); _pref(d.qg, qg)
+    _pref(d.wqkv_t, wqkv_t); _pref(d.wo_t, wo_t); _pref(d.wi_t, wi_t); _pref(d.wo2_t, wo2_t)
+    d.l1_wo2, d.l1_wo = l1_wo2.data_ptr(), l1_wo.data_ptr()
+    (d.s_dfo, d.s_dfo_ref, d.s_dh, d.s_dx1, d.s_dao, d.s_dao_ref, d.s_dctx, d.s_dqkv, d.s_dx) = [s.data_ptr() for s in slots]
+    d.ln_ws, d.delta = _ln_workspace(dev, hid, ntok, 3).data_ptr(), delta.data_ptr()
+    if det:
+        ws = _det_colsum_ws(dev, max(int(lib.vbg_colsum_det_ws_elems(ntok, inter)), int(lib.vbg_colsum_det_ws_elems(ntok, 3 * hid))))
+        d.det_scratch, d.det_ws = det_scratch.data_ptr(), ws.data_ptr()
+    _pref(d.qdfo, qdfo); _pref(d.qdh, qdh); _pref(d.qdao, qdao); _pref(d.pdctx, pdctx); _pref(d.qdqkv, qdqkv)
+    d.dx1, d.dqkv, d.dx = dx1.data_ptr(), dqkv.data_ptr(), dx.data_ptr()
+    d.dg2, d.db2, d.dbo2, d.dbi, d.dg1, d.db1, d.dbo, d.dbqkv = (dg2.data_ptr(), db2.data_ptr(), dbo2.data_ptr(), dbi.data_ptr(), dg1.data_ptr(),
+                                                                 db1.data_ptr(), dbo.data_ptr(), dbqkv.data_ptr())
+    d.dwo2, d.dwi, d.dwo, d.dwqkv = dwo2.data_ptr(), dwi.data_ptr(), dwo.data_ptr(), dwqkv.data_ptr()
+    if _DISPATCH[0] is not None:            # (the same tags the per-launch path leaves: tests assert which forms ran)
+        fam = "plane_gemm:onep" if _AMP[0] else "plane_gemm:pair"
+        for t in (tile_dh, tile_h, tile_h, tile_h):
+            _seen(fam)
+            _seen(f"plane_gemm:tile{int(t)}")
+        _seen("plane_gemm:grouped_onep" if _AMP[0] else "plane_gemm:grouped_pair")
+        for _ in range(2):
+            _seen("attn:onep" if d.form_attn == 2 else "attn:pair")
+        for tag in (("det:colsum", "det:plane_colsum", "det:colsum", "det:split_colsum") if det else ("fatomic:plane_colsum", "fatomic:split_colsum")):
+            _seen(tag)
+        _seen("bert_layer_bwd:entry")
+    check(lib.vbg_bert_layer_bwd(C.byref(d), _stream()), "vbg_bert_layer_bwd")
+
+
+def bert_layer_bwd_launches(meta, *, p, seed, sid, scale, masks, dy, s_dy, xh2, rs2, g2, xh1, rs1, g1, h, ctxv, kbar, lse, delta, pqkv, qx, qctx, qx1,
+                            qg, wqkv_t, wo_t, wi_t, wo2_t, l1_wo2, l1_wo, tile_dh, tile_h, tile_wgrad, slots, qdfo, dx1, qdh, qdao, dx, pdctx, dqkv,
+                            qdqkv, det_scratch, dg2, db2, dbo2, dbi, dg1, db1, dbo, dbqkv, dwo2, dwi, dwo, dwqkv):
+    """bert_layer_bwd one launch at a time, same kernels and descriptors (the measurement hooks time single launches)"""
+    s_dfo, s_dfo_ref, s_dh, s_dx1, s_dao, s_dao_ref, s_dctx, s_dqkv, s_dx = slots
+    # LayerNorm 2 backward -> dfo straight as pair planes scaled by a rigorous bound (max |dy| x max |gamma| x max rstd x (2 + sqrt H) /
+    # keep; csrc/rowops.hip PL = 2), the bias gradient of the FFN output projection riding along: s_dfo = true max |dfo| (the next bound's
+    # input), s_dfo_ref = the scale the planes were written with
+    dropout_add_ln_bwd_pair(dy, xh2, rs2, g2, p, seed, sid + 2, dg2, db2, dbo2, s_dy, s_dfo, s_dfo_ref, out=(qdfo, dx1))
+    # dL/dh = (dfo Wo2) o gelu'(h) leaves the product's epilogue as pair planes, scaled by the power of two of a BOUND -- max |dfo| * the
+    # largest column L1 norm of Wo2 * max gelu' -- so it needs no fp32 round trip and no split pass; s_dh receives the bound
+    plane_gemm(qdfo, wo2_t, det_scratch, epi=EPI_MUL_GELU_GRAD, C2=h, tile=tile_dh, form=1, a_amax=s_dfo_ref, out_pair=qdh, q_ref_in=s_dfo,
+               q_l1=l1_wo2, q_mul=Q_MUL_GELU_GRAD, q_ref_out=s_dh, colsum_out=dbi)
+    plane_gemm(qdh, wi_t, dx1, accumulate=True, tile=tile_h, form=1, a_amax=s_dh, c_amax=s_dx1)      # (max |dx1|: LayerNorm 1's bound)
+    dropout_add_ln_bwd_pair(dx1, xh1, rs1, g1, p, seed, sid + 1, dg1, db1, dbo, s_dx1, s_dao, s_dao_ref, out=(qdao, dx))
+    # d(context), the dO operand of the fused attention backward: pair planes scaled by a bound (max |dao| x the largest column L1 norm
+    # of W_o; the attention kernels read the scale from s_dctx)
+    plane_gemm(qdao, wo_t, None, tile=tile_h, form=1, a_amax=s_dao_ref, out_pair=pdctx, q_ref_in=s_dao, q_l1=l1_wo, q_mul=Q_MUL_LINEAR,
+               q_ref_out=s_dctx)
+    attn(meta, ATTN_DQ, pqkv, pdctx, dqkv, lse, delta, masks, scale, p, kbar=kbar, o=ctxv, out_amax=s_dqkv, do_amax=s_dctx)
+    attn(meta, ATTN_DKV, pqkv, pdctx, dqkv, lse, delta, masks, scale, p, out_amax=s_dqkv, do_amax=s_dctx)
+    split_planes_pair(dqkv, out=qdqkv, amax_slot_=s_dqkv, colsum_out=dbqkv)
+    plane_gemm(qdqkv, wqkv_t, dx, accumulate=True, tile=tile_h, form=1, a_amax=s_dqkv, c_amax=s_dx)   # (max |dx|: the bound of the layer below)
+    # the four weight gradients: one grouped TN launch on pair planes
+    plane_gemm_grouped([(qdfo, qg, dwo2), (qdh, qx1, dwi), (qdao, qctx, dwo), (qdqkv, qx, dwqkv)], trans=True, accumulate=True, tile=tile_wgrad,
+                       form=1, a_amax=[s_dfo_ref, s_dh, s_dao_ref, s_dqkv])
 
 
 def row_softmax(x):

@@ -719,6 +719,47 @@ int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int 
                      vbg_decode_rec* best, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation counts of `validate` (csrc/metrics.hip): what pipeline/criteria.py's token_F1_criteria, token_classification_criteria and
+ * BIO_F1_criteria (seqeval, default mode) need from a forward -- a few dozen integers -- counted where the scores lie.  ONE launch, one
+ * workgroup per sequence; sequence d owns the rows h_doc_off[d] .. h_doc_off[d + 1].  `h_doc_off` is HOST memory (ndoc + 1 entries, not
+ * decreasing, first >= 0), copied into the kernel arguments as vbg_field_decode does -- 512 sequences to a launch.  Exactly one of
+ *   scores    fp32 [N, C] row-major: the predicted class of a row is the first index of its largest raw score;
+ *   pred_tags int32 [N]: the predicted class itself (the crf head returns tags)
+ * is given, the other is NULL.  gt int32 [N].  A row whose gt -- or pred_tags entry -- lies outside [0, C) counts nowhere: it indexes
+ * nothing, it is left out of the token tables and both of its tags read `O` in the entity walk.
+ * `counts` is device memory of VBG_METRICS_COUNTS(T, C) 64-bit integers, which the launch ADDS to (64-bit integer atomics: sums of
+ * integers, exact and the same for every schedule, so the deterministic mode needs no other form):
+ *   counts[VBG_METRICS_ENT(T, C)  + ty * 3 + {0, 1, 2}]   entities of type ty: in gt (n_true), predicted (n_pred), in both (n_correct);
+ *   counts[VBG_METRICS_CONF(T, C) + g * C + p]            rows with gt class g and predicted class p;
+ *   counts[VBG_METRICS_TOK(T, C)  + c * 4 + {0, 1, 2, 3}] token_F1_criteria's literal TP, TN, FP, FN of class c, with scores only:
+ *             v = the row's score of class c truncated toward zero (`pred_label.int()`); TP: gt == c and v == 1, FN: gt == c and v == 0,
+ *             FP: gt != c and v == 1, TN: gt != c and v == 0; any other v, NaN included, counts nowhere.
+ * Entities (T >= 1; T == 0: no tag table, the entity block is empty): class k carries the tag letter tags.prefix[k] (VBG_TAG_*) and the
+ * type tags.type[k] in [0, T).  seqeval's get_entities: with (pt, pty) the tag of the row in front (`O` in front of row 0) and a
+ * virtual `O` row behind the last,
+ *   end(i)   = pt in {E, S}  or  (pt in {B, I} and t in {B, S, O})  or  (pt != O and pty != ty);     the entity in front of i is closed
+ *   start(i) = t in {B, S}   or  (pt in {E, S, O} and t in {E, I})  or  (t != O and pty != ty);      an entity begins at i
+ * an entity is (type, begin, last row); n_correct counts the entities of gt that the prediction holds with the same three values.
+ * Sequences carry nothing into each other.  Argument errors, before any launch: C outside [1, 64], T outside [0, 64], a table entry
+ * outside its range, both or neither of scores / pred_tags, negative or decreasing offsets, NULL gt with rows, NULL counts with
+ * ndoc > 0.  ndoc == 0 and empty sequences count nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define VBG_METRICS_MAX_C 64
+#define VBG_METRICS_MAX_T 64
+#define VBG_TAG_O 0
+#define VBG_TAG_B 1
+#define VBG_TAG_I 2
+#define VBG_TAG_E 3
+#define VBG_TAG_S 4
+#define VBG_METRICS_ENT(T, C) 0
+#define VBG_METRICS_CONF(T, C) (3 * (T))
+#define VBG_METRICS_TOK(T, C) (3 * (T) + (C) * (C))
+#define VBG_METRICS_COUNTS(T, C) (3 * (T) + (C) * (C) + 4 * (C))
+typedef struct vbg_tag_table { unsigned char prefix[VBG_METRICS_MAX_C]; unsigned char type[VBG_METRICS_MAX_C]; } vbg_tag_table;
+int vbg_seq_metrics(const float* scores, const int* pred_tags, const int* gt, const int* h_doc_off, int ndoc, int C, int T,
+                    vbg_tag_table tags, long long* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a13b. sampling and hard-example selection on the device  (csrc/sample.hip)
  *
  * vbg_sample_select replaces, for up to four label categories of one label array, the reference's `ce_loss[mask]` compaction plus

@@ -158,6 +158,10 @@ class OhemCats(C.Structure):                 # include/vbg.h vbg_ohem_cats (pass
     _fields_ = [("c", OhemCat * 4)]
 
 
+class TagTable(C.Structure):                 # include/vbg.h vbg_tag_table (passed by value)
+    _fields_ = [("prefix", C.c_ubyte * 64), ("type", C.c_ubyte * 64)]
+
+
 SGD_NESTEROV, SGD_MAXIMIZE, SGD_FIRST = 1, 2, 4          # vbg_sgd_group_opt.flags
 ADAM_AMSGRAD, ADAM_MAXIMIZE, ADAM_COUPLED = 1, 2, 4      # vbg_adam_group_opt.flags
 OPTIM_MAX_GROUPS = 32                        # include/vbg.h VBG_OPTIM_MAX_GROUPS
@@ -270,6 +274,7 @@ SIGNATURES = {
     "vbg_crf_nll_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vbg_crf_viterbi": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_field_decode": (c_int, [c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_d, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_seq_metrics": (c_int, [c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, TagTable, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_sgd_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroup), c_int, c_int, c_f, c_vp]),

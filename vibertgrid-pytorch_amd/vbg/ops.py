@@ -8,7 +8,7 @@ import os
 import torch
 
 from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_DKV, ATTN_DQ, ATTN_FWD, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, VbgError, check, lib)
+                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, TagTable, VbgError, check, lib)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -1905,6 +1905,30 @@ def field_decode(x, doc_off=None, thresh=None):
     check(lib.vbg_field_decode(P(x.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, int(thresh is not None),
                                0.0 if thresh is None else float(thresh), P(cls), P(score), P(best), _stream()), "vbg_field_decode")
     return cls, score, best
+
+
+def seq_metrics(gt, off, ncls, ntype, tag_table, counts, scores=None, pred_tags=None):
+    """counts (int64, device) += the validation counts of the sequences `off` (HOST row ranges, ndoc + 1 ints) in ONE launch
+    (vbg_seq_metrics, include/vbg.h): scores [N, ncls] fp32 or pred_tags [N] int32 (exactly one), gt [N] int32.  tag_table: a
+    lib.TagTable, read when ntype > 0.  No host read."""
+    ndoc = len(off) - 1
+    N = gt.shape[0]
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"vbg_seq_metrics: doc_off {list(off[:4])}... does not fit {N} rows")
+    if (scores is None) == (pred_tags is None):
+        raise VbgError("vbg_seq_metrics: exactly one of scores / pred_tags")
+    if N == 0 and ndoc >= 0 and all(int(v) == 0 for v in off):
+        return counts                                               # no rows: nothing to launch, nothing to count
+    assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 3 * ntype + ncls * ncls + 4 * ncls
+    assert gt.dtype == i32 and gt.is_contiguous()
+    if scores is not None:
+        _chk_f32(scores)
+        assert scores.shape == (N, ncls) and scores.is_contiguous()
+    else:
+        assert pred_tags.dtype == i32 and pred_tags.shape == (N,) and pred_tags.is_contiguous()
+    check(lib.vbg_seq_metrics(P(scores), P(pred_tags), P(gt), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, ntype, tag_table, P(counts), _stream()),
+          "vbg_seq_metrics")
+    return counts
 
 
 def gelu_bwd_(h, dg):

@@ -379,6 +379,42 @@ int vbg_normalize_resize(const float* img, int h, int w, int oh, int ow, const f
 int vbg_rescale_boxes(const long long* in, int S, float ratio_h, float ratio_w, int* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The whole of a1 for a batch (csrc/convaux.hip).  Replaces the per-image loop of pipeline/transform.py:104-171, 225-271 --
+ * normalise, resize_image, resize_boxes, batch_images' zero padding -- and the packing of the boxes that the grid scatter and
+ * RoIAlign read: ONE launch per VBG_TRANSFORM_MAX_IMAGES images.  `h_images` is HOST memory (B descriptors), copied into the kernel
+ * arguments as vbg_field_decode's row ranges are -- no device copy, no sync; a larger batch takes several launches.
+ *   formats   VBG_IMAGE_F32_CHW  fp32 [3,h,w], contiguous: the sample vbg_normalize_resize reads;
+ *             VBG_IMAGE_U8_CHW   uint8 [3,h,w], contiguous;
+ *             VBG_IMAGE_U8_HWC   uint8 [h,w,3], dense, a pixel's three bytes adjacent (a decoded image as it lies in memory);
+ *             a byte u is the sample (float)u / 255.0f, by DIVISION, correctly rounded: the value torch's CPU
+ *             `uint8 -> float32 -> .div(255)` (ToTensor) gives for all 256 bytes.  A multiplication by 1/255 differs in 126 of them.
+ *             image_mean / image_std stay on the 0..1 scale for every format.
+ *   image     slot i of the NHWC fp32 [B,H,W,3] batch: rows < oh and columns < ow with vbg_normalize_resize's arithmetic (the two
+ *             kernels share one device function: same bits), the right and bottom padding as +0.0.  Every element of the slot is
+ *             written exactly once: the caller needs no fill.
+ *   boxes     int64 [S,4] (NULL with S == 0) -> rows box_row .. box_row + S of boxes_out int32 [N,4] with vbg_rescale_boxes's
+ *             arithmetic and the ratios (float)((double)oh / h), (float)((double)ow / w): columns 0, 2 take the HEIGHT ratio as the
+ *             reference does (:167-168).  box_doc[row] = i for those rows; box_off[i] = box_row, box_off[B] = the last image's
+ *             box_row + S (box_off int32 [B + 1], may be NULL).  box_row must be the running sum of S: box_row[i + 1] = box_row[i] + S[i].
+ * 64-bit indexing; bytes are read one at a time, nothing outside the 3 * h * w samples of an image is touched and no alignment is
+ * assumed.  No atomics: deterministic.  Argument errors, before any launch: h, w, oh or ow < 1, oh > H, ow > W, an unknown format,
+ * S < 0, rows outside [0, N), box_row not the running sum, B < 0, a NULL operand that is needed.  B == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+#define VBG_TRANSFORM_MAX_IMAGES 64
+#define VBG_IMAGE_F32_CHW 0
+#define VBG_IMAGE_U8_CHW 1
+#define VBG_IMAGE_U8_HWC 2
+typedef struct vbg_transform_image {                              /* 48 bytes */
+    const void* img;
+    const long long* boxes;
+    int format, h, w, oh, ow;
+    int S, box_row;
+} vbg_transform_image;
+int vbg_transform_max_images(void);
+int vbg_transform_batch(const vbg_transform_image* h_images, int B, const float* h_mean3, const float* h_std3, float* batch_nhwc,
+                        int H, int W, int* boxes_out, int* box_doc, int* box_off, long long N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * a3. BERT encoder pieces (transformers BertModel; model/BERTgrid_generator.py:134)
  * ------------------------------------------------------------------------------------------ */
 /* out[t] = dropout(LN(word[ids[t]] + pos[pos_ids[t]] + type[0])) ; saves xhat/rstd for backward */

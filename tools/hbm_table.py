@@ -48,6 +48,8 @@ bytes_per_step = {
     "grid_scatter_bwd_kernel": act(B * 64 * 64, HID) + NSEG * HID * f4,
     "upsample2_add_kernel": sum(act(B * s * s, 256) * 2 + act(B * s * s // 4, 256) for s in (32, 64, 128)),
     "normalize_resize_kernel": 2 * B * H * W * 3 * f4,
+    # a1 in one launch: the fp32 images read once, every slot written once (padding included, no fill); uint8 images read a quarter
+    "transform_batch_kernel": 2 * B * H * W * 3 * f4,
     "seg_reduce_fwd_kernel": 4096 * HID * f4 + NSEG * HID * f4,
     "seg_reduce_bwd_kernel": 4096 * HID * f4 + NSEG * HID * f4,
     # gradient operands that still take a split pass of their own (end of round 4): d(qkv) [ntok, 2304] per layer, the encoder input and

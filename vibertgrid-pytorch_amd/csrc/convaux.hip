@@ -531,16 +531,13 @@ __global__ void upsample_nhwc_to_nchw_kernel(const float* __restrict__ x, int B,
 // input transform: (img - mean) / std, bilinear resize (align_corners=False, scale = in/out),
 // written NHWC into batch slot b.  One thread per output pixel (3 channels).
 // ------------------------------------------------------------------------------------------
-__global__ void normalize_resize_kernel(const float* __restrict__ img, int h, int w, int oh, int ow, float m0, float m1, float m2,
-                                        float s0, float s1, float s2, float* __restrict__ out, int W) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= oh * ow) return;
-    const int oy = i / ow, ox = i - oy * ow;
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-    float v[3];
+// The arithmetic of one output pixel, shared by normalize_resize_kernel and transform_batch_kernel (same bits from both):
+// tap(c, y, x) is the NORMALISED sample of channel c at source row y, column x; the identity case takes the sample as it is.
+template <class Tap>
+__device__ __forceinline__ void normalize_resize_pixel(const Tap& tap, int h, int w, int oh, int ow, int oy, int ox, float v[3]) {
     if (oh == h && ow == w) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = (img[((long long)c * h + oy) * w + ox] - mean[c]) / sd[c];
+        for (int c = 0; c < 3; ++c) v[c] = tap(c, oy, ox);
     } else {
         const float sy = (float)h / (float)oh, sx = (float)w / (float)ow;
         float fy = ((float)oy + 0.5f) * sy - 0.5f; if (fy < 0.f) fy = 0.f;
@@ -550,12 +547,28 @@ __global__ void normalize_resize_kernel(const float* __restrict__ img, int h, in
         const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float* p = img + (long long)c * h * w;
-            const float a = (p[(long long)y0 * w + x0] - mean[c]) / sd[c], b = (p[(long long)y0 * w + x1] - mean[c]) / sd[c];
-            const float d = (p[(long long)y1 * w + x0] - mean[c]) / sd[c], e = (p[(long long)y1 * w + x1] - mean[c]) / sd[c];
+            const float a = tap(c, y0, x0), b = tap(c, y0, x1);
+            const float d = tap(c, y1, x0), e = tap(c, y1, x1);
             v[c] = hy * (hx * a + lx * b) + ly * (hx * d + lx * e);
         }
     }
+}
+
+struct tap_f32_chw {            // fp32 [3,h,w]
+    const float* img; int h, w; float mean[3], sd[3];
+    __device__ __forceinline__ float operator()(int c, int y, int x) const {
+        return (img[((long long)c * h + y) * w + x] - mean[c]) / sd[c];
+    }
+};
+
+__global__ void normalize_resize_kernel(const float* __restrict__ img, int h, int w, int oh, int ow, float m0, float m1, float m2,
+                                        float s0, float s1, float s2, float* __restrict__ out, int W) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= oh * ow) return;
+    const int oy = i / ow, ox = i - oy * ow;
+    const tap_f32_chw tap = {img, h, w, {m0, m1, m2}, {s0, s1, s2}};
+    float v[3];
+    normalize_resize_pixel(tap, h, w, oh, ow, oy, ox, v);
     float* o = out + ((long long)oy * W + ox) * 3;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
 }
@@ -565,6 +578,74 @@ __global__ void rescale_boxes_kernel(const long long* __restrict__ in, int n, fl
     if (i >= n) return;
     const float r = ((i & 1) == 0) ? rh : rw;       // cols 0,2 <- height ratio; 1,3 <- width ratio (reference swap)
     out[i] = (int)__fmul_rn((float)in[i], r);
+}
+
+// ---- the whole of a1 for a group of images in ONE launch ------------------------------------------------------------------------------
+// grid (x, y): y = the image of the group; the first `pix_blocks` blocks of a row cover the H * W pixels of the image's batch slot,
+// one thread per pixel (the resized region with normalize_resize_pixel, the right and bottom padding as +0.0: the slot is written
+// exactly once and needs no fill), the blocks behind them the 4 * S box coordinates (rescale_boxes_kernel's arithmetic), box_doc and
+// box_off.  The descriptors travel in the kernel arguments (TB_IMAGES * 56 bytes + the scalars < 4 KB).  uint8 samples: u / 255.0f by
+// DIVISION (what torch's CPU `.float().div(255)` gives for all 256 bytes; a reciprocal multiply differs in 126 of them); a block of
+// a uint8 image first forms the 3 x 256 table of ((float)u / 255.0f - mean) / std in LDS with that arithmetic, so a tap is one LDS read
+// with the bits the expression gives.  Bytes are read one at a time: no alignment of a row is assumed and nothing outside the
+// 3 * h * w samples is touched.  No atomics.
+constexpr int TB_IMAGES = VBG_TRANSFORM_MAX_IMAGES;
+constexpr int TB_THREADS = 256;
+struct tb_image { const void* img; const long long* boxes; int fmt, h, w, oh, ow, S, row0; float rh, rw; };
+struct tb_images { tb_image im[TB_IMAGES]; };
+static_assert(sizeof(tb_images) + 128 <= 4096, "the descriptors must fit the kernel-argument block");
+
+struct tap_u8 {                 // uint8 [3,h,w] (sp = 1, sc = h * w) or dense [h,w,3] (sp = 3, sc = 1), through the LDS table
+    const unsigned char* img; long long w, sp, sc; const float* tab;
+    __device__ __forceinline__ float operator()(int c, int y, int x) const {
+        return tab[c * 256 + img[((long long)y * w + x) * sp + c * sc]];
+    }
+};
+
+__global__ __launch_bounds__(TB_THREADS) void transform_batch_kernel(tb_images g, int b0, int nimg, int pix_blocks, int H, int W, float m0,
+                                                                     float m1, float m2, float s0, float s1, float s2,
+                                                                     float* __restrict__ batch, int* __restrict__ boxes_out,
+                                                                     int* __restrict__ box_doc, int* __restrict__ box_off) {
+    __shared__ float tab[3 * 256];
+    const int j = blockIdx.y;
+    const tb_image& im = g.im[j];
+    if ((int)blockIdx.x >= pix_blocks) {                      // (block-uniform) the boxes of image j
+        const long long i = (long long)(blockIdx.x - pix_blocks) * TB_THREADS + threadIdx.x;
+        if (i < 4ll * im.S) {
+            const float r = ((i & 1) == 0) ? im.rh : im.rw;   // cols 0,2 <- height ratio; 1,3 <- width ratio (reference swap)
+            boxes_out[4ll * im.row0 + i] = (int)__fmul_rn((float)im.boxes[i], r);
+        }
+        if (i < im.S) box_doc[im.row0 + i] = b0 + j;
+        if (blockIdx.x == pix_blocks && threadIdx.x == 0 && box_off) {
+            box_off[b0 + j] = im.row0;
+            if (j == nimg - 1) box_off[b0 + nimg] = im.row0 + im.S;
+        }
+        return;
+    }
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    if (im.fmt != 0) {                                        // (block-uniform)
+        for (int k = threadIdx.x; k < 3 * 256; k += TB_THREADS) {
+            const int c = k >> 8;
+            tab[k] = ((float)(k & 255) / 255.0f - mean[c]) / sd[c];
+        }
+        __syncthreads();
+    }
+    const long long i = (long long)blockIdx.x * TB_THREADS + threadIdx.x;
+    if (i >= (long long)H * W) return;
+    const int oy = (int)(i / W), ox = (int)(i - (long long)oy * W);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (oy < im.oh && ox < im.ow) {
+        if (im.fmt == 0) {
+            const tap_f32_chw tap = {(const float*)im.img, im.h, im.w, {m0, m1, m2}, {s0, s1, s2}};
+            normalize_resize_pixel(tap, im.h, im.w, im.oh, im.ow, oy, ox, v);
+        } else {
+            const bool hwc = im.fmt == 2;
+            const tap_u8 tap = {(const unsigned char*)im.img, im.w, hwc ? 3ll : 1ll, hwc ? 1ll : (long long)im.h * im.w, tab};
+            normalize_resize_pixel(tap, im.h, im.w, im.oh, im.ow, oy, ox, v);
+        }
+    }
+    float* o = batch + (((long long)(b0 + j) * H) * W + i) * 3;
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
 }
 
 __global__ void im2col_kernel(const float* __restrict__ x, int B, int H, int W, int C, int kh, int kw, int stride, int pad,
@@ -798,6 +879,42 @@ extern "C" int vbg_rescale_boxes(const long long* in, int S, float ratio_h, floa
     if (S == 0) return VBG_OK;
     VBG_CHECK_ARG(in && out);
     VBG_LAUNCH(rescale_boxes_kernel, dim3(cdiv(S * 4, 256)), dim3(256), 0, S_, in, S * 4, ratio_h, ratio_w, out);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_transform_max_images(void) { return TB_IMAGES; }
+
+extern "C" int vbg_transform_batch(const vbg_transform_image* h_images, int B, const float* h_mean3, const float* h_std3,
+                                   float* batch_nhwc, int H, int W, int* boxes_out, int* box_doc, int* box_off, long long N,
+                                   void* stream) {
+    VBG_CHECK_ARG(B >= 0 && N >= 0);
+    if (B == 0) return VBG_OK;
+    VBG_CHECK_ARG(h_images && h_mean3 && h_std3 && batch_nhwc && H >= 1 && W >= 1);
+    for (int i = 0; i < B; ++i) {
+        const vbg_transform_image& d = h_images[i];
+        VBG_CHECK_ARG(d.img && d.h >= 1 && d.w >= 1 && d.oh >= 1 && d.ow >= 1 && d.oh <= H && d.ow <= W);
+        VBG_CHECK_ARG(d.format == VBG_IMAGE_F32_CHW || d.format == VBG_IMAGE_U8_CHW || d.format == VBG_IMAGE_U8_HWC);
+        VBG_CHECK_ARG(d.S >= 0 && d.box_row >= 0 && (long long)d.box_row + d.S <= N && (d.S == 0 || (d.boxes && boxes_out && box_doc)));
+        if (i > 0) VBG_CHECK_ARG(d.box_row == h_images[i - 1].box_row + h_images[i - 1].S);      // box_off is the running sum
+    }
+    const long long pix = (long long)H * W;
+    VBG_CHECK_ARG(cdiv(pix, TB_THREADS) < (1ll << 30));
+    const int pix_blocks = cdiv(pix, TB_THREADS);
+    for (int b0 = 0; b0 < B; b0 += TB_IMAGES) {
+        const int n = B - b0 < TB_IMAGES ? B - b0 : TB_IMAGES;
+        tb_images g;
+        int smax = 0;
+        for (int j = 0; j < TB_IMAGES; ++j) {
+            const vbg_transform_image& d = h_images[b0 + (j < n ? j : n - 1)];          // (the unused tail repeats the last one)
+            g.im[j] = tb_image{d.img, d.boxes, d.format, d.h, d.w, d.oh, d.ow, d.S, d.box_row,
+                               (float)((double)d.oh / (double)d.h), (float)((double)d.ow / (double)d.w)};
+            if (j < n && d.S > smax) smax = d.S;
+        }
+        // (>= 1 box block per image: its first thread writes box_off)
+        const int box_blocks = smax > 0 ? cdiv(4ll * smax, TB_THREADS) : 1;
+        VBG_LAUNCH(transform_batch_kernel, dim3(pix_blocks + box_blocks, n), dim3(TB_THREADS), 0, S_, g, b0, n, pix_blocks, H, W, h_mean3[0],
+                   h_mean3[1], h_mean3[2], h_std3[0], h_std3[1], h_std3[2], batch_nhwc, boxes_out, box_doc, box_off);
+    }
     VBG_LAUNCH_RET();
 }
 

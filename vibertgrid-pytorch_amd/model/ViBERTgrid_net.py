@@ -190,9 +190,8 @@ class ViBERTgridNet(nn.Module):
 
     # ---------------------------------------------------------------------------------------------
     def _trunk(self, image, seg_indices, coors, corpus, mask):
-        batch, icoors, _ = self.transform.forward_nhwc(image, coors)
+        batch, icoors, _, packed = self.transform.forward_packed(image, coors)
         B, H, W, _ = batch.shape
-        packed = BERTgridGenerator.pack_boxes(tuple(icoors))
         return batch, icoors, packed, B, H, W
 
     def _features(self, batch, packed, B, H, W, seg_indices, corpus, mask):

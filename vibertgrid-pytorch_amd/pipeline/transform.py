@@ -1,7 +1,8 @@
 """Input transform of the ViBERTgrid model — same class names, constructor and return types as the
 reference (pipeline/transform.py: `ImageList` :9-33, `GeneralizedViBERTgridTransform` :36-312), with the
 per-image normalise / bilinear resize / zero-pad-to-32 and the box rescale running as HIP kernels
-that write straight into the padded batch (no intermediate per-image tensors).
+that write straight into the padded batch (no intermediate per-image tensors): one launch for the
+whole batch (`forward_packed`), which also takes the images as uint8 bytes.
 """
 import math
 from typing import List, Tuple
@@ -67,14 +68,36 @@ class GeneralizedViBERTgridTransform(nn.Module):
         W = int(math.ceil(float(max(s[1] for s in sizes)) / 32.0) * 32)
         return sizes, H, W
 
+    def forward_packed(self, images, ocr_coors):
+        """-> (batch NHWC fp32 [B,H,W,3], list of int32 [S,4] boxes, sizes, packed).  packed = (boxes [N,4], box_off [B+1],
+        box_doc [N]), what BERTgridGenerator.pack_boxes returns for the list, or None when an image came without boxes.  Images are
+        fp32 on the 0..1 scale (ToTensor's output) or uint8 bytes, CHW or a decoded HWC array seen through `.permute(2, 0, 1)`
+        (vbg.ops.transform_input); image_mean / image_std stay on the 0..1 scale either way.  uint8 images, and fp32 ones unless
+        VBG_TRANSFORM_BATCH=0, take one launch for the whole batch (vbg.ops.transform_batch): the boxes of the list are then row
+        slices of the packed buffer."""
+        return self._forward(images, ocr_coors, True)
+
     def forward_nhwc(self, images, ocr_coors):
         """-> (batch NHWC fp32 [B,H,W,3], list of int32 [S,4] boxes, sizes)"""
+        return self._forward(images, ocr_coors, False)[:3]
+
+    def _forward(self, images, ocr_coors, want_packed):
         images, ocr_coors = list(images), list(ocr_coors)
         for image in images:
             if image.dim() != 3:
                 raise ValueError("images is expected to be a list of 3d tensors of shape [C, H, W], got {}".format(image.shape))
         shapes = [tuple(im.shape[-2:]) for im in images]
         sizes, H, W = self.plan(shapes)
+        complete = all(c is not None for c in ocr_coors)
+        if ops.transform_batch_enabled() or any(im.dtype == torch.uint8 for im in images):
+            batch, boxes, box_off, box_doc = ops.transform_batch(images, sizes, self.image_mean, self.image_std, H, W, ocr_coors)
+            out_coors, r = [], 0
+            for c in ocr_coors:
+                n = 0 if c is None else c.numel() // 4
+                out_coors.append(None if c is None else boxes[r:r + n])
+                r += n
+            return batch, out_coors, sizes, ((boxes, box_off, box_doc) if complete else None)
+        # VBG_TRANSFORM_BATCH=0: a zero fill, then one resize launch and one box launch per image, then pack_boxes
         dev = images[0].device
         batch = torch.zeros((len(images), H, W, 3), device=dev, dtype=torch.float32)
         out_coors = []
@@ -86,7 +109,11 @@ class GeneralizedViBERTgridTransform(nn.Module):
             if c is not None:
                 c = ops.rescale_boxes(c.long().contiguous(), oh / h, ow / w)     # cols 0,2 <- HEIGHT ratio (reference :167-168)
             out_coors.append(c)
-        return batch, out_coors, sizes
+        packed = None
+        if want_packed and complete:
+            from model.BERTgrid_generator import BERTgridGenerator
+            packed = BERTgridGenerator.pack_boxes(tuple(out_coors))
+        return batch, out_coors, sizes, packed
 
     def forward(self, images: Tuple[torch.Tensor], ocr_coors: Tuple[torch.Tensor]):
         batch, out_coors, sizes = self.forward_nhwc(images, ocr_coors)

@@ -22,10 +22,18 @@ def host_mirror(t: torch.Tensor):
     return getattr(t, "_vbg_host", None)
 
 
+def _dense_order(t: torch.Tensor):
+    """the axis order in which a non-contiguous tensor is contiguous (it covers its memory densely, only permuted), or None"""
+    if t.is_contiguous() or t.numel() == 0:
+        return None
+    order = sorted(range(t.dim()), key=lambda d: -t.stride(d))
+    return order if t.permute(order).is_contiguous() else None
+
+
 class PackedBatch:
     def __init__(self, buf: torch.Tensor, table, extras=()):
         self.buf = buf                  # uint8, pinned when possible
-        self.table = table              # [(group, offset, dtype, shape)]
+        self.table = table              # [(group, offset, dtype, shape)], + (strides,) for a dense permuted image
         self.extras = tuple(extras)     # whatever followed the six model arguments in the collate output (eval mode)
 
     @staticmethod
@@ -43,18 +51,29 @@ class PackedBatch:
         out = []
         for gi, o, dt, shape, t in table:
             n = t.numel() * t.element_size()
-            if n:
-                buf[o:o + n].view(dt).view(shape).copy_(t)
-            out.append((gi, o, dt, shape))
+            order = _dense_order(t) if gi == 0 else None
+            if order is None:
+                if n:
+                    buf[o:o + n].view(dt).view(shape).copy_(t)
+                out.append((gi, o, dt, shape))
+            else:
+                # a dense permuted image (a decoded HWC array seen as CHW): its bytes as they lie in memory, and the strides to
+                # rebuild the view -- no transpose on the host, and the device reads it in place (vbg.ops.transform_input)
+                src = t.permute(order)
+                buf[o:o + n].view(dt).view(tuple(src.shape)).copy_(src)
+                out.append((gi, o, dt, shape, tuple(t.stride())))
         return PackedBatch(buf, out, extras)
 
     def to(self, device, non_blocking: bool = True) -> Tuple:
         """one H2D copy -> (image_list, seg_indices, token_classes, ocr_coors, ocr_corpus, mask) on `device`"""
         dbuf = self.buf.to(device, non_blocking=non_blocking)
         groups = [[] for _ in range(6)]
-        for gi, o, dt, shape in self.table:
+        for gi, o, dt, shape, *strides in self.table:
             n = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
-            v = dbuf[o:o + n].view(dt).view(shape) if n else torch.empty(shape, dtype=dt, device=dbuf.device)
+            if strides:
+                v = torch.as_strided(dbuf[o:o + n].view(dt), shape, strides[0])
+            else:
+                v = dbuf[o:o + n].view(dt).view(shape) if n else torch.empty(shape, dtype=dt, device=dbuf.device)
             if gi in (1, 4, 5):          # seg_indices, corpus, mask: the model derives its index tables from these on the host
                 v._vbg_host = self.buf[o:o + n].view(dt).view(shape).numpy() if n else np.zeros(shape, dtype=np.int64)
             groups[gi].append(v)

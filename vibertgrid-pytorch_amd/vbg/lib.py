@@ -162,6 +162,13 @@ class TagTable(C.Structure):                 # include/vbg.h vbg_tag_table (pass
     _fields_ = [("prefix", C.c_ubyte * 64), ("type", C.c_ubyte * 64)]
 
 
+class TransformImage(C.Structure):           # include/vbg.h vbg_transform_image (an array of them, host memory)
+    _fields_ = [("img", c_vp), ("boxes", c_vp), ("format", c_int), ("h", c_int), ("w", c_int), ("oh", c_int), ("ow", c_int),
+                ("S", c_int), ("box_row", c_int)]
+
+
+TRANSFORM_MAX_IMAGES = 64                    # include/vbg.h VBG_TRANSFORM_MAX_IMAGES
+IMAGE_F32_CHW, IMAGE_U8_CHW, IMAGE_U8_HWC = 0, 1, 2
 SGD_NESTEROV, SGD_MAXIMIZE, SGD_FIRST = 1, 2, 4          # vbg_sgd_group_opt.flags
 ADAM_AMSGRAD, ADAM_MAXIMIZE, ADAM_COUPLED = 1, 2, 4      # vbg_adam_group_opt.flags
 OPTIM_MAX_GROUPS = 32                        # include/vbg.h VBG_OPTIM_MAX_GROUPS
@@ -209,6 +216,9 @@ SIGNATURES = {
     "vbg_im2col": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "vbg_normalize_resize": (c_int, [c_vp, c_int, c_int, c_int, c_int, C.POINTER(c_f), C.POINTER(c_f), c_vp, c_int, c_int, c_int, c_vp]),
     "vbg_rescale_boxes": (c_int, [c_vp, c_int, c_f, c_f, c_vp, c_vp]),
+    "vbg_transform_max_images": (c_int, []),
+    "vbg_transform_batch": (c_int, [C.POINTER(TransformImage), c_int, C.POINTER(c_f), C.POINTER(c_f), c_vp, c_int, c_int, c_vp, c_vp, c_vp,
+                                    c_ll, c_vp]),
     "vbg_embed_ln_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_ull, c_ull, c_vp, c_vp, c_vp, c_vp]),
     "vbg_embed_ln_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_f, c_ull, c_ull, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vbg_dropout_add_ln_fwd": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_f, c_f, c_ull, c_ull, c_vp, c_vp, c_vp, c_vp]),

@@ -8,7 +8,8 @@ import os
 import torch
 
 from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_DKV, ATTN_DQ, ATTN_FWD, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
-                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, TagTable, VbgError, check, lib)
+                  AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, TagTable, VbgError, check, lib,
+                  IMAGE_F32_CHW, IMAGE_U8_CHW, IMAGE_U8_HWC, TRANSFORM_MAX_IMAGES, TransformImage)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -2250,6 +2251,88 @@ def rescale_boxes(coor_i64, rh, rw):
     out = torch.empty((S, 4), device=coor_i64.device, dtype=i32)
     check(lib.vbg_rescale_boxes(P(coor_i64) if S else None, S, float(rh), float(rw), P(out) if S else None, _stream()), "vbg_rescale_boxes")
     return out
+
+
+# ---- a1 for the whole batch in one launch (vbg_transform_batch, include/vbg.h) --------------------------------------------------------
+_TRANSFORM_BATCH = [os.environ.get("VBG_TRANSFORM_BATCH", "1") != "0"]
+
+
+def set_transform_batch(on: bool):
+    """fp32 images go through vbg_transform_batch (one launch per TRANSFORM_MAX_IMAGES images: resize, padding, boxes, box tables)
+    instead of a fill, two launches per image and pack_boxes.  Same bits either way (tests/test_gpu_transform_batch.py).  uint8 images
+    always take the batched entry: they have no other route."""
+    _TRANSFORM_BATCH[0] = bool(on)
+
+
+def transform_batch_enabled() -> bool:
+    return _TRANSFORM_BATCH[0]
+
+
+def _strides_are(t, want) -> bool:
+    return all(n <= 1 or s == w_ for n, s, w_ in zip(t.shape, t.stride(), want))       # (the stride of an extent-1 axis is free)
+
+
+def transform_input(t):
+    """one image [3,h,w] -> (the tensor the kernel reads, its format).  The format is read from dtype and STRIDES (shape alone cannot
+    tell a [3,h,3] CHW image from an HWC one): fp32 contiguous 0; uint8 contiguous 1; uint8 with strides (1, 3w, 3) -- a dense HWC
+    image seen through `.permute(2, 0, 1)` -- 2, read in place.  Other strides are made contiguous and other float dtypes converted to
+    fp32 first; an integer dtype other than uint8 has no 0..1 meaning here and raises TypeError."""
+    if t.dim() != 3 or t.shape[0] != 3:
+        raise ValueError(f"transform_batch: an image is [3, h, w], got {tuple(t.shape)}")
+    _, h, w = t.shape
+    if t.dtype == torch.uint8:
+        if t.is_contiguous():
+            return t, IMAGE_U8_CHW
+        if _strides_are(t, (1, 3 * w, 3)):
+            return t, IMAGE_U8_HWC
+        return t.contiguous(), IMAGE_U8_CHW
+    if not t.is_floating_point():
+        raise TypeError(f"transform_batch: images are floating point on the 0..1 scale or uint8 bytes, got {t.dtype}")
+    t = t.to(f32)
+    return (t if t.is_contiguous() else t.contiguous()), IMAGE_F32_CHW
+
+
+def transform_table(images, sizes, coors):
+    """host side of transform_batch, no device work: -> (TransformImage array [B], the tensors it points into, box counts).  Image b's
+    boxes start at row sum(counts[:b]) of the packed output; a `None` entry of coors is an image without boxes (S = 0)."""
+    B = len(images)
+    descs = (TransformImage * max(B, 1))()
+    keep, counts, row = [], [], 0
+    for b in range(B):
+        im, fmt = transform_input(images[b])
+        c = coors[b]
+        if c is not None:
+            c = c.reshape(-1, 4).long().contiguous()
+        S = 0 if c is None else int(c.shape[0])
+        oh, ow = sizes[b]
+        d = descs[b]
+        d.img, d.boxes = im.data_ptr(), (c.data_ptr() if S else None)
+        d.format, d.h, d.w, d.oh, d.ow, d.S, d.box_row = fmt, int(im.shape[1]), int(im.shape[2]), int(oh), int(ow), S, row
+        keep += [im, c]
+        counts.append(S)
+        row += S
+    return descs, keep, counts
+
+
+def transform_batch(images, sizes, mean, std, H, W, coors, out=None):
+    """images: B device tensors [3,h,w] (fp32 0..1, uint8 CHW, or uint8 HWC seen through permute(2, 0, 1): transform_input);
+    sizes: their resized (oh, ow); coors: B int64 [S,4] box tensors (None: no boxes) -> (batch NHWC fp32 [B,H,W,3], boxes int32 [N,4],
+    box_off int32 [B+1], box_doc int32 [N]) in ceil(B / TRANSFORM_MAX_IMAGES) launches.  Padding and tables are written by the
+    kernel: nothing is filled, nothing is uploaded.  out: the batch buffer to write (any contents), else a new one."""
+    B = len(images)
+    dev = images[0].device
+    descs, keep, counts = transform_table(images, sizes, coors)
+    for t in keep:
+        assert t is None or (t.is_cuda and t.device == dev), "libvbg operates on device memory only"
+    N = sum(counts)
+    batch = torch.empty((B, H, W, 3), device=dev, dtype=f32) if out is None else out
+    assert batch.shape == (B, H, W, 3) and batch.dtype == f32 and batch.is_contiguous() and batch.device == dev
+    tab =torch.empty(5 * N + B + 1, device=dev, dtype=i32)
+    boxes, box_doc, box_off = tab[:4 * N].view(N, 4), tab[4 * N:5 * N], tab[5 * N:]
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s = (C.c_float * 3)(*[float(v) for v in std])
+    check(lib.vbg_transform_batch(descs, B, m, s, P(batch), H, W, P(boxes), P(box_doc), P(box_off), N, _stream()), "vbg_transform_batch")
+    return batch, boxes, box_off, box_doc
 
 
 # ----------------------------------------------------------------------------------------------

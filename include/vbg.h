@@ -920,6 +920,25 @@ int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, float* vmax, 
  *   the elements, not from the sums: finite gradients whose squares overflow leave an inf partial and no flag. */
 int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunks, int nchunks, const float* inv_scale, float* found_inf, void* stream);
 int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, void* stream);
+/* The norm pass and the finish above for norm types 2, 1 and inf, with the reference's loss gate (`if train_loss > loss_clip_tresh:`,
+ * pipeline/train_val_utils.py:281) taken on the device: vbg.optim.clip_in_step(norm_type=..., when=(loss, threshold)).
+ * kind: 2 (L2), 1 (L1) or 0 (inf norm).  The gate: gate_loss is a device scalar, fp64 when gate_f64 == 1 (8-byte aligned), fp32 when
+ * gate_f64 == 0 (4-byte aligned); it is open when *gate_loss > gate_threshold, compared in that dtype -- fp32 against
+ * (float)gate_threshold, which is what torch compares an fp32 tensor with; strictly greater: a NaN loss closes it, +inf opens it.
+ * gate_loss NULL: no gate.  The loss is read by the kernels (one load, uniform over the launch), never by the host.
+ * vbg_grad_norm_seg: table, alignment contract and row walk of vbg_grad_sumsq_seg; a plain store per row.  kind 2: partials[c] as
+ *   vbg_grad_sumsq_seg leaves it, bit for bit.  kind 1: partials[c] = sum of |g| over row c, summed the same way (per thread over its
+ *   float4s, then over the block, in fp32).  kind 0: partials[c] = max |g| of row c, exact; a NaN anywhere in the row gives a NaN,
+ *   +-inf gives +inf.  found_inf (optional, 4-byte aligned): the per-element test of vbg_grad_sumsq_seg_inf, for any kind.  With a gate
+ *   that is closed and found_inf NULL every block returns before it touches g or partials; with found_inf the rows always walk.
+ * vbg_clip_coef_gate: one block.  Gate closed: out = (0, 1, 0) and no partial is read.  Otherwise total = (float)sqrt(sum in double)
+ *   (kind 2), (float)(sum in double) (kind 1) or the maximum of the partials with a NaN kept (kind 0), then the statements of
+ *   vbg_clip_coef (norm_scale, the inverse grad_scale, the coefficient), and out = (total, coefficient, 1).  n == 0: (0, 1, gate).
+ *   out: 3 floats of device memory; out + 1 is what the *_seg_clip entries take. */
+int vbg_grad_norm_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, int kind, float* found_inf,
+                      const void* gate_loss, int gate_f64, double gate_threshold, void* stream);
+int vbg_clip_coef_gate(const float* partials, int n, int kind, float max_norm, float norm_scale, const float* grad_scale,
+                       const void* gate_loss, int gate_f64, double gate_threshold, float* out, void* stream);
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);

@@ -12,7 +12,8 @@
 // instantiation with one more device scalar, the coefficient of a gradient-norm clip that vbg_grad_sumsq_seg (per-row sums of squares
 // over the same chunk table) and vbg_clip_coef (their sum in double, torch's coefficient) leave in device memory.  The same row walk
 // carries GradScaler's own pass over the gradients: vbg_grad_unscale_check_seg (its inf check and unscale_) and vbg_grad_sumsq_seg_inf
-// (the norm pass with that check riding along).
+// (the norm pass with that check riding along).  vbg_grad_norm_seg / vbg_clip_coef_gate are the norm pass and its finish for norm types
+// 2, 1 and inf with the reference's loss gate (`if train_loss > loss_clip_tresh`) read from device memory by the kernels themselves.
 #include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
@@ -373,6 +374,133 @@ __global__ void __launch_bounds__(COEF_THREADS) clip_coef_kernel(const float* __
     }
 }
 
+// ---- the loss gate and the other norm types (vbg_grad_norm_seg / vbg_clip_coef_gate) ------------------------------------
+// The reference clips only `if train_loss > loss_clip_tresh` (pipeline/train_val_utils.py:281), a host read of a device scalar.  Here
+// the loss stays where it is: both kernels read it (one load, uniform over the launch) and take torch's own decision, `loss > threshold`
+// in the loss tensor's dtype -- strictly greater, so a NaN loss closes the gate and +inf opens it; thr32 is the threshold rounded to
+// fp32 on the host, which is what torch compares an fp32 tensor with.  loss NULL: no gate.
+struct ClipGate { const void* loss; double thr64; float thr32; int f64; };
+
+__device__ __forceinline__ bool gate_open(const ClipGate& gt) {
+    if (!gt.loss) return true;
+    return gt.f64 ? *reinterpret_cast<const double*>(gt.loss) > gt.thr64 : *reinterpret_cast<const float*>(gt.loss) > gt.thr32;
+}
+
+// max over the block of |x| carried as its bit pattern: as unsigned integers finite < inf < NaN, so one integer max is exact, turns
+// +-inf into +inf and keeps a NaN (fmaxf alone drops it).  `sh` has >= 16 words; result broadcast.
+__device__ __forceinline__ unsigned block_max_bits(unsigned v, unsigned* sh) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
+        v = u > v ? u : v;
+    }
+    __syncthreads();
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    unsigned r = sh[0];
+    for (int i = 1; i < nw; ++i) r = sh[i] > r ? sh[i] : r;
+    return r;
+}
+
+__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+
+// The row pass of grad_sumsq_seg_kernel for the three norm types: KIND 2 sums squares in its very statements (the same partials, bit
+// for bit), KIND 1 sums |g| the same way (fabsf rounds nothing), KIND 0 leaves max |g| of the row.  A plain store per row, no atomics.
+// Without CHECK a closed gate makes every block return before it touches g or partials; with CHECK (GradScaler's flag rides in the
+// loop) the rows always walk and only the finish reads the gate.
+template <int KIND, bool CHECK>
+__global__ void __launch_bounds__(SEG_THREADS) grad_norm_seg_kernel(const float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
+                                                                     float* __restrict__ partials, float* __restrict__ found_inf, ClipGate gate) {
+    __shared__ float sh[16];
+    if constexpr (!CHECK) if (!gate_open(gate)) return;
+    int c = blockIdx.x;
+    float z = 0.f;
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
+        const int n4 = ch.length >> 2;
+        float acc = 0.f;
+        unsigned mx = 0u;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+        for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+            const float4 gv = g4[i];
+            if constexpr (CHECK) fold_finite4(z, gv);
+            if constexpr (KIND == 2) {
+                acc += gv.x * gv.x;
+                acc += gv.y * gv.y;
+                acc += gv.z * gv.z;
+                acc += gv.w * gv.w;
+            } else if constexpr (KIND == 1) {
+                acc += fabsf(gv.x);
+                acc += fabsf(gv.y);
+                acc += fabsf(gv.z);
+                acc += fabsf(gv.w);
+            } else {
+                const unsigned a = abs_bits(gv.x), b = abs_bits(gv.y), c2 = abs_bits(gv.z), d = abs_bits(gv.w);
+                const unsigned ab = a > b ? a : b, cd = c2 > d ? c2 : d;
+                const unsigned m4 = ab > cd ? ab : cd;
+                mx = m4 > mx ? m4 : mx;
+            }
+        }
+        float r;
+        if constexpr (KIND == 0) r = __uint_as_float(block_max_bits(mx, reinterpret_cast<unsigned*>(sh)));
+        else r = block_sum(acc, sh);
+        if (threadIdx.x == 0) partials[c] = r;
+        c += (int)gridDim.x;
+    });
+    if constexpr (CHECK) raise_found_inf(!(z == 0.f), found_inf);
+}
+
+// The finish of clip_coef_kernel for the three norm types and the gate: KIND 2 and 1 sum the partials in double in its fixed order
+// (then sqrt for 2), KIND 0 takes their maximum with a NaN kept; the statements after that are clip_coef_kernel's.  Three floats:
+// out[0] = total, out[1] = coefficient, out[2] = 1.0f (gate open, or no gate) / 0.0f.  A closed gate leaves (0, 1, 0) and reads no partial.
+template <int KIND>
+__global__ void __launch_bounds__(COEF_THREADS) clip_coef_gate_kernel(const float* __restrict__ partials, int n, float max_norm, float norm_scale,
+                                                                       const float* __restrict__ grad_scale, ClipGate gate, float* __restrict__ out) {
+    __shared__ double sh[COEF_THREADS];
+    if (!gate_open(gate)) {
+        if (threadIdx.x == 0) {
+            out[0] = 0.f;
+            out[1] = 1.f;
+            out[2] = 0.f;
+        }
+        return;
+    }
+    double s = 0.0;
+    bool bad = false;
+    for (int i = threadIdx.x; i < n; i += COEF_THREADS) {
+        const float p = partials[i];
+        if constexpr (KIND == 0) {
+            bad = bad || p != p;
+            s = fmax(s, (double)p);
+        } else {
+            s += (double)p;
+        }
+    }
+    if constexpr (KIND == 0) bad = __syncthreads_or(bad);
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = COEF_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            if constexpr (KIND == 0) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + o]);
+            else sh[threadIdx.x] += sh[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        float root;
+        if constexpr (KIND == 2) root = (float)sqrt(sh[0]);
+        else if constexpr (KIND == 1) root = (float)sh[0];
+        else root = bad ? __uint_as_float(0x7fc00000u) : (float)sh[0];
+        float total = __fmul_rn(root, norm_scale);
+        if (grad_scale) total = __fmul_rn(total, (float)(1.0 / (double)*grad_scale));          // (the gradients still hold scaled values)
+        const float c = __fmul_rn(__fdiv_rn(1.f, __fadd_rn(total, 1e-6f)), max_norm);
+        out[0] = total;
+        out[1] = c > 1.f ? 1.f : c;
+        out[2] = 1.f;
+    }
+}
+
 static inline int ew_grid(long long n, int block) {
     long long g = (n + block - 1) / block;
     if (g > 256 * 8) g = 256 * 8;
@@ -577,5 +705,48 @@ extern "C" int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunk
 extern "C" int vbg_clip_coef(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, float* out, void* stream) {
     VBG_CHECK_ARG(n >= 0 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 && (uintptr_t)grad_scale % 4 == 0);
     VBG_LAUNCH(clip_coef_kernel, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, out);
+    VBG_LAUNCH_RET();
+}
+
+// The row pass and the finish for norm types 2, 1 and inf (kind 2 / 1 / 0) with the loss gate of clip_in_step(when=...): gate_loss is a
+// device scalar (fp64 when gate_f64, fp32 otherwise; NULL: no gate), the gate is open when *gate_loss > gate_threshold in that dtype.
+// found_inf is optional here (NULL: no check); with it the rows walk whatever the gate says.
+static inline bool gate_args(const void* loss, int f64) { return (f64 == 0 || f64 == 1) && (uintptr_t)loss % (f64 ? 8 : 4) == 0; }
+static inline ClipGate make_gate(const void* loss, int f64, double threshold) { return ClipGate{loss, threshold, (float)threshold, f64}; }
+
+template <int KIND>
+static int grad_norm_seg_launch(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, ClipGate gate,
+                                void* stream) {
+    if (found_inf)
+        VBG_LAUNCH((grad_norm_seg_kernel<KIND, true>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
+                   partials, found_inf, gate);
+    else
+        VBG_LAUNCH((grad_norm_seg_kernel<KIND, false>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
+                   partials, found_inf, gate);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_grad_norm_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, int kind, float* found_inf,
+                                 const void* gate_loss, int gate_f64, double gate_threshold, void* stream) {
+    VBG_CHECK_ARG(nchunks >= 0 && kind >= 0 && kind <= 2 && (uintptr_t)found_inf % 4 == 0 && gate_args(gate_loss, gate_f64));
+    if (nchunks == 0) return VBG_OK;
+    VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
+    const ClipGate gate = make_gate(gate_loss, gate_f64, gate_threshold);
+    if (kind == 2) return grad_norm_seg_launch<2>(g, chunks, nchunks, partials, found_inf, gate, stream);
+    if (kind == 1) return grad_norm_seg_launch<1>(g, chunks, nchunks, partials, found_inf, gate, stream);
+    return grad_norm_seg_launch<0>(g, chunks, nchunks, partials, found_inf, gate, stream);
+}
+
+extern "C" int vbg_clip_coef_gate(const float* partials, int n, int kind, float max_norm, float norm_scale, const float* grad_scale,
+                                  const void* gate_loss, int gate_f64, double gate_threshold, float* out, void* stream) {
+    VBG_CHECK_ARG(n >= 0 && kind >= 0 && kind <= 2 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 &&
+                  (uintptr_t)grad_scale % 4 == 0 && gate_args(gate_loss, gate_f64));
+    const ClipGate gate = make_gate(gate_loss, gate_f64, gate_threshold);
+    if (kind == 2)
+        VBG_LAUNCH(clip_coef_gate_kernel<2>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
+    else if (kind == 1)
+        VBG_LAUNCH(clip_coef_gate_kernel<1>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
+    else
+        VBG_LAUNCH(clip_coef_gate_kernel<0>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
     VBG_LAUNCH_RET();
 }

@@ -299,6 +299,8 @@ SIGNATURES = {
     "vbg_adam_step_seg_clip": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamGroupOpt), c_int, c_vp, c_vp, c_vp, c_f, c_vp]),
     "vbg_grad_unscale_check_seg": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "vbg_grad_sumsq_seg_inf": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "vbg_grad_norm_seg": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_d, c_vp]),
+    "vbg_clip_coef_gate": (c_int, [c_vp, c_int, c_int, c_f, c_f, c_vp, c_vp, c_int, c_d, c_vp, c_vp]),
     "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
     "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_sum_det_ws_elems": (c_int, []),

@@ -2843,6 +2843,76 @@ def clip_coef(partials, n, max_norm, norm_scale=1.0, grad_scale=None, out=None):
     return out
 
 
+NORM_KINDS = (2, 1, 0)          # the `kind` of vbg_grad_norm_seg / vbg_clip_coef_gate: L2, L1, inf norm
+
+
+def _gate_args(gate, device, what):
+    """(loss, fp64 flag, threshold) of a checked loss gate `(loss, threshold)` -- loss: one fp64 or fp32 element on `device`, only ever read
+    by the kernels; threshold: a Python number -- or (None, 0, 0.0) for no gate"""
+    if gate is None:
+        return None, 0, 0.0
+    if not isinstance(gate, tuple) or len(gate) != 2:
+        raise TypeError(f"{what}: the gate is a pair (loss tensor, threshold)")
+    loss, threshold = gate
+    if not isinstance(loss, torch.Tensor):
+        raise TypeError(f"{what}: the gate's loss must be a tensor, not {type(loss).__name__}")
+    if loss.dtype not in (torch.float64, f32):
+        raise TypeError(f"{what}: the gate's loss must be fp64 or fp32, not {loss.dtype}")
+    if loss.numel() != 1 or loss.device != device:
+        raise ValueError(f"{what}: the gate's loss must be one element on the buffers' device ({device})")
+    if isinstance(threshold, (bool, torch.Tensor)) or not isinstance(threshold, (int, float)):
+        raise TypeError(f"{what}: the gate's threshold must be a Python number")
+    return loss, int(loss.dtype == torch.float64), float(threshold)
+
+
+def _device_memory(what, *tensors):
+    """the last check of a wrapper before its pointers leave Python: host tensors are refused with an exception (P()'s `assert` is gone
+    under `python -O`, and a kernel launched on host pointers faults the GPU)"""
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise TypeError(f"{what}: libvbg operates on device memory only, got a tensor on {t.device}")
+
+
+def grad_norm_seg(g, table, partials, kind=2, found_inf=None, gate=None):
+    """vbg_grad_norm_seg: the row pass of grad_sumsq_seg for kind 2 (sums of squares, the same bits), 1 (sums of |g|) or 0 (max |g|, a NaN
+    kept); found_inf: GradScaler's flag as in grad_sumsq_seg_inf, optional; gate: (loss, threshold) -- a closed gate (not loss > threshold,
+    decided on the device) without found_inf makes the launch return before it touches g or partials"""
+    if kind not in NORM_KINDS:
+        raise ValueError("segmented gradient norm: kind is 2 (L2), 1 (L1) or 0 (inf norm)")
+    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
+        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
+    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
+        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
+    if found_inf is not None:
+        _scaler_scalars(table, found_inf=found_inf)
+    loss, f64, thr = _gate_args(gate, table.rows.device, "segmented gradient norm")
+    _device_memory("segmented gradient norm", g, table.rows, partials, found_inf, loss)
+    check(lib.vbg_grad_norm_seg(P(g), P(table.rows), table.n, P(partials), int(kind), None if found_inf is None else P(found_inf), P(loss), f64, thr,
+                                _stream()), "vbg_grad_norm_seg")
+    return partials
+
+
+def clip_coef_gate(partials, n, max_norm, norm_scale=1.0, grad_scale=None, kind=2, gate=None, out=None):
+    """vbg_clip_coef_gate: -> out (3 fp32: total norm, clip coefficient, gate 1.0 open / 0.0 closed) from partials[0 .. n) of kind 2, 1 or 0;
+    a closed gate leaves (0, 1, 0) and reads no partial.  One small launch, no host sync"""
+    if kind not in NORM_KINDS:
+        raise ValueError("clip coefficient: kind is 2 (L2), 1 (L1) or 0 (inf norm)")
+    if partials.dtype != f32 or not partials.is_contiguous() or not 0 <= n <= partials.numel():
+        raise ValueError("clip coefficient: partials must be contiguous fp32 with at least n elements")
+    if out is None:
+        out = torch.empty((3,), device=partials.device, dtype=f32)
+    if out.dtype != f32 or not out.is_contiguous() or out.numel() < 3 or out.device != partials.device:
+        raise ValueError("clip coefficient: out must be three contiguous fp32 elements on the partials' device")
+    if grad_scale is not None and (not isinstance(grad_scale, torch.Tensor) or grad_scale.dtype != f32 or grad_scale.numel() != 1
+                                   or grad_scale.device != partials.device):
+        raise ValueError("clip coefficient: grad_scale must be one fp32 element on the partials' device")
+    loss, f64, thr = _gate_args(gate, partials.device, "clip coefficient")
+    _device_memory("clip coefficient", partials, out, grad_scale, loss)
+    check(lib.vbg_clip_coef_gate(P(partials), int(n), int(kind), float(max_norm), float(norm_scale), None if grad_scale is None else P(grad_scale),
+                                 P(loss), f64, thr, P(out), _stream()), "vbg_clip_coef_gate")
+    return out
+
+
 def sgd_step_seg_clip(p, g, mom, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0, keep_mom=False):
     """vbg_sgd_step_seg_clip: sgd_step_seg_amp with the clip coefficient (a device scalar, required) applied to g after the unscale;
     found_inf may be None (no scaler); host_scale: the host float of sgd_step_seg_opt; keep_mom: momentum-0 groups write `mom` as in

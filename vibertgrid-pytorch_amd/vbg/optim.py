@@ -1107,8 +1107,31 @@ def clip_grad_norm_(optimizers, max_norm: float, norm_scale: float = 1.0) -> flo
 _CLIP_PARTIALS = {}          # device -> the partials buffer clip_in_step's norm launches share (grown, never shrunk)
 
 
-def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=None) -> torch.Tensor:
-    """torch.nn.utils.clip_grad_norm_ (norm type 2) folded into the optimizer step, with no host sync and no pass of its own over the
+_NORM_KINDS = {2.0: 2, 1.0: 1, float("inf"): 0}          # norm_type -> the `kind` of vbg_grad_norm_seg / vbg_clip_coef_gate
+
+
+def _clip_gate(when, dev):
+    """clip_in_step's `when`: None, or (loss, threshold) checked here -- the loss is handed on as it is and never read on the host"""
+    if when is None:
+        return None
+    if not isinstance(when, (tuple, list)) or len(when) != 2:
+        raise TypeError("clip_in_step: when=(loss, threshold) -- a one-element device tensor and a Python number")
+    loss, threshold = when
+    if not isinstance(loss, torch.Tensor):
+        raise TypeError(f"clip_in_step: the gate's loss must be a tensor, not {type(loss).__name__}")
+    if loss.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"clip_in_step: the gate's loss must be fp64 or fp32, not {loss.dtype}")
+    if loss.numel() != 1:
+        raise ValueError(f"clip_in_step: the gate's loss must have one element, not {loss.numel()}")
+    if loss.device != dev:
+        raise ValueError(f"clip_in_step: the gate's loss lives on {loss.device}, the flat gradient buffers on {dev}")
+    if isinstance(threshold, (bool, torch.Tensor)) or not isinstance(threshold, (int, float)):
+        raise TypeError("clip_in_step: the gate's threshold must be a Python number")
+    return (loss.detach(), threshold)
+
+
+def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=None, norm_type=2.0, when=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (norm type 2, 1 or inf) folded into the optimizer step, with no host sync and no pass of its own over the
     gradients beyond the norm: one `vbg_grad_sumsq_seg` launch per optimizer over its chunk table, one `vbg_clip_coef`, and the
     coefficient stays in device memory, pending on every listed optimizer until its next `step()` (or `scaler.step(optimizer)`), whose
     launch multiplies the gradients by it -- stored back to `.grad`, as torch leaves them -- right before the rule reads them
@@ -1128,10 +1151,33 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
     A step that falls back to torch's own (fuse(): a closure, ...) multiplies the present gradients by the coefficient first
     (`torch._foreach_mul_`); a step skipped by found_inf consumes the coefficient; `zero_grad()` before the step drops it; a second call
     while one is pending raises.  (A GradScaler that finds an inf never calls step() on an optimizer fused without amp_scaling: the
-    coefficient then waits for the loop's zero_grad().)"""
+    coefficient then waits for the loop's zero_grad().)
+
+    norm_type: 2, 1 or float("inf") (int or float), as torch.nn.utils.clip_grad_norm_(..., norm_type=...) defines them; anything else
+    raises ValueError.  `error_if_nonfinite` is not offered: raising on the host is a host read of the norm by definition.
+
+    when=(loss, threshold): the reference's `if train_loss > loss_clip_tresh:` around its clip (pipeline/train_val_utils.py:281), decided
+    on the device.  loss: a one-element fp64 or fp32 tensor on the flat buffers' device (what ViBERTgridNet.forward returns, detached);
+    it is only read by the two launches, never synchronised with.  threshold: a Python number.  The decision is torch's own
+    `loss > threshold` in the loss tensor's dtype: strictly greater, a NaN loss closes the gate, +inf opens it.  Gate open: exactly the
+    call without `when`.  Gate closed: the pending coefficient is exactly 1.0 (the next step() is the unclipped step bit for bit and
+    leaves `.grad` unwritten), the returned total is 0.0 -- the reference computes no norm then either -- and the norm launches return
+    before they read a gradient; with a fuse_scaler() scaler they still walk the rows, for the scaler's inf flag.
+
+        vbg.optim.clip_in_step([optimizer_cnn, optimizer_bert], clip_norm, when=(train_loss.detach(), loss_clip_tresh))
+
+    Several ranks: the gate reads the tensor it is given and nothing else.  Where every rank must take the same decision, hand in a loss
+    that was all-reduced with MAX on the device queue (`dist.all_reduce(loss, op=dist.ReduceOp.MAX)` on the NCCL/RCCL group): every
+    rank then compares the same number.  clip_in_step itself runs no collective.
+
+    A call with norm_type 2 and no `when` issues `vbg_grad_sumsq_seg[_inf]` and `vbg_clip_coef` as before; any other call issues
+    `vbg_grad_norm_seg` once per optimizer and one `vbg_clip_coef_gate`."""
     optimizers = list(optimizers)
     if not optimizers:
         raise ValueError("clip_in_step: no optimizers")
+    kind = _NORM_KINDS.get(float(norm_type)) if isinstance(norm_type, (int, float)) and not isinstance(norm_type, bool) else None
+    if kind is None:
+        raise ValueError(f"clip_in_step: norm_type is 2, 1 or float('inf'), not {norm_type!r}")
     work = []
     for o in optimizers:
         if not isinstance(o, (_FlatOptimizer, _FusedStock)):
@@ -1160,6 +1206,7 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
         grad_scale = scaler._scale
         if grad_scale is None:
             raise RuntimeError("clip_in_step(scaler=...): the scaler has not scaled a loss yet")
+    gate = _clip_gate(when, dev)
     n = sum(t.n for _, _, t in work)
     partials = _CLIP_PARTIALS.get(dev)
     if partials is None or partials.numel() < n:
@@ -1168,14 +1215,20 @@ def clip_in_step(optimizers, max_norm: float, norm_scale: float = 1.0, scaler=No
     # would skip an optimizer whose own gradients are finite), fresh for this call
     flags = torch.zeros((len(work),), device=dev, dtype=torch.float32).unbind(0) if grad_scale is not None and isinstance(scaler, _FusedScaler) else None
     at = 0
+    plain = kind == 2 and gate is None          # the L2 entries without a gate: vbg_grad_sumsq_seg[_inf] / vbg_clip_coef
     for j, (_, g, t) in enumerate(work):
-        if flags is None:
+        if not plain:
+            ops.grad_norm_seg(g.gflat, t, partials[at:at + t.n], kind, None if flags is None else flags[j], gate)
+        elif flags is None:
             ops.grad_sumsq_seg(g.gflat, t, partials[at:at + t.n])
         else:
             ops.grad_sumsq_seg_inf(g.gflat, t, partials[at:at + t.n], flags[j])
         at += t.n
-    out = ops.clip_coef(partials, n, max_norm, norm_scale, grad_scale)
-    coef = out[1:]
+    if plain:
+        out = ops.clip_coef(partials, n, max_norm, norm_scale, grad_scale)
+    else:
+        out = ops.clip_coef_gate(partials, n, max_norm, norm_scale, grad_scale, kind, gate)
+    coef = out[1:2]
     for o in optimizers:
         o._vbg_clip = coef
     if flags is not None:

@@ -730,6 +730,20 @@ int vbg_crf_nll_bwd(const float* emissions, const int* tags, const int* doc_off,
                     float* dtrans_accum, void* stream);
 int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                     int stop_tag, int* backptr, int* path, float* score, void* stream);
+/* Posterior of the same CRF, for the prediction path of the crf mode (reference model/field_type_classification_head.py:690-716
+ * returns the Viterbi tags and no score): ONE launch gives, for all documents,
+ *   path int32 [N], score [ndoc]   vbg_crf_viterbi's, bit for bit (the same additions, the same first maximum);
+ *   logz [ndoc]                    log Z of model/crf.py:48-79;
+ *   marginals [N, ntag]            p(y_t = i | x) = d logZ / d emissions[t, i]: a forward and a backward recursion in log space, both
+ *                                  re-centred at every step (the maximum of the previous vector is taken out of the step's result and
+ *                                  carried into logz in double), each row divided by its own sum at the end -- the error does not grow with
+ *                                  the document's length (vbg_crf_nll_bwd keeps alpha and beta unnormalised: DESIGN.md, section 8).  The
+ *                                  START and STOP columns are exact zeros (expf underflows on the -10000 entries).
+ * ws: workspace of 2 * N * ntag 4-byte words (per row: ntag fp32 forward values, ntag int32 back pointers), contents undefined
+ * afterwards.  An empty document writes score and logz (vbg_crf_viterbi's / vbg_crf_nll_fwd's values) and touches no row.  No
+ * atomics: the same bits with and without the deterministic mode.  Emissions holding NaN or infinities are outside the contract. */
+int vbg_crf_posterior(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
+                      int stop_tag, void* ws, int* path, float* score, float* logz, float* marginals, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Field decoding of the returned class scores (csrc/decode.hip).  Replaces the per-segment loop every caller of the reference runs
@@ -753,6 +767,23 @@ int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const 
 typedef struct vbg_decode_rec { int start; int len; double mean; } vbg_decode_rec;      /* 16 bytes */
 int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls, float* score,
                      vbg_decode_rec* best, void* stream);
+/* The same table from the crf mode's outputs (vbg_crf_posterior's marginals [N, ntag] and path [N]) -- the loop above never had a
+ * crf form: the reference's scripts allow only seqeval with the crf classifier, and its deployment loops read a [N, 1] tag column as
+ * class 0 everywhere.  ONE launch, same row ranges, same vbg_decode_rec table [ndoc, C].  h_tag_class / h_tag_begin: HOST tables of ntag
+ * ints, copied into the kernel arguments: tag -> class in [0, C), and 1 where the tag opens a new run even behind a row of its class.
+ *   per row   c = tag_class[path[i]]; score[i] = the class posterior: the fp32 sum, in increasing tag order, of marginals[i, k] over the
+ *             tags k with tag_class[k] == c; use_thresh != 0 and (double)score[i] < thresh: c = 0 (the score stays); cls[i] = c.
+ *             A path entry outside [0, ntag) gives class 0 and score 0.
+ *   runs      maximal stretches of equal cls; a row whose tag has tag_begin set starts a new run whatever its (thresholded) class;
+ *   mean      every score enters as the integer rint((double)score * 2^30), added in 64 bits: mean = (double)sum / 2^30 / len, rounded
+ *             once -- the same bits for any grouping of the additions (fewer than 2^20 rows per document);
+ *   filing    EVERY run under its own class (the last-run quirk above belongs to a loop the crf mode never had);
+ *   best      per class the largest mean, then the earliest start.  A run whose integer sum is 0 leaves no record.
+ * Argument errors: ntag or C outside [1, 64], a class outside [0, C), a begin flag other than 0 / 1, 2^20 rows or more in a document,
+ * NULL tables.  No atomics on global memory: deterministic.  ndoc == 0 is a no-op. */
+int vbg_field_decode_tags(const float* marginals, const int* path, const int* h_doc_off, int ndoc, int ntag, int C,
+                          const int* h_tag_class, const int* h_tag_begin, int use_thresh, double thresh, int* cls, float* score,
+                          vbg_decode_rec* best, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Validation counts of `validate` (csrc/metrics.hip): what pipeline/criteria.py's token_F1_criteria, token_classification_criteria and

@@ -156,6 +156,227 @@ __global__ __launch_bounds__(64) void crf_viterbi_kernel(const float* __restrict
     }
 }
 
+// Posterior marginals + Viterbi + log Z in one launch (vbg_crf_posterior): one wave per document, lane i owns tag i.
+//
+// The grid is a handful of waves and the time is the serial chain, rows x work per step, so the kernel is shaped by what sits on it:
+//   transitions  lane i keeps ITS row (forward, Viterbi) and later its column (backward) in registers: tw[], ntag rounded up to a
+//                template size NTP, the tail filled with -inf (a term that never wins a maximum and adds exp(-inf) == 0 to a sum);
+//   vectors      the previous step's vector lies in LDS (two buffers, one barrier per step) and the lanes read it at the same
+//                addresses -- a broadcast, no bank conflict -- four values to a read;
+//   lanes        up to 32 tags, two lanes share a tag: each walks half of the previous tags, and one exchange across the halves per
+//                step joins the two partial sums (and the two Viterbi candidates, the lower half winning ties: the first maximum);
+//   emissions    loaded one step ahead, as are the forward vector and the back pointers in the backward pass;
+//   back trace   walked inside the backward pass, from the row of back pointers that pass has already fetched: no chain of
+//                dependent global loads behind the recursions.
+// Forward and backward run in log space and are re-centred at every step: the maximum of the previous vector -- which the lanes
+// have in hand from the broadcast read, so no reduction over the tags -- is taken out of the step's result, and the forward pass
+// carries these maxima into log Z in double.  The magnitudes stay at (emission + transition + log ntag) whatever the length.
+// Position t's marginals are exp(a_t + b_t - max) / sum: 64 rows of a_t + b_t are gathered in an LDS tile (odd row stride), then one
+// lane per row takes maximum and sum in tag order and the tile goes out in whole rows.
+// The Viterbi chain repeats crf_viterbi_kernel's arithmetic on the unnormalised values: prev[j] + tr[i][j], first maximum, + em.
+constexpr int CRF_TILE_ROWS = 64;
+constexpr int CRF_TILE_STRIDE = CRF_MAX_TAGS + 1;
+
+// log-sum-exp over JW terms v[j] + w[j], as (max, sum of exp(. - max)), with the maximum of v alone on the side.  A slice that holds
+// only -inf terms gives (CRF_LOW, 0): a finite stand-in for its maximum keeps -inf - max from being NaN.
+constexpr float CRF_LOW = -3.0e38f;
+
+template <int JW>
+__device__ __forceinline__ void lse_slice(const float* __restrict__ v, const float (&w)[JW], float& mx_v, float& m2, float& s) {
+    float pr[JW];
+    mx_v = -INFINITY;
+    m2 = CRF_LOW;
+#pragma unroll
+    for (int j = 0; j < JW; j += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(v + j);
+        mx_v = fmaxf(fmaxf(mx_v, q.x), fmaxf(q.y, fmaxf(q.z, q.w)));
+        pr[j] = q.x + w[j]; pr[j + 1] = q.y + w[j + 1]; pr[j + 2] = q.z + w[j + 2]; pr[j + 3] = q.w + w[j + 3];
+        m2 = fmaxf(fmaxf(m2, pr[j]), fmaxf(pr[j + 1], fmaxf(pr[j + 2], pr[j + 3])));
+    }
+    s = 0.f;
+#pragma unroll
+    for (int j = 0; j < JW; ++j) s += __expf(pr[j] - m2);
+}
+
+// HALF: two lanes per tag (ntag <= 32).  Lane l and lane l + 32 own tag l; each walks one half of the previous tags and the two
+// exchange their partial results once per step and chain (one cross-half shuffle each way) -- half the instructions on the chain.
+template <bool HALF>
+__device__ __forceinline__ void lse_join(float& mx_v, float& m2, float& s) {
+    if (HALF) {
+        const float mo = __shfl_xor(mx_v, 32, 64), m2o = __shfl_xor(m2, 32, 64), so = __shfl_xor(s, 32, 64);
+        const float m = fmaxf(m2, m2o);
+        s = s * __expf(m2 - m) + so * __expf(m2o - m);
+        m2 = m;
+        mx_v = fmaxf(mx_v, mo);
+    }
+}
+
+template <int NTP, bool HALF>
+__global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restrict__ em, const int* __restrict__ doc_off,
+                                                           const float* __restrict__ trans, int ntag, int start, int stop,
+                                                           float* __restrict__ ws, int* __restrict__ path, float* __restrict__ score,
+                                                           float* __restrict__ logz, float* __restrict__ marg) {
+    static_assert(!HALF || NTP <= 32, "two lanes per tag need ntag <= 32");
+    constexpr int JW = HALF ? NTP / 2 : NTP;                // previous tags per lane
+    static_assert(JW % 4 == 0, "the vectors are read four values at a time");
+    __shared__ __attribute__((aligned(16))) float s_a[2][CRF_MAX_TAGS], s_v[2][CRF_MAX_TAGS], s_stop[CRF_MAX_TAGS];
+    __shared__ float s_tile[CRF_TILE_ROWS * CRF_TILE_STRIDE];
+    const int d = blockIdx.x, lane = threadIdx.x;
+    const int i = HALF ? (lane & 31) : lane;                // the lane's tag
+    const int j0 = HALF ? (lane >> 5) * JW : 0;             // first previous tag of the lane's slice
+    const int r0 = doc_off[d], n = doc_off[d + 1] - r0;
+    const bool own = lane < ntag;                           // the lanes that store: one per tag
+    const int ic = i < ntag ? i : ntag - 1;                 // lanes past the tags repeat the last tag's loads and store nothing
+    const float NEG = -INFINITY;
+    const long long wrow = 2ll * ntag;                      // workspace words per row: ntag forward values, ntag back pointers
+    int* __restrict__ wsi = reinterpret_cast<int*>(ws);
+
+    float tw[JW];
+#pragma unroll
+    for (int j = 0; j < JW; ++j) tw[j] = j0 + j < ntag ? trans[ic * ntag + j0 + j] : NEG;
+    s_stop[lane] = own ? trans[stop * ntag + lane] : NEG;
+    s_a[0][lane] = s_v[0][lane] = own ? (lane == start ? 0.f : -10000.f) : NEG;
+    s_a[1][lane] = s_v[1][lane] = NEG;
+    __syncthreads();
+
+    // ---- forward + Viterbi, t = 0 .. n - 1
+    double carry = 0.0;                                     // sum of the maxima taken out so far (the same in every lane)
+    float e_next = n > 0 ? em[(long long)r0 * ntag + ic] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        const float e = e_next;
+        if (t + 1 < n) e_next = em[(long long)(r0 + t + 1) * ntag + ic];
+        // forward: a_t[i] = em + log sum_j exp(prev[j] + tr[i][j]) - max(prev)
+        float mx, m2, s;
+        lse_slice<JW>(s_a[t & 1] + j0, tw, mx, m2, s);
+        // Viterbi: crf_viterbi_kernel's additions in its order, the first maximum of the lane's slice
+        const float4* pv = reinterpret_cast<const float4*>(s_v[t & 1] + j0);
+        float best;
+        int bj = j0;
+        {
+            const float4 q0 = pv[0];
+            best = q0.x + tw[0];
+            float v = q0.y + tw[1];
+            if (v > best) { best = v; bj = j0 + 1; }
+            v = q0.z + tw[2];
+            if (v > best) { best = v; bj = j0 + 2; }
+            v = q0.w + tw[3];
+            if (v > best) { best = v; bj = j0 + 3; }
+        }
+#pragma unroll
+        for (int j = 4; j < JW; j += 4) {
+            const float4 q = pv[j >> 2];
+            float v = q.x + tw[j];
+            if (v > best) { best = v; bj = j0 + j; }
+            v = q.y + tw[j + 1];
+            if (v > best) { best = v; bj = j0 + j + 1; }
+            v = q.z + tw[j + 2];
+            if (v > best) { best = v; bj = j0 + j + 2; }
+            v = q.w + tw[j + 3];
+            if (v > best) { best = v; bj = j0 + j + 3; }
+        }
+        lse_join<HALF>(mx, m2, s);
+        if (HALF) {                                         // the upper slice wins only when strictly greater: the first maximum
+            const float bo = __shfl_xor(best, 32, 64);
+            const int jo = __shfl_xor(bj, 32, 64);
+            const bool up = lane >= 32;
+            const float blo = up ? bo : best, bhi = up ? best : bo;
+            const int jlo = up ? jo : bj, jhi = up ? bj : jo;
+            best = bhi > blo ? bhi : blo;
+            bj = bhi > blo ? jhi : jlo;
+        }
+        const float a = e + ((m2 - mx) + __logf(s));
+        carry += (double)mx;
+        best += e;
+        const int nb = (t + 1) & 1;
+        s_a[nb][lane] = own ? a : NEG;
+        s_v[nb][lane] = own ? best : NEG;
+        if (own) {
+            ws[(long long)(r0 + t) * wrow + lane] = a;
+            wsi[(long long)(r0 + t) * wrow + ntag + lane] = bj;
+        }
+        __syncthreads();
+    }
+
+    // ---- the end of both chains: every lane forms the same two values, lane 0 writes them
+    int cur = 0;
+    {
+        const float* pa = s_a[n & 1];
+        const float* pv = s_v[n & 1];
+        float mx = pa[0];
+        for (int j = 1; j < ntag; ++j) mx = fmaxf(mx, pa[j]);
+        float m2 = (pa[0] - mx) + s_stop[0];
+        for (int j = 1; j < ntag; ++j) m2 = fmaxf(m2, (pa[j] - mx) + s_stop[j]);
+        float s = 0.f;
+        for (int j = 0; j < ntag; ++j) s += expf((pa[j] - mx) + s_stop[j] - m2);
+        const float z = (float)(carry + (double)mx + (double)(m2 + logf(s)));
+        float best = pv[0] + s_stop[0];
+        for (int j = 1; j < ntag; ++j) {
+            const float v = pv[j] + s_stop[j];
+            if (v > best) { best = v; cur = j; }
+        }
+        if (lane == 0) { logz[d] = z; score[d] = best; }
+    }
+    if (n == 0) return;
+
+    // ---- backward + back trace + marginals, t = n - 1 .. 0.  tw becomes the lane's slice of tag i's COLUMN: tw[k] = score of i -> j0 + k
+#pragma unroll
+    for (int k = 0; k < JW; ++k) tw[k] = j0 + k < ntag ? trans[(j0 + k) * ntag + ic] : NEG;
+    float b = own ? s_stop[lane] : NEG;                     // beta of the last position: the transition to STOP
+    long long row = (long long)(r0 + n - 1);
+    float a_next = ws[row * wrow + ic], e_next_b = em[row * ntag + ic];
+    int bp_next = wsi[row * wrow + ntag + ic];
+    int slot = 0;                                           // rows waiting in the tile: tile row k holds position t + slot - 1 - k
+    __syncthreads();                                        // (s_a is reused below)
+    for (int t = n - 1; t >= 0; --t) {
+        const float a = a_next, e = e_next_b;
+        const int bp = bp_next;
+        if (t > 0) {
+            row = (long long)(r0 + t - 1);
+            a_next = ws[row * wrow + ic];
+            bp_next = wsi[row * wrow + ntag + ic];
+            e_next_b = em[row * ntag + ic];
+        }
+        if (own) s_tile[slot * CRF_TILE_STRIDE + lane] = a + b;
+        if (lane == 0) path[r0 + t] = cur;
+        cur = __builtin_amdgcn_readlane(bp, __builtin_amdgcn_readfirstlane(cur));
+        ++slot;
+        if (slot == CRF_TILE_ROWS || t == 0) {
+            __syncthreads();
+            if (lane < slot) {                              // one lane per row: maximum, sum in tag order, division
+                float* p = s_tile + lane * CRF_TILE_STRIDE;
+                float mx = p[0];
+                for (int k = 1; k < ntag; ++k) mx = fmaxf(mx, p[k]);
+                float s = 0.f;
+                for (int k = 0; k < ntag; ++k) { const float x = expf(p[k] - mx); p[k] = x; s += x; }
+                for (int k = 0; k < ntag; ++k) p[k] = p[k] / s;
+            }
+            __syncthreads();
+            // positions t .. t + slot - 1 are contiguous in `marg`: whole rows go out, 64 consecutive floats to a store
+            int rr = lane / ntag, cc = lane - rr * ntag;
+            const int q = 64 / ntag, rem = 64 - q * ntag;
+            float* out = marg + (long long)(r0 + t) * ntag;
+            for (int f = lane; f < slot * ntag; f += 64) {
+                out[f] = s_tile[(slot - 1 - rr) * CRF_TILE_STRIDE + cc];
+                rr += q;
+                cc += rem;
+                if (cc >= ntag) { cc -= ntag; ++rr; }
+            }
+            slot = 0;
+            __syncthreads();
+        }
+        if (t > 0) {
+            // beta of position t - 1: b[i] = log sum_k exp(tr[k][i] + em_t[k] + b_t[k]) - max(em_t + b_t)
+            float* nbuf = s_a[t & 1];
+            nbuf[lane] = own ? e + b : NEG;
+            __syncthreads();
+            float mx, m2, s;
+            lse_slice<JW>(nbuf + j0, tw, mx, m2, s);
+            lse_join<HALF>(mx, m2, s);
+            b = (m2 - mx) + __logf(s);
+        }
+    }
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* __restrict__ dst) {
     const long long total = n * C;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -222,6 +443,23 @@ extern "C" int vbg_crf_viterbi(const float* emissions, const int* doc_off, int n
     VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_viterbi_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, start_tag, stop_tag, backptr, path, score);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_crf_posterior(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
+                                 int stop_tag, void* ws, int* path, float* score, float* logz, float* marginals, void* stream) {
+    VBG_CHECK_ARG(emissions && doc_off && trans && ws && path && score && logz && marginals && ndoc >= 0);
+    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    if (ndoc == 0) return VBG_OK;
+    float* w = static_cast<float*>(ws);
+#define VBG_CRF_POST(NTP, HALF) VBG_LAUNCH((crf_posterior_kernel<NTP, HALF>), dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, \
+                                           start_tag, stop_tag, w, path, score, logz, marginals)
+    if (ntag <= 8) VBG_CRF_POST(8, true);
+    else if (ntag <= 16) VBG_CRF_POST(16, true);
+    else if (ntag <= 32) VBG_CRF_POST(32, true);
+    else if (ntag <= 48) VBG_CRF_POST(48, false);
+    else VBG_CRF_POST(64, false);
+#undef VBG_CRF_POST
     VBG_LAUNCH_RET();
 }
 

@@ -28,6 +28,19 @@
 // The filing quirk of the reference is reproduced, not repaired: its loop files the LAST run under the class of row N - 2 (`prev_class`
 // is updated after the append at :472-477) -- the run's own class if it has two or more rows, the class of the run before it if it
 // has one, and class C - 1 for N == 1 (prev_class == -1 indexes the list from the back).
+//
+// THE SAME TABLE FROM THE CRF MODE'S OUTPUTS (vbg_field_decode_tags: marginals [N, ntag] and the Viterbi path [N]) is the kernel's
+// second instance, TAGS.  The chunk walk -- heads by ballot, prefix sums, the winner tables -- is shared; what the tag path changes:
+//   rows     class = tag_class[path[r]]; score = the class posterior, the fp32 sum in tag order of the row's marginals over the tags
+//            of that class; the threshold in double as above;
+//   heads    a row also starts a run when its tag has tag_begin set;
+//   sums     a score enters as the integer rint((double)score * 2^30) and the prefix sums are 64-bit integers: a marginal is no
+//            multiple of 2^-30 as a softmax score is, so the exactness argued above is had by construction instead -- integer
+//            additions associate, the one rounding is the division by len;
+//   filing   every run under its own class, the last one included (the quirk belongs to a loop the crf mode never had).
+// A run whose integer sum is 0 has the mean bits 0, which is "no record" in the winner tables: it leaves none.
+#include <type_traits>
+
 #include "vbg_common.h"
 #include "../../include/vbg.h"
 
@@ -43,64 +56,98 @@ struct dec_docs { int off[DEC_DOCS + 1]; };
 
 __device__ __forceinline__ int highest_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
 
-__global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* __restrict__ x, dec_docs docs, int doc0, int C,
-                                                                   int use_thresh, double thresh, int* __restrict__ cls_out,
-                                                                   float* __restrict__ score_out, vbg_decode_rec* __restrict__ best) {
+constexpr double DEC_FIX = 1073741824.0;    // 2^30: the fixed-point scale of the TAGS sums
+
+struct dec_tags { unsigned char cls[DEC_MAX_C]; unsigned char begin[DEC_MAX_C]; };     // tag -> class, tag -> opens a run
+
+// a run's mean from its sum: the one rounding of either instance
+__device__ __forceinline__ double run_mean(double sum, int len) { return sum / (double)len; }
+__device__ __forceinline__ double run_mean(long long sum, int len) { return (double)sum * (1.0 / DEC_FIX) / (double)len; }
+
+// TAGS == false: x = class scores [N, cols], cols == C, `path` and `tags` unused.  TAGS == true: x = marginals [N, cols], cols == ntag.
+template <bool TAGS>
+__global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* __restrict__ x, const int* __restrict__ path, dec_docs docs,
+                                                                   dec_tags tags, int doc0, int cols, int C, int use_thresh, double thresh,
+                                                                   int* __restrict__ cls_out, float* __restrict__ score_out,
+                                                                   vbg_decode_rec* __restrict__ best) {
+    using sum_t = std::conditional_t<TAGS, long long, double>;
     __shared__ int s_cls[DEC_THREADS];                      // class of the chunk's rows
-    __shared__ double s_pb[DEC_THREADS];                    // sum of the document's scores in front of the row
-    __shared__ double s_wtot[DEC_WAVES];
+    __shared__ sum_t s_pb[DEC_THREADS];                     // sum of the document's scores in front of the row
+    __shared__ sum_t s_wtot[DEC_WAVES];
     __shared__ int s_whead[DEC_WAVES];                      // last run head inside the wave's rows, or -1
     __shared__ unsigned long long s_cmax[DEC_MAX_C], s_ckey[DEC_MAX_C];     // per class, this chunk: largest mean, then smallest (start, len)
     __shared__ unsigned long long s_bmean[DEC_MAX_C], s_bkey[DEC_MAX_C];    // per class, so far (mean bits 0: no record)
+    __shared__ int s_tc[DEC_MAX_C], s_tb[DEC_MAX_C];        // TAGS: the two tag tables
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int r0 = docs.off[blockIdx.x], n = docs.off[blockIdx.x + 1] - r0;
-    if (t < DEC_MAX_C) { s_cmax[t] = 0ull; s_ckey[t] = ~0ull; s_bmean[t] = 0ull; s_bkey[t] = ~0ull; }
+    if (t < DEC_MAX_C) {
+        s_cmax[t] = 0ull; s_ckey[t] = ~0ull; s_bmean[t] = 0ull; s_bkey[t] = ~0ull;
+        if constexpr (TAGS) { s_tc[t] = tags.cls[t]; s_tb[t] = tags.begin[t]; }
+    }
     __syncthreads();
 
     // carried from chunk to chunk, the same in every thread
-    double total = 0.0;      // sum of the scores of the rows in front of the chunk
+    sum_t total = 0;         // sum of the scores of the rows in front of the chunk
     int open_head = -1;      // first row of the run that is open at the chunk's start
-    double open_pb = 0.0;    // sum of the scores in front of that row
+    sum_t open_pb = 0;       // sum of the scores in front of that row
     int prev_last = -1;      // class of the row in front of the chunk (-1: none, so row 0 is a head)
-    int cls_nm2 = -1;        // class of row n - 2
+    int file_last = -1;      // class the document's last run is filed under
     for (int base = 0; base < n; base += DEC_THREADS) {
         const int g = base + t;
         const bool valid = g < n;
         int c = -1;
+        bool begin = false;
         float sc = 0.f;
         if (valid) {
-            const float* p = x + (long long)(r0 + g) * C;
-            float mx;
-            const float inv = row_softmax_norm(p, C, mx);
-            c = 0;
-            sc = row_softmax_prob(p[0], mx, inv);
-            for (int k = 1; k < C; ++k) {
-                const float v = row_softmax_prob(p[k], mx, inv);
-                if (v > sc) { sc = v; c = k; }
+            const float* p = x + (long long)(r0 + g) * cols;
+            if constexpr (TAGS) {
+                const int tag = path[r0 + g];
+                c = 0;
+                if (tag >= 0 && tag < cols) {               // (a tag outside the table: class 0, score 0)
+                    c = s_tc[tag];
+                    begin = s_tb[tag] != 0;
+                    for (int k = 0; k < cols; ++k)
+                        if (s_tc[k] == c) sc += p[k];
+                }
+            } else {
+                float mx;
+                const float inv = row_softmax_norm(p, cols, mx);
+                c = 0;
+                sc = row_softmax_prob(p[0], mx, inv);
+                for (int k = 1; k < cols; ++k) {
+                    const float v = row_softmax_prob(p[k], mx, inv);
+                    if (v > sc) { sc = v; c = k; }
+                }
             }
             if (use_thresh && (double)sc < thresh) c = 0;
             cls_out[r0 + g] = c;
             score_out[r0 + g] = sc;
         }
-        double incl = (double)sc;
+        sum_t own;
+        if constexpr (TAGS) own = __double2ll_rn((double)sc * DEC_FIX);
+        else own = (double)sc;
+        sum_t incl = own;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            const double up = __shfl_up(incl, o, 64);
+            const sum_t up = __shfl_up(incl, o, 64);
             if (lane >= o) incl += up;
         }
         s_cls[t] = c;
         if (lane == 63) s_wtot[w] = incl;
         __syncthreads();                                                            // 1: classes and wave totals of the chunk
-        double pb = total + (incl - (double)sc), chunk_total = 0.0;
+        sum_t pb = total + (incl - own), chunk_total = 0;
 #pragma unroll
         for (int k = 0; k < DEC_WAVES; ++k) {
-            const double wt = s_wtot[k];
+            const sum_t wt = s_wtot[k];
             if (k < w) pb += wt;
             chunk_total += wt;
         }
         const int left = t > 0 ? s_cls[t - 1] : prev_last;
-        const bool head = valid && c != left;
-        if (base + DEC_THREADS >= n) cls_nm2 = n - 2 >= base ? s_cls[n - 2 - base] : prev_last;
+        const bool head = valid && (c != left || begin);
+        if (base + DEC_THREADS >= n) {
+            if constexpr (TAGS) file_last = s_cls[n - 1 - base];                    // its own class
+            else file_last = n == 1 ? C - 1 : (n - 2 >= base ? s_cls[n - 2 - base] : prev_last);      // the reference's: the class of row n - 2
+        }
         const int chunk_last = s_cls[DEC_THREADS - 1];
         s_pb[t] = pb;
         const unsigned long long hm = __ballot(head);
@@ -113,11 +160,11 @@ __global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* 
             const unsigned long long lower = hm & ((1ull << lane) - 1ull);
             int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
             for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
-            double ppb;
+            sum_t ppb;
             if (ph >= 0) ppb = s_pb[ph - base];
             else { ph = open_head; ppb = open_pb; }
             const int len = g - ph;
-            bits = (unsigned long long)__double_as_longlong((pb - ppb) / (double)len);
+            bits = (unsigned long long)__double_as_longlong(run_mean(pb - ppb, len));
             key = ((unsigned long long)ph << DEC_ROW_BITS) | (unsigned long long)len;
             fc = left;
             atomicMax(&s_cmax[fc], bits);
@@ -137,10 +184,10 @@ __global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* 
         }
     }
     __syncthreads();
-    if (n > 0 && t == 0) {                                  // the last run, filed the reference's way (last in its class's list)
-        const int fc = n == 1 ? C - 1 : cls_nm2;
+    if (n > 0 && t == 0) {                                  // the last run (scores: filed the reference's way, last in its class's list)
+        const int fc = file_last;
         const int len = n - open_head;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong((total - open_pb) / (double)len);
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(run_mean(total - open_pb, len));
         if (bits > s_bmean[fc]) {
             s_bmean[fc] = bits;
             s_bkey[fc] = ((unsigned long long)open_head << DEC_ROW_BITS) | (unsigned long long)len;
@@ -161,9 +208,10 @@ __global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* 
 
 using namespace vbg;
 
-extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
-                                float* score, vbg_decode_rec* best, void* stream) {
-    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
+// the part the two entries share: the row ranges' checks and the launches, 512 documents each
+template <bool TAGS>
+static int decode_launch(const float* x, const int* path, const int* h_doc_off, int ndoc, const dec_tags& tags, int cols, int C,
+                         int use_thresh, double thresh, int* cls, float* score, vbg_decode_rec* best, void* stream) {
     VBG_CHECK_ARG(h_doc_off[0] >= 0);
     for (int d = 0; d < ndoc; ++d) {
         const long long nd = (long long)h_doc_off[d + 1] - h_doc_off[d];
@@ -171,14 +219,33 @@ extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, 
     }
     if (ndoc == 0) return VBG_OK;
     VBG_CHECK_ARG(best);
-    if (h_doc_off[ndoc] > h_doc_off[0]) VBG_CHECK_ARG(x && cls && score);
+    if (h_doc_off[ndoc] > h_doc_off[0]) VBG_CHECK_ARG(x && cls && score && (path || !TAGS));
     for (int d0 = 0; d0 < ndoc; d0 += DEC_DOCS) {
         const int nd = ndoc - d0 < DEC_DOCS ? ndoc - d0 : DEC_DOCS;
         dec_docs docs;
         for (int i = 0; i <= nd; ++i) docs.off[i] = h_doc_off[d0 + i];
         for (int i = nd + 1; i <= DEC_DOCS; ++i) docs.off[i] = docs.off[nd];
-        VBG_LAUNCH(field_decode_kernel, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, docs, d0, C, use_thresh, thresh, cls, score,
-                   best);
+        VBG_LAUNCH(field_decode_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, docs, tags, d0, cols, C,
+                   use_thresh, thresh, cls, score, best);
     }
     VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
+                                float* score, vbg_decode_rec* best, void* stream) {
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
+    return decode_launch<false>(x, nullptr, h_doc_off, ndoc, dec_tags{}, C, C, use_thresh, thresh, cls, score, best, stream);
+}
+
+extern "C" int vbg_field_decode_tags(const float* marginals, const int* path, const int* h_doc_off, int ndoc, int ntag, int C,
+                                     const int* h_tag_class, const int* h_tag_begin, int use_thresh, double thresh, int* cls, float* score,
+                                     vbg_decode_rec* best, void* stream) {
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C && ntag >= 1 && ntag <= DEC_MAX_C && h_tag_class && h_tag_begin);
+    dec_tags tags = {};
+    for (int k = 0; k < ntag; ++k) {
+        VBG_CHECK_ARG(h_tag_class[k] >= 0 && h_tag_class[k] < C && (h_tag_begin[k] == 0 || h_tag_begin[k] == 1));
+        tags.cls[k] = (unsigned char)h_tag_class[k];
+        tags.begin[k] = (unsigned char)h_tag_begin[k];
+    }
+    return decode_launch<true>(marginals, path, h_doc_off, ndoc, tags, ntag, C, use_thresh, thresh, cls, score, best, stream);
 }

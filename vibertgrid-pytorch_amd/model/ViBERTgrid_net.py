@@ -294,6 +294,30 @@ class ViBERTgridNet(nn.Module):
         fuse = self.late_fusion_net(roi, emb_cat)
         return self.field_type_classification_head.inference(fuse)
 
+    def inference_posterior(self, image: Tuple[torch.Tensor], seg_indices: Tuple[torch.Tensor], coors: torch.Tensor,
+                            corpus: torch.Tensor, mask: torch.Tensor):
+        """classifier_mode "crf" only: `inference()`'s trunk, then model.crf.CrfPosterior(path, score, logz, marginals) for all
+        documents of the call from one launch -- the tags `inference()` returns (path[:, None].float() of a one-document call) with
+        the per-segment posteriors that vbg.decode.decode_tags / crf_field_strings need.  Documents are the images of the call: their
+        row ranges are the box table's offsets, already on the device."""
+        if self.classifier_mode != "crf":
+            raise ValueError(f"inference_posterior needs classifier_mode 'crf', this model has {self.classifier_mode!r}")
+        ops.set_amp(torch.is_autocast_enabled("cuda"))
+        ops.latch_deterministic()
+        self.BERTgrid_generator.prefetch_host(corpus, mask, seg_indices)
+        try:
+            batch, icoors, packed, B, H, W = self._trunk(image, seg_indices, coors, corpus, mask)
+            emb_cat, p_fuse = self._features(batch, packed, B, H, W, seg_indices, corpus, mask)
+        finally:
+            self.BERTgrid_generator.release_host()
+            Fn.SIDE_OK[0] = False
+        roi = self.grid_roi_align_net(p_fuse, icoors, None, packed=packed)
+        fuse = self.late_fusion_net(roi, emb_cat)
+        head = self.field_type_classification_head
+        em = head.category_classification_net(fuse.reshape((-1, head.fuse_embedding_channel))).detach()
+        doc_off = packed[1] if packed is not None else head._doc_off([0 if c is None else c.shape[0] for c in icoors], em.device)
+        return head.crf_layer.posterior(em, doc_off)
+
     def forward(self, image: Tuple[torch.Tensor], seg_indices: Tuple[torch.Tensor], segment_classes: Tuple[torch.Tensor],
                 coors: torch.Tensor, corpus: torch.Tensor, mask: torch.Tensor):
         # (the host copies of the integer inputs first: one device->host copy while the stream holds nothing of this step)

@@ -3,8 +3,12 @@
 Same parameter (`transitions[i, j]` = score of the transition j -> i, with the START row / STOP column pinned to -10000) and the same
 per-document API (`forward(feats, tags)` -> (log Z - gold score) / len, `inference(feats)` -> (path score, tag list)); `nll` /
 `decode` take all documents of a batch at once (row ranges `doc_off`), one launch each: forward algorithm + gold score,
-backward = (marginals - gold indicators), Viterbi with first-maximum tie breaking like `torch.max`.
+backward = (marginals - gold indicators), Viterbi with first-maximum tie breaking like `torch.max`.  `posterior` adds what the
+reference's prediction path lacks: the same Viterbi path and score together with log Z and the posterior marginals
+p(y_t = i | x) of every row, from one launch (vbg_crf_posterior).
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -13,6 +17,9 @@ from vbg import ops
 
 START_TAG = "<START>"
 STOP_TAG = "<STOP>"
+
+# path int32 [N], score fp32 [ndoc], logz fp32 [ndoc], marginals fp32 [N, ntag] (rows sum to 1; START / STOP columns are zeros)
+CrfPosterior = namedtuple("CrfPosterior", ["path", "score", "logz", "marginals"])
 
 
 class CRF(nn.Module):
@@ -37,6 +44,11 @@ class CRF(nn.Module):
         """-> (best tag per row int32 [N], path score per document [ndoc])"""
         s, e = self._ends()
         return ops.crf_viterbi(feats.contiguous(), doc_off, self.transitions.detach().contiguous(), s, e)
+
+    def posterior(self, feats: torch.Tensor, doc_off: torch.Tensor) -> CrfPosterior:
+        """`decode`'s path and score, bit for bit, with log Z per document and the marginals of every row: one launch"""
+        s, e = self._ends()
+        return CrfPosterior(*ops.crf_posterior(feats.detach().contiguous(), doc_off, self.transitions.detach().contiguous(), s, e))
 
     def forward(self, feats, tags):
         off = torch.tensor([0, feats.shape[0]], dtype=torch.int32).to(feats.device)

@@ -249,6 +249,15 @@ class CRFFieldTypeClassification(nn.Module):
         path, _ = self.crf_layer.decode(em, self._doc_off([em.shape[0]], em.device))
         return path.unsqueeze(1).float()
 
+    def posterior(self, fuse_embeddings: torch.Tensor, lens=None):
+        """-> model.crf.CrfPosterior: `inference`'s tags with their path score, log Z and the posterior marginals of every segment.
+        lens: segments per document (None: one document); all documents go through one launch."""
+        fuse = fuse_embeddings.reshape((-1, self.fuse_embedding_channel))
+        em = self.category_classification_net(fuse).detach()
+        lens = [em.shape[0]] if lens is None else [int(n) for n in lens]
+        assert sum(lens) == em.shape[0], f"lens {lens} do not cover {em.shape[0]} segments"
+        return self.crf_layer.posterior(em, self._doc_off(lens, em.device))
+
     def forward(self, fuse_embeddings: torch.Tensor, segment_classes: Tuple[torch.Tensor], prepared=None):
         device = fuse_embeddings.device
         lens = [int(b.shape[0]) for b in segment_classes]

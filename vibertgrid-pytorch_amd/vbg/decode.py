@@ -7,9 +7,19 @@ host, for the winning runs only.
     pred_key_list = field_strings(pred_label, num_classes, ocr_text, thresh=strcmp_tresh, join="space_before")
 
 `pred_label` is the 2-D float32 device tensor the classifier returns ([N, C] scores; the reference applies softmax to it once more,
-and so does the kernel).  The tag vector of the crf mode is not an input of these functions.  Rows that hold NaN or infinities are
-outside the contract: their document's records are meaningless (nothing faults or hangs).  C <= 64 and fewer than 2^20 segments per
-document, or the library reports an argument error."""
+and so does the kernel).  Rows that hold NaN or infinities are outside the contract: their document's records are meaningless (nothing
+faults or hangs).  C <= 64 and fewer than 2^20 segments per document, or the library reports an argument error.
+
+The crf mode returns tags, not scores, and the reference has no such loop for it.  Its counterpart here takes the posterior of the
+CRF (ViBERTgridNet.inference_posterior / CRF.posterior: Viterbi path + marginals, one launch) and gives the same table:
+
+    table = tag_table(tag_to_idx, category_list)
+    pred_key_list = crf_field_strings(net.inference_posterior(...), table, num_classes, ocr_text, thresh=strcmp_tresh)
+
+A segment's class is the class of its Viterbi tag, its score the posterior of that CLASS (the sum of the marginals of the class's
+tags); runs also break in front of a begin tag, means are exact (fixed-point sums), every run is filed under its own class -- the
+last-run quirk of the score loop is not carried over -- and a run whose scores all round to 0 leaves no record (decode_tags ->
+vbg_field_decode_tags, include/vbg.h).  Two launches and one device-to-host copy per document or batch."""
 from collections import namedtuple
 
 import numpy as np
@@ -83,3 +93,63 @@ def field_strings(pred_label, num_classes, ocr_text, thresh=None, join="space_be
     if len(texts) != pred_label.shape[0]:
         raise ValueError(f"{len(texts)} segment texts for {pred_label.shape[0]} rows")
     return join_winners(decode_fields(pred_label, thresh).best[0], texts, join)
+
+
+# ---- the crf mode: tags + posterior marginals
+# tag_class[k]: class of tag k; tag_begin[k]: 1 where tag k opens a new run even behind a row of its class (host lists of ntag ints)
+TagTable = namedtuple("TagTable", ["tag_class", "tag_begin"])
+
+_ENDS = ("<START>", "<STOP>")
+
+
+def tag_table(tag_to_idx, category_list):
+    """Dictionaries in the reference's format -> TagTable.  "O" and <START> / <STOP> map to class 0; "B-x" and "I-x" to the index of x
+    in category_list.  A "B-x" tag is a begin tag exactly when the dictionary also has "I-x":
+    the plain TAG_TO_IDX sets label every segment of a field "B-x", and there a B- tag says nothing about where a field starts.
+    Indices must be 0 .. ntag - 1, each once; unknown names raise ValueError."""
+    ntag = len(tag_to_idx)
+    cats = list(category_list)
+    tag_class, tag_begin = [None] * ntag, [0] * ntag
+    for name, k in tag_to_idx.items():
+        if not (isinstance(k, int) and 0 <= k < ntag) or tag_class[k] is not None:
+            raise ValueError(f"tag indices must be 0 .. {ntag - 1}, each once: {name!r} -> {k!r}")
+        if name == "O" or name in _ENDS:
+            tag_class[k] = 0
+            continue
+        field = name[2:]
+        if name[:2] not in ("B-", "I-") or field not in cats:
+            raise ValueError(f"tag {name!r} is neither 'O', <START> / <STOP> nor 'B-x' / 'I-x' with x in category_list {cats}")
+        tag_class[k] = cats.index(field)
+        tag_begin[k] = int(name[:2] == "B-" and ("I-" + field) in tag_to_idx)
+    return TagTable(tag_class, tag_begin)
+
+
+def _posterior_parts(posterior):
+    marginals, path = (posterior.marginals, posterior.path) if hasattr(posterior, "marginals") else posterior
+    if not (torch.is_tensor(marginals) and marginals.dim() == 2 and marginals.dtype == torch.float32 and marginals.is_cuda):
+        raise TypeError("marginals must be a 2-D float32 device tensor [N, ntag] (CRF.posterior's)")
+    if not (torch.is_tensor(path) and path.dim() == 1 and path.dtype == torch.int32 and path.shape[0] == marginals.shape[0]):
+        raise TypeError(f"path must be a 1-D int32 device tensor of {marginals.shape[0]} tags (CRF.posterior's)")
+    return marginals, path
+
+
+def decode_tags(posterior, table, num_classes, thresh=None, doc_off=None):
+    """posterior: a CrfPosterior or (marginals, path); table: tag_table's -> FieldDecode, as decode_fields gives it for scores.
+    One launch, one device-to-host copy."""
+    marginals, path = _posterior_parts(posterior)
+    n = marginals.shape[0]
+    off = [0, n] if doc_off is None else [int(v) for v in doc_off]
+    cls, score, best = ops.field_decode_tags(marginals, path, table.tag_class, table.tag_begin, num_classes, off, thresh)
+    rec = best.cpu().numpy().view(REC).reshape(len(off) - 1, int(num_classes))     # the one device-to-host copy
+    return FieldDecode(cls, score, rec, off)
+
+
+def crf_field_strings(posterior, table, num_classes, ocr_text, thresh=None, join="space_before"):
+    """`pred_key_list` of one document in the crf mode: one string per class, joined by the rules of field_strings"""
+    marginals, _ = _posterior_parts(posterior)
+    if join not in JOIN:
+        raise ValueError(f"join must be one of {sorted(JOIN)}, got {join!r}")
+    texts = ocr_text[0] if len(ocr_text) > 0 and not isinstance(ocr_text[0], str) else ocr_text
+    if len(texts) != marginals.shape[0]:
+        raise ValueError(f"{len(texts)} segment texts for {marginals.shape[0]} rows")
+    return join_winners(decode_tags(posterior, table, num_classes, thresh).best[0], texts, join)

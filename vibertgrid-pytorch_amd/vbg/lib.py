@@ -284,6 +284,9 @@ SIGNATURES = {
     "vbg_crf_nll_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "vbg_crf_viterbi": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_field_decode": (c_int, [c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_d, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_crf_posterior": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_field_decode_tags": (c_int, [c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int, c_d,
+                                      c_vp, c_vp, c_vp, c_vp]),
     "vbg_seq_metrics": (c_int, [c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, TagTable, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),

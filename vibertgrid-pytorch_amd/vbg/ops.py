@@ -2626,6 +2626,52 @@ def crf_viterbi(em, doc_off, trans, start, stop):
     return path, score
 
 
+def crf_posterior(em, doc_off, trans, start, stop):
+    """-> (path int32 [N], score [ndoc], logz [ndoc], marginals [N, ntag]) in ONE launch (vbg_crf_posterior, include/vbg.h): path and
+    score are crf_viterbi's bit for bit; marginals[t, i] = p(y_t = i | x), each row summing to 1, the START / STOP columns exact zeros.
+    No atomics: the deterministic mode takes the same route."""
+    _chk_f32(em)
+    _chk_f32(trans)
+    N, ntag = em.shape
+    ndoc = doc_off.numel() - 1
+    if tuple(trans.shape) != (ntag, ntag) or doc_off.dtype != i32:
+        raise VbgError(f"vbg_crf_posterior: trans {tuple(trans.shape)} / doc_off {doc_off.dtype} do not fit emissions [{N}, {ntag}]")
+    ws = torch.empty((max(N, 1), 2 * ntag), device=em.device, dtype=f32)
+    path = torch.empty((N,), device=em.device, dtype=i32)
+    score = torch.empty((ndoc,), device=em.device, dtype=f32)
+    logz = torch.empty((ndoc,), device=em.device, dtype=f32)
+    marg = torch.empty((N, ntag), device=em.device, dtype=f32)
+    check(lib.vbg_crf_posterior(P(em.contiguous()), P(doc_off), ndoc, P(trans.contiguous()), ntag, start, stop, P(ws), P(path), P(score),
+                                P(logz), P(marg), _stream()), "vbg_crf_posterior")
+    return path, score, logz, marg
+
+
+def field_decode_tags(marginals, path, tag_class, tag_begin, num_classes, doc_off=None, thresh=None):
+    """marginals [N, ntag] fp32 and path [N] int32 (device: crf_posterior's) -> (cls int32 [N], score fp32 [N], best float64
+    [ndoc * num_classes, 2]) in ONE launch (vbg_field_decode_tags, include/vbg.h).  tag_class / tag_begin: HOST lists of ntag ints (tag ->
+    class; 1 where the tag opens a new run); doc_off, thresh and the layout of `best` as in field_decode."""
+    _chk_f32(marginals)
+    N, ntag = marginals.shape
+    if path.dtype != i32 or tuple(path.shape) != (N,) or path.device != marginals.device:
+        raise VbgError(f"vbg_field_decode_tags: path must be int32 [{N}] on {marginals.device}, got {path.dtype} {tuple(path.shape)}")
+    if len(tag_class) != ntag or len(tag_begin) != ntag:
+        raise VbgError(f"vbg_field_decode_tags: {len(tag_class)} / {len(tag_begin)} table entries for {ntag} tags")
+    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
+    ndoc = len(off) - 1
+    ncls = int(num_classes)
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"vbg_field_decode_tags: doc_off {off[:4]}... does not fit {N} rows")
+    cls = torch.empty(N, dtype=i32, device=marginals.device)
+    score = torch.empty(N, dtype=f32, device=marginals.device)
+    best = torch.empty(ndoc * max(ncls, 0), 2, dtype=torch.float64, device=marginals.device)
+    tc = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_class])
+    tb = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_begin])
+    check(lib.vbg_field_decode_tags(P(marginals.contiguous()), P(path.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ntag, ncls, tc, tb,
+                                    int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(best),
+                                    _stream()), "vbg_field_decode_tags")
+    return cls, score, best
+
+
 def _sum_det(x, out, squares):
     ws = torch.empty((int(lib.vbg_sum_det_ws_elems()),), device=x.device, dtype=f32)
     check(lib.vbg_sum_det(P(x), x.numel(), int(squares), P(out), P(ws), _stream()), "vbg_sum_det")

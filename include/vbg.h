@@ -744,6 +744,33 @@ int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const 
  * atomics: the same bits with and without the deterministic mode.  Emissions holding NaN or infinities are outside the contract. */
 int vbg_crf_posterior(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                       int stop_tag, void* ws, int* path, float* score, float* logz, float* marginals, void* stream);
+/* The training loss of the same CRF with a gradient whose error does not grow with the document's length (vbg_crf_nll_bwd forms every
+ * marginal as exp(alpha + beta - logZ) from unnormalised vectors: DESIGN.md, section 8).  Documents, row ranges, trans, the -10000
+ * initial vector and the START / STOP conventions are vbg_crf_nll_fwd's.  ONE launch for all documents gives
+ *   logz [ndoc]                    log Z from a forward recursion in log space, re-centred at every step as vbg_crf_posterior's (the
+ *                                  maxima taken out are summed in double);
+ *   nll [ndoc]                     (float)((log Z - gold score) / n_d), gold score and quotient in double;
+ * and, when both tables are given (both or neither: a loss-only call passes NULL twice and stores no vector), the gradient of
+ * n_d * nll[d], that is at marginal scale:
+ *   dem_unit [N, ntag]             p(y_t = i | x) - [tags[t] == i];
+ *   dtrans_unit [ndoc, ntag, ntag] block d, entry [i, j]: sum_t p(y_{t-1} = j, y_t = i | x) with y_{-1} = START, plus on row
+ *                                  i = STOP p(y_{n-1} = j | x), minus the gold path's transition counts.
+ * The pairwise table of step t is built from the re-centred forward vector of t - 1, the transitions, the emission of t and the
+ * re-centred backward vector of t; its own maximum is taken out before the exponentials and it is divided by its own sum.  The state
+ * marginal of row t is the row sum of that table: rows of dem_unit + indicator sum to 1 by construction, and no term holds log Z or
+ * anything that grows with t.  The tables are added up in double.  No workspace: the forward vectors wait in the rows of dem_unit.
+ * n_d == 0: nll 0, logz vbg_crf_nll_fwd's value, no row touched, the dtrans_unit block zeros.  A tag outside [0, ntag) contributes no
+ * indicator and no emission term, and the gold transitions into and out of it are skipped: that document's result is meaningless,
+ * nothing faults.  No atomics: the same bits with and without the deterministic mode, and documents carry nothing into each other.
+ * bwd, ONE launch: demissions[r, :] = (gout[d] / n_d) * dem_unit[r, :] over the rows of document d (out of place: the tables survive
+ * a second backward) and dtrans_accum[k] += sum_d (gout[d] / n_d) * dtrans_unit[d, k], one thread per entry walking the documents in
+ * increasing d, product and sum rounded separately; empty documents are skipped.
+ * Argument errors: ntag outside [1, 64], start_tag / stop_tag outside [0, ntag), ndoc < 0, exactly one table NULL, a NULL required
+ * pointer with ndoc > 0.  ndoc == 0 is a no-op.  Emissions holding NaN or infinities are outside the contract. */
+int vbg_crf_nll_stable(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
+                       int start_tag, int stop_tag, float* nll, float* logz, float* dem_unit, float* dtrans_unit, void* stream);
+int vbg_crf_nll_stable_bwd(const float* dem_unit, const float* dtrans_unit, const int* doc_off, int ndoc, int ntag,
+                           const float* gout, float* demissions, float* dtrans_accum, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Field decoding of the returned class scores (csrc/decode.hip).  Replaces the per-segment loop every caller of the reference runs

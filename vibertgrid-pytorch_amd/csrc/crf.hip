@@ -377,6 +377,212 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
     }
 }
 
+// Training loss and gradient that hold at any length (vbg_crf_nll_stable): one wave per document, lane i owns tag i.
+//
+// Nothing that grows with the row index is ever formed.  The forward vectors are crf_posterior_kernel's: log space, the maximum of
+// the previous vector taken out of every step and summed into log Z in double; on top of that every row of emissions is taken
+// relative to its own maximum (a reduction off the chain, on a row fetched a step ahead; the maxima go into the same double).  The
+// backward vectors are re-centred the same way.  The gradient never touches log Z: the pairwise table of step t,
+//     x[i][j] = exp(a_{t-1}[j] + tr[i][j] + em_t[i] + b_t[i] - its own maximum),
+// is divided by its own sum, lane i owning row i; the state marginal of row t is the row sum of that table and the transition
+// gradient the sum of the tables over t in an fp64 accumulator in LDS (lane i owns row i of it).  The gold path is taken off as the
+// tables go in: row t's indicator leaves entry [tags[t]][tags[t-1]] at step t.  The exponentials of a table are formed twice (once for
+// its sum, once for the quotients) by the same code, so the two passes see the same bits: an image of the table next to the fp64
+// accumulator and the transitions would not fit a static LDS allocation.
+// The forward vectors wait in the rows of dem_unit: row t is written by the forward pass, read back by the same lane at backward
+// step t + 1 (fetched during step t + 2) and overwritten with its gradient at step t.  A loss-only call stores no vector.
+// Tags outside [0, ntag) match no lane and no column: no indicator, no emission term, no gold transition in or out of them.
+constexpr int CRF_ST_STRIDE = CRF_MAX_TAGS + 1;            // odd row stride of the LDS images: lane i walking row i meets no bank conflict
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// one entry of the pairwise table before its maximum is taken out; the ONE statement of this sum (three passes use it)
+__device__ __forceinline__ float crf_pair_arg(float a_prev_j, float tr_ij, float nb_i) { return (a_prev_j + tr_ij) + nb_i; }
+
+__global__ __launch_bounds__(64) void crf_nll_stable_kernel(const float* __restrict__ em, const int* __restrict__ tags,
+                                                            const int* __restrict__ doc_off, const float* __restrict__ trans, int ntag,
+                                                            int start, int stop, float* __restrict__ nll, float* __restrict__ logz,
+                                                            float* dem_unit, float* __restrict__ dtrans_unit) {
+    __shared__ float s_tr[CRF_MAX_TAGS * CRF_ST_STRIDE];
+    __shared__ double s_acc[CRF_MAX_TAGS * CRF_ST_STRIDE];
+    __shared__ float s_a[2][CRF_MAX_TAGS], s_nb[CRF_MAX_TAGS];
+    const int d = blockIdx.x, lane = threadIdx.x;
+    const int r0 = doc_off[d], n = doc_off[d + 1] - r0;
+    const bool own = lane < ntag;
+    const int ic = own ? lane : ntag - 1;                   // lanes past the tags repeat the last tag's loads and store nothing
+    const bool grad = dem_unit != nullptr;
+    const float NEG = -INFINITY;
+    const float* trow = s_tr + ic * CRF_ST_STRIDE;          // the lane's row: trow[j] = score of j -> lane
+    double* arow = s_acc + ic * CRF_ST_STRIDE;
+
+    for (int k = lane; k < ntag * ntag; k += 64) {
+        const int i = k / ntag, j = k - i * ntag;
+        s_tr[i * CRF_ST_STRIDE + j] = trans[k];
+        s_acc[i * CRF_ST_STRIDE + j] = 0.0;
+    }
+    s_a[0][lane] = own ? (lane == start ? 0.f : -10000.f) : NEG;
+    __syncthreads();
+
+    // ---- forward, t = 0 .. n - 1: a_t[i] = (em_t[i] - max em_t) + log sum_j exp(a_{t-1}[j] + tr[i][j]) - max(a_{t-1})
+    double carry = 0.0;                                     // what has been taken out so far (the same in every lane)
+    float e_next = n > 0 ? em[(long long)r0 * ntag + ic] : 0.f;
+    for (int t = 0; t < n; ++t) {
+        const float e = e_next;
+        if (t + 1 < n) e_next = em[(long long)(r0 + t + 1) * ntag + ic];
+        const float emax = wave_max(own ? e : NEG);
+        const float* prev = s_a[t & 1];
+        float mx = prev[0], m2 = prev[0] + trow[0];
+        for (int j = 1; j < ntag; ++j) {
+            mx = fmaxf(mx, prev[j]);
+            m2 = fmaxf(m2, prev[j] + trow[j]);
+        }
+        float s = 0.f;
+        for (int j = 0; j < ntag; ++j) s += expf((prev[j] + trow[j]) - m2);
+        const float a = (e - emax) + ((m2 - mx) + logf(s));
+        carry += (double)mx + (double)emax;
+        s_a[(t + 1) & 1][lane] = own ? a : NEG;
+        if (grad && own) dem_unit[(long long)(r0 + t) * ntag + lane] = a;
+        __syncthreads();
+    }
+
+    // ---- log Z (every lane forms the same value) and the gold score: lane l takes rows l, l + 64, ...; the sums are double
+    double zd;
+    {
+        const float* pa = s_a[n & 1];
+        const float* ps = s_tr + stop * CRF_ST_STRIDE;
+        float mx = pa[0];
+        for (int j = 1; j < ntag; ++j) mx = fmaxf(mx, pa[j]);
+        float m2 = (pa[0] - mx) + ps[0];
+        for (int j = 1; j < ntag; ++j) m2 = fmaxf(m2, (pa[j] - mx) + ps[j]);
+        float s = 0.f;
+        for (int j = 0; j < ntag; ++j) s += expf((pa[j] - mx) + ps[j] - m2);
+        zd = carry + (double)mx + (double)(m2 + logf(s));
+    }
+    double gold = 0.0;
+    for (int t = lane; t < n; t += 64) {
+        const int ct = tags[r0 + t], pt = t > 0 ? tags[r0 + t - 1] : start;
+        const bool cin = (unsigned)ct < (unsigned)ntag, pin = (unsigned)pt < (unsigned)ntag;
+        if (cin) gold += (double)em[(long long)(r0 + t) * ntag + ct];
+        if (cin && pin) gold += (double)s_tr[ct * CRF_ST_STRIDE + pt];
+        if (t == n - 1 && cin) gold += (double)s_tr[stop * CRF_ST_STRIDE + ct];
+    }
+    gold = wave_sum_f64(gold);
+    if (lane == 0) {
+        logz[d] = (float)zd;
+        nll[d] = n > 0 ? (float)((zd - gold) / (double)n) : 0.f;
+    }
+    if (!grad) return;
+
+    // ---- backward + both gradients, t = n - 1 .. 0
+    float b = 0.f;                                          // beta of the last position: the transition to STOP, less its maximum
+    if (n > 0) {
+        const float bs = own ? s_tr[stop * CRF_ST_STRIDE + lane] : NEG;
+        b = bs - wave_max(bs);
+    }
+    float e_nx = 0.f, a_nx = 0.f;                           // emission of row t and forward vector of row t - 1, a step ahead
+    int ct_nx = -1, pt_nx = -1;
+    if (n > 0) {
+        e_nx = em[(long long)(r0 + n - 1) * ntag + ic];
+        ct_nx = tags[r0 + n - 1];
+        pt_nx = n > 1 ? tags[r0 + n - 2] : start;
+        a_nx = n > 1 ? dem_unit[(long long)(r0 + n - 2) * ntag + ic] : (ic == start ? 0.f : -10000.f);
+    }
+    for (int t = n - 1; t >= 0; --t) {
+        const float e = e_nx, ap = a_nx;
+        const int ct = ct_nx, pt = pt_nx;
+        if (t > 0) {
+            e_nx = em[(long long)(r0 + t - 1) * ntag + ic];
+            ct_nx = pt;
+            pt_nx = t > 1 ? tags[r0 + t - 2] : start;
+            a_nx = t > 1 ? dem_unit[(long long)(r0 + t - 2) * ntag + ic] : (ic == start ? 0.f : -10000.f);
+        }
+        const float emax = wave_max(own ? e : NEG);
+        const float nb = (e - emax) + b;                    // emission of t + everything after it, for the lane's tag
+        float* avec = s_a[t & 1];
+        avec[lane] = own ? ap : NEG;
+        s_nb[lane] = own ? nb : NEG;
+        __syncthreads();
+        // the table's maximum and sum
+        float rm = NEG;
+        if (own)
+            for (int j = 0; j < ntag; ++j) rm = fmaxf(rm, crf_pair_arg(avec[j], trow[j], nb));
+        const float M = wave_max(rm);
+        float rs = 0.f;
+        if (own)
+            for (int j = 0; j < ntag; ++j) rs += expf(crf_pair_arg(avec[j], trow[j], nb) - M);
+        const float S = wave_sum(rs);
+        // the quotients: into the accumulator less the gold transition, their row sum into the state marginal
+        float p = 0.f;
+        if (own) {
+            for (int j = 0; j < ntag; ++j) {
+                const float q = expf(crf_pair_arg(avec[j], trow[j], nb) - M) / S;
+                p += q;
+                arow[j] += (double)q - ((lane == ct && j == pt) ? 1.0 : 0.0);
+            }
+            dem_unit[(long long)(r0 + t) * ntag + lane] = p - (lane == ct ? 1.f : 0.f);
+        }
+        if (t == n - 1) {                                   // the terminal transition i -> STOP: row STOP of the accumulator
+            __syncthreads();
+            if (own) s_acc[stop * CRF_ST_STRIDE + lane] += (double)p - (lane == ct ? 1.0 : 0.0);
+        }
+        if (t > 0) {
+            // beta of position t - 1: b[j] = log sum_k exp(tr[k][j] + nb[k]) - max(nb), the lane's COLUMN of the transitions
+            const float* tcol = s_tr + ic;
+            float mx = s_nb[0], m2 = s_nb[0] + tcol[0];
+            for (int k = 1; k < ntag; ++k) {
+                mx = fmaxf(mx, s_nb[k]);
+                m2 = fmaxf(m2, s_nb[k] + tcol[k * CRF_ST_STRIDE]);
+            }
+            float s = 0.f;
+            for (int k = 0; k < ntag; ++k) s += expf((s_nb[k] + tcol[k * CRF_ST_STRIDE]) - m2);
+            b = (m2 - mx) + logf(s);
+        }
+        __syncthreads();
+    }
+    for (int k = lane; k < ntag * ntag; k += 64) {
+        const int i = k / ntag, j = k - i * ntag;
+        dtrans_unit[(long long)d * ntag * ntag + k] = (float)s_acc[i * CRF_ST_STRIDE + j];
+    }
+}
+
+// demissions = (gout[d] / n_d) * dem_unit over the rows of every document, and dtrans += the scaled blocks in document order.
+// Blocks 0 .. tr_blocks - 1 own the transition entries (one thread per entry walks the documents: a fixed order, no atomics);
+// block tr_blocks + d * CRF_ST_CHUNKS + c takes every CRF_ST_CHUNKS-th 256-element slice of document d's rows.
+constexpr int CRF_ST_CHUNKS = 8;
+
+__global__ __launch_bounds__(256) void crf_nll_stable_bwd_kernel(const float* __restrict__ dem_unit, const float* __restrict__ dtrans_unit,
+                                                                 const int* __restrict__ doc_off, int ndoc, int ntag, int tr_blocks,
+                                                                 const float* __restrict__ gout, float* __restrict__ dem,
+                                                                 float* __restrict__ dtrans) {
+    // product and sum are rounded one after the other, never fused into one multiply-add: the ordered fp32 sum of the scaled blocks
+#pragma clang fp contract(off)
+    const int nn = ntag * ntag;
+    if ((int)blockIdx.x < tr_blocks) {
+        const int k = blockIdx.x * 256 + threadIdx.x;
+        if (k >= nn) return;
+        float acc = dtrans[k];
+        for (int d = 0; d < ndoc; ++d) {
+            const int n = doc_off[d + 1] - doc_off[d];
+            if (n <= 0) continue;
+            const float scaled = (gout[d] / (float)n) * dtrans_unit[(long long)d * nn + k];
+            acc = acc + scaled;
+        }
+        dtrans[k] = acc;
+        return;
+    }
+    const int bb = blockIdx.x - tr_blocks;
+    const int d = bb / CRF_ST_CHUNKS, c = bb - d * CRF_ST_CHUNKS;
+    const int r0 = doc_off[d], n = doc_off[d + 1] - r0;
+    if (n <= 0) return;
+    const float g = gout[d] / (float)n;
+    const long long base = (long long)r0 * ntag, total = (long long)n * ntag;
+    for (long long e = (long long)c * 256 + threadIdx.x; e < total; e += CRF_ST_CHUNKS * 256) dem[base + e] = g * dem_unit[base + e];
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* __restrict__ dst) {
     const long long total = n * C;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -460,6 +666,28 @@ extern "C" int vbg_crf_posterior(const float* emissions, const int* doc_off, int
     else if (ntag <= 48) VBG_CRF_POST(48, false);
     else VBG_CRF_POST(64, false);
 #undef VBG_CRF_POST
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_crf_nll_stable(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
+                                  int start_tag, int stop_tag, float* nll, float* logz, float* dem_unit, float* dtrans_unit, void* stream) {
+    VBG_CHECK_ARG(ntag >= 1 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(ndoc >= 0 && (dem_unit == nullptr) == (dtrans_unit == nullptr));
+    if (ndoc == 0) return VBG_OK;
+    VBG_CHECK_ARG(emissions && tags && doc_off && trans && nll && logz);
+    VBG_LAUNCH(crf_nll_stable_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, nll, logz,
+               dem_unit, dtrans_unit);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_crf_nll_stable_bwd(const float* dem_unit, const float* dtrans_unit, const int* doc_off, int ndoc, int ntag,
+                                      const float* gout, float* demissions, float* dtrans_accum, void* stream) {
+    VBG_CHECK_ARG(ntag >= 1 && ntag <= CRF_MAX_TAGS && ndoc >= 0);
+    if (ndoc == 0) return VBG_OK;
+    VBG_CHECK_ARG(dem_unit && dtrans_unit && doc_off && gout && demissions && dtrans_accum);
+    const int tr_blocks = cdiv(ntag * ntag, 256);
+    VBG_LAUNCH(crf_nll_stable_bwd_kernel, dim3(tr_blocks + ndoc * CRF_ST_CHUNKS), dim3(256), 0, S_, dem_unit, dtrans_unit, doc_off, ndoc,
+               ntag, tr_blocks, gout, demissions, dtrans_accum);
     VBG_LAUNCH_RET();
 }
 

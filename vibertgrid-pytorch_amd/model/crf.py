@@ -5,7 +5,8 @@ per-document API (`forward(feats, tags)` -> (log Z - gold score) / len, `inferen
 `decode` take all documents of a batch at once (row ranges `doc_off`), one launch each: forward algorithm + gold score,
 backward = (marginals - gold indicators), Viterbi with first-maximum tie breaking like `torch.max`.  `posterior` adds what the
 reference's prediction path lacks: the same Viterbi path and score together with log Z and the posterior marginals
-p(y_t = i | x) of every row, from one launch (vbg_crf_posterior).
+p(y_t = i | x) of every row, from one launch (vbg_crf_posterior).  With ops.set_crf_stable(True) / VBG_CRF_STABLE=1 `nll` -- and so
+`forward(feats, tags)` -- takes Fn.CrfNllStableFn: the same loss with a gradient whose error does not grow with the document's length.
 """
 from collections import namedtuple
 
@@ -38,7 +39,8 @@ class CRF(nn.Module):
     def nll(self, feats: torch.Tensor, tags_i32: torch.Tensor, doc_off: torch.Tensor) -> torch.Tensor:
         """feats [N, T], tags int32 [N], doc_off int32 [ndoc + 1] -> per-document (log Z - gold) / len, shape [ndoc]"""
         s, e = self._ends()
-        return Fn.CrfNllFn.apply(feats, self.transitions, tags_i32.contiguous(), doc_off, s, e)
+        fn = Fn.CrfNllStableFn if ops.crf_stable_enabled() else Fn.CrfNllFn      # the switch is read at call time (ops.set_crf_stable)
+        return fn.apply(feats, self.transitions, tags_i32.contiguous(), doc_off, s, e)
 
     def decode(self, feats: torch.Tensor, doc_off: torch.Tensor):
         """-> (best tag per row int32 [N], path score per document [ndoc])"""

@@ -1230,6 +1230,28 @@ class CrfNllFn(torch.autograd.Function):
         return dem, dtrans, None, None, None, None
 
 
+class CrfNllStableFn(torch.autograd.Function):
+    """CrfNllFn's loss with a gradient whose error does not grow with the document's length (vbg_crf_nll_stable, include/vbg.h): the
+    forward launch leaves the gradient of n_d * nll[d] in two tables (only when a gradient is to come), backward scales them."""
+
+    @staticmethod
+    def forward(ctx, em, trans, tags, doc_off, start, stop):
+        em, trans = _c(em), _c(trans)
+        want = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        nll, _, dem_unit, dtrans_unit = ops.crf_nll_stable(em, tags, doc_off, trans, start, stop, want)
+        if want:
+            ctx.save_for_backward(dem_unit, dtrans_unit, doc_off)
+        return nll
+
+    @staticmethod
+    def backward(ctx, dnll):
+        dem_unit, dtrans_unit, doc_off = ctx.saved_tensors
+        ntag = dem_unit.shape[1]
+        dtrans = torch.zeros((ntag, ntag), device=dem_unit.device, dtype=f32)
+        dem = ops.crf_nll_stable_bwd(dem_unit, dtrans_unit, doc_off, _c(dnll).to(f32), dtrans)
+        return dem, dtrans, None, None, None, None
+
+
 # ----------------------------------------------------------------------------------------------
 # losses
 # ----------------------------------------------------------------------------------------------

@@ -285,6 +285,8 @@ SIGNATURES = {
     "vbg_crf_viterbi": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_field_decode": (c_int, [c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_d, c_vp, c_vp, c_vp, c_vp]),
     "vbg_crf_posterior": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_crf_nll_stable": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_crf_nll_stable_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_field_decode_tags": (c_int, [c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int, c_d,
                                       c_vp, c_vp, c_vp, c_vp]),
     "vbg_seq_metrics": (c_int, [c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, TagTable, c_vp, c_vp]),

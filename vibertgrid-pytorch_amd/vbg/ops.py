@@ -2646,6 +2646,65 @@ def crf_posterior(em, doc_off, trans, start, stop):
     return path, score, logz, marg
 
 
+_CRF_STABLE = [os.environ.get("VBG_CRF_STABLE", "0") not in ("", "0")]
+
+
+def set_crf_stable(on: bool):
+    """CRF.nll trains through vbg_crf_nll_stable / vbg_crf_nll_stable_bwd: a gradient whose error does not grow with the document's
+    length.  Off by default: the route changes the bits of a training step."""
+    _CRF_STABLE[0] = bool(on)
+
+
+def crf_stable_enabled() -> bool:
+    return _CRF_STABLE[0]
+
+
+def _chk_crf_stable(name, em, doc_off):
+    _chk_f32(em)
+    if em.dim() != 2 or doc_off.dtype != i32 or doc_off.dim() != 1 or doc_off.numel() < 1 or doc_off.device != em.device:
+        raise VbgError(f"{name}: doc_off {doc_off.dtype} {tuple(doc_off.shape)} on {doc_off.device} does not fit rows {tuple(em.shape)} on {em.device}")
+
+
+def crf_nll_stable(em, tags, doc_off, trans, start, stop, want_grad):
+    """-> (nll [ndoc], logz [ndoc], dem_unit [N, ntag] | None, dtrans_unit [ndoc, ntag, ntag] | None) in ONE launch (vbg_crf_nll_stable,
+    include/vbg.h).  The two tables (want_grad) are the gradient of n_d * nll[d] -- marginals less gold indicators -- from pairwise
+    tables that are divided by their own sums; crf_nll_stable_bwd scales them.  No atomics: the deterministic mode takes the same route."""
+    _chk_crf_stable("vbg_crf_nll_stable", em, doc_off)
+    _chk_f32(trans)
+    N, ntag = em.shape
+    ndoc = doc_off.numel() - 1
+    if tuple(trans.shape) != (ntag, ntag) or tags.dtype != i32 or tuple(tags.shape) != (N,) or tags.device != em.device:
+        raise VbgError(f"vbg_crf_nll_stable: trans {tuple(trans.shape)} / tags {tags.dtype} {tuple(tags.shape)} do not fit emissions [{N}, {ntag}]")
+    nll = torch.empty((ndoc,), device=em.device, dtype=f32)
+    logz = torch.empty((ndoc,), device=em.device, dtype=f32)
+    dem_unit = torch.empty((N, ntag), device=em.device, dtype=f32) if want_grad else None
+    dtrans_unit = torch.empty((ndoc, ntag, ntag), device=em.device, dtype=f32) if want_grad else None
+    _seen("crf:nll_stable")
+    check(lib.vbg_crf_nll_stable(P(em.contiguous()), P(tags.contiguous()), P(doc_off), ndoc, P(trans.contiguous()), ntag, start, stop,
+                                 P(nll), P(logz), P(dem_unit), P(dtrans_unit), _stream()), "vbg_crf_nll_stable")
+    return nll, logz, dem_unit, dtrans_unit
+
+
+def crf_nll_stable_bwd(dem_unit, dtrans_unit, doc_off, gout, dtrans):
+    """-> demissions = (gout[d] / n_d) * dem_unit over every document's rows (a new tensor; rows of no document are not written, as
+    in crf_nll_bwd); dtrans [ntag, ntag] += the scaled blocks of dtrans_unit in document order.  ONE launch, no atomics."""
+    _chk_crf_stable("vbg_crf_nll_stable_bwd", dem_unit, doc_off)
+    _chk_f32(dtrans_unit)
+    _chk_f32(gout)
+    _chk_f32(dtrans)
+    N, ntag = dem_unit.shape
+    ndoc = doc_off.numel() - 1
+    if tuple(dtrans_unit.shape) != (ndoc, ntag, ntag) or tuple(dtrans.shape) != (ntag, ntag) or gout.numel() != ndoc:
+        raise VbgError(f"vbg_crf_nll_stable_bwd: dtrans_unit {tuple(dtrans_unit.shape)} / dtrans {tuple(dtrans.shape)} / gout "
+                       f"{tuple(gout.shape)} do not fit {ndoc} documents of [{N}, {ntag}] rows")
+    if not (dem_unit.is_contiguous() and dtrans_unit.is_contiguous() and dtrans.is_contiguous()):
+        raise VbgError("vbg_crf_nll_stable_bwd: the tables and dtrans must be contiguous")
+    dem = torch.empty_like(dem_unit)
+    check(lib.vbg_crf_nll_stable_bwd(P(dem_unit), P(dtrans_unit), P(doc_off), ndoc, ntag, P(gout.contiguous()), P(dem), P(dtrans), _stream()),
+          "vbg_crf_nll_stable_bwd")
+    return dem
+
+
 def field_decode_tags(marginals, path, tag_class, tag_begin, num_classes, doc_off=None, thresh=None):
     """marginals [N, ntag] fp32 and path [N] int32 (device: crf_posterior's) -> (cls int32 [N], score fp32 [N], best float64
     [ndoc * num_classes, 2]) in ONE launch (vbg_field_decode_tags, include/vbg.h).  tag_class / tag_begin: HOST lists of ntag ints (tag ->

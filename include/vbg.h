@@ -940,16 +940,18 @@ int vbg_adam_step_seg_amp(float* p, float* g, float* m, float* v, float* vmax, c
                           const vbg_adam_group_opt* groups, int ngroups, const float* grad_scale, const float* found_inf, void* stream);
 /* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm type 2) without a host sync and without a pass of its own over the
  * gradients: a norm pass over the chunk table the step will walk, a one-block finish that leaves the norm and torch's coefficient in
- * device memory, and the step entries below, which read the coefficient as the *_amp entries read the scale.
- * vbg_grad_sumsq_seg: partials[c] = sum of g[start .. start + length)^2 of row c, c in [0, nchunks) -- a plain store per row (no
+ * device memory, and the step entries below, which read the coefficient as the *_amp entries read the scale.  The library has one
+ * row pass with three entries (vbg_grad_sumsq_seg, vbg_grad_sumsq_seg_inf, vbg_grad_norm_seg) and one finish with two (vbg_clip_coef,
+ * vbg_clip_coef_gate).
+ * vbg_grad_sumsq_seg: the row pass for squares, without flag or gate.  partials[c] = sum of g[start .. start + length)^2 of row c, c in [0, nchunks) -- a plain store per row (no
  *   atomics, nothing to zero, the same bits on every call), summed per thread over its float4s and then over the block, in fp32.
  *   Same table and alignment contract as the segmented steps; the group field is ignored, what no row covers is not read, nchunks == 0
  *   is a no-op.  partials is device memory of >= nchunks floats.
- * vbg_clip_coef: one block sums partials[0 .. n) in double in a fixed order (partials of several tables side by side: one norm over
+ * vbg_clip_coef: the finish for squares, without a gate.  One block sums partials[0 .. n) in double in a fixed order (partials of several tables side by side: one norm over
  *   several optimizers) and writes out[0] = total = (float)sqrt(sum) * norm_scale [* (float)(1.0 / (double)*grad_scale) when grad_scale,
  *   a device scalar, is given: the gradients still hold scaled values] and out[1] = the coefficient in fp32 as torch forms it:
  *   c = (1 / (total + 1e-6f)) * max_norm (torch evaluates `max_norm / tensor` as reciprocal times scalar), out[1] = c > 1 ? 1 : c --
- *   a NaN norm gives NaN, an inf norm 0, n == 0 gives (0, 1).  out: 2 floats of device memory.
+ *   a NaN norm gives NaN, an inf norm 0, n == 0 gives (0, 1).  out: 2 floats of device memory; nothing is stored behind them.
  * vbg_sgd_step_seg_clip / vbg_adam_step_seg_clip: the *_amp entries with clip_coef (device scalar, required; out + 1 above), found_inf
  *   optional (NULL: no scaler) and the host float of the *_seg_opt entries (host_scale, applied inside the rule).  Per chunk, before the
  *   rule: g' = (g * inv) * coef, inv as in the *_amp entries (1 without grad_scale), each product rounded on its own, stored back to g
@@ -974,7 +976,7 @@ int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, float* vmax, 
  * vbg_grad_unscale_check_seg: that torch op over the rows.  *inv_scale == 1.0f (GradScaler._check_inf_per_device): g is only read,
  *   4 B per element.  Otherwise every covered element becomes g * *inv_scale, one rounded fp32 product, non-finite elements included
  *   (as torch stores them): 8 B per element.
- * vbg_grad_sumsq_seg_inf: vbg_grad_sumsq_seg (same partials, bit for bit) with the per-element test in its loop.  The flag comes from
+ * vbg_grad_sumsq_seg_inf: the row pass for squares (the partials of vbg_grad_sumsq_seg, bit for bit) with the per-element test in its loop.  The flag comes from
  *   the elements, not from the sums: finite gradients whose squares overflow leave an inf partial and no flag. */
 int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunks, int nchunks, const float* inv_scale, float* found_inf, void* stream);
 int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, void* stream);
@@ -984,12 +986,12 @@ int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nc
  * gate_f64 == 0 (4-byte aligned); it is open when *gate_loss > gate_threshold, compared in that dtype -- fp32 against
  * (float)gate_threshold, which is what torch compares an fp32 tensor with; strictly greater: a NaN loss closes it, +inf opens it.
  * gate_loss NULL: no gate.  The loss is read by the kernels (one load, uniform over the launch), never by the host.
- * vbg_grad_norm_seg: table, alignment contract and row walk of vbg_grad_sumsq_seg; a plain store per row.  kind 2: partials[c] as
- *   vbg_grad_sumsq_seg leaves it, bit for bit.  kind 1: partials[c] = sum of |g| over row c, summed the same way (per thread over its
+ * vbg_grad_norm_seg: the row pass with every argument it has: table, alignment contract and row walk of vbg_grad_sumsq_seg; a plain store
+ *   per row.  kind 2: partials[c] as vbg_grad_sumsq_seg leaves it, bit for bit (with found_inf: as vbg_grad_sumsq_seg_inf does).  kind 1: partials[c] = sum of |g| over row c, summed the same way (per thread over its
  *   float4s, then over the block, in fp32).  kind 0: partials[c] = max |g| of row c, exact; a NaN anywhere in the row gives a NaN,
  *   +-inf gives +inf.  found_inf (optional, 4-byte aligned): the per-element test of vbg_grad_sumsq_seg_inf, for any kind.  With a gate
  *   that is closed and found_inf NULL every block returns before it touches g or partials; with found_inf the rows always walk.
- * vbg_clip_coef_gate: one block.  Gate closed: out = (0, 1, 0) and no partial is read.  Otherwise total = (float)sqrt(sum in double)
+ * vbg_clip_coef_gate: the finish with every argument it has; one block.  Gate closed: out = (0, 1, 0) and no partial is read.  Otherwise total = (float)sqrt(sum in double)
  *   (kind 2), (float)(sum in double) (kind 1) or the maximum of the partials with a NaN kept (kind 0), then the statements of
  *   vbg_clip_coef (norm_scale, the inverse grad_scale, the coefficient), and out = (total, coefficient, 1).  n == 0: (0, 1, gate).
  *   out: 3 floats of device memory; out + 1 is what the *_seg_clip entries take. */

@@ -340,6 +340,89 @@ def test_ops_wrappers_check_kind_gate_and_buffers():
         ops.clip_coef_gate(z(4), 4, 1.0, out=z(2))
     with pytest.raises(ValueError):
         ops.clip_coef_gate(z(4), 4, 1.0, grad_scale=torch.ones(2))
+    # the rejecting cases of test_what_the_new_arguments_refuse, on the wrappers
+    for wrapper in (lambda gate: ops.grad_norm_seg(z(), ok, z(2), 1, gate=gate), lambda gate: ops.clip_coef_gate(z(4), 4, 1.0, gate=gate)):
+        for _, make, exc, words in BAD_GATES:
+            with pytest.raises(exc, match=words):
+                wrapper(make(loss))
+
+
+# (what, the gate made of a good loss, what clip_in_step raises on it in test_what_the_new_arguments_refuse, its words)
+BAD_GATES = [("a bare tensor", lambda loss: loss, TypeError, None), ("one element", lambda loss: (loss,), TypeError, None),
+             ("three elements", lambda loss: (loss, 1.0, 2.0), TypeError, None), ("a number", lambda loss: 10.0, TypeError, None),
+             ("a float loss", lambda loss: (3.0, 1.0), TypeError, None), ("a numpy loss", lambda loss: (np.float64(3.0), 1.0), TypeError, None),
+             ("an integer loss", lambda loss: (torch.tensor(3), 1.0), TypeError, "fp64 or fp32"),
+             ("a half loss", lambda loss: (torch.tensor(3.0, dtype=torch.float16), 1.0), TypeError, "fp64 or fp32"),
+             ("a bool loss", lambda loss: (torch.tensor(True), 1.0), TypeError, "fp64 or fp32"),
+             ("two losses", lambda loss: (torch.zeros(2, dtype=torch.float64), 1.0), ValueError, "one element"),
+             ("no loss", lambda loss: (torch.zeros(0), 1.0), ValueError, "one element"),
+             ("a loss elsewhere", lambda loss: (torch.zeros((), device="meta"), 1.0), ValueError, "lives on"),
+             ("a tensor threshold", lambda loss: (loss, torch.tensor(1.0)), TypeError, "Python number"),
+             ("a str threshold", lambda loss: (loss, "10"), TypeError, "Python number"),
+             ("no threshold", lambda loss: (loss, None), TypeError, "Python number"), ("a bool threshold", lambda loss: (loss, True), TypeError, "Python number")]
+
+
+@pytest.mark.parametrize("what,make,exc,words", BAD_GATES, ids=[b[0] for b in BAD_GATES])
+def test_one_verdict_on_a_bad_gate(what, make, exc, words):
+    """vbg.optim._clip_gate and the two gated ops wrappers run one statement: the same exception and the same words after the caller's
+    name on every bad gate; a good gate passes all three (the wrappers get as far as refusing host memory)"""
+    from vbg import ops
+    from vbg import optim as vo
+    ok = ops.chunk_table([(0, 8, 0), (8, 64, 1)], 2, 72, "cpu")
+    cpu = torch.device("cpu")
+    gate = make(torch.tensor(3.0, dtype=torch.float64))
+    verdicts = []
+    for call in (lambda: vo._clip_gate(gate, cpu), lambda: ops.grad_norm_seg(torch.zeros(72), ok, torch.zeros(2), 1, gate=gate),
+                 lambda: ops.clip_coef_gate(torch.zeros(4), 4, 1.0, gate=gate)):
+        with pytest.raises(exc, match=words) as e:
+            call()
+        verdicts.append((type(e.value), str(e.value).split(": ", 1)[1]))
+    assert verdicts[0] == verdicts[1] == verdicts[2] and "device memory" not in verdicts[0][1], verdicts
+    good = (torch.tensor(3.0), 1)
+    assert vo._clip_gate(good, cpu)[1] == 1 and vo._clip_gate(list(good), cpu)[0].dtype == torch.float32
+    with pytest.raises(TypeError, match="device memory"):
+        ops.clip_coef_gate(torch.zeros(4), 4, 1.0, gate=good)
+
+
+def _wrapper_calls():
+    """every optimizer wrapper of vbg.ops that takes buffers against a chunk table: name -> (call(**buffers), its buffer arguments)"""
+    from vbg import ops
+    ok = ops.chunk_table([(0, 8, 0), (8, 64, 1)], 2, 72, "cpu")
+    one = torch.ones(1)
+    s3, a5 = [(0.1, 0.9, 0.0)] * 2, [(1e-3, 0.9, 0.999, 1e-8, 0.0)] * 2
+    so, ao = [(0.1, 0.9, 0.0, 0.0, 0)] * 2, [(1e-3, 0.9, 0.999, 1e-8, 0.0, 1, 1)] * 2          # (amsgrad: vmax is a buffer of the launch)
+    return {
+        "sgd_step_seg": (lambda p, g, mom: ops.sgd_step_seg(p, g, mom, ok, s3, True), "p g mom"),
+        "adamw_step_seg": (lambda p, g, m, v: ops.adamw_step_seg(p, g, m, v, ok, a5, 1), "p g m v"),
+        "sgd_step_seg_opt": (lambda p, g, mom: ops.sgd_step_seg_opt(p, g, mom, ok, so), "p g mom"),
+        "adam_step_seg_opt": (lambda p, g, m, v, vmax: ops.adam_step_seg_opt(p, g, m, v, vmax, ok, ao), "p g m v vmax"),
+        "sgd_step_seg_amp": (lambda p, g, mom: ops.sgd_step_seg_amp(p, g, mom, ok, so, one, one), "p g mom"),
+        "adam_step_seg_amp": (lambda p, g, m, v, vmax: ops.adam_step_seg_amp(p, g, m, v, vmax, ok, ao, one, one), "p g m v vmax"),
+        "sgd_step_seg_clip": (lambda p, g, mom: ops.sgd_step_seg_clip(p, g, mom, ok, so, one, one, one), "p g mom"),
+        "adam_step_seg_clip": (lambda p, g, m, v, vmax: ops.adam_step_seg_clip(p, g, m, v, vmax, ok, ao, one, one, one), "p g m v vmax"),
+        "grad_sumsq_seg": (lambda g, partials: ops.grad_sumsq_seg(g, ok, partials), "g partials"),
+        "grad_sumsq_seg_inf": (lambda g, partials: ops.grad_sumsq_seg_inf(g, ok, partials, one), "g partials"),
+        "grad_norm_seg": (lambda g, partials: ops.grad_norm_seg(g, ok, partials, 1, one), "g partials"),
+        "grad_unscale_check_seg": (lambda g: ops.grad_unscale_check_seg(g, ok, one, one), "g"),
+        "clip_coef": (lambda partials, out: ops.clip_coef(partials, 2, 1.0, out=out), "partials out"),
+        "clip_coef_gate": (lambda partials, out: ops.clip_coef_gate(partials, 2, 1.0, out=out), "partials out"),
+    }
+
+
+@pytest.mark.parametrize("name", sorted(_wrapper_calls()))
+def test_every_wrapper_refuses_a_bad_buffer(name):
+    """each buffer argument of each wrapper in turn: fp64, one element short, strided -- a ValueError before a pointer leaves Python"""
+    call, names = _wrapper_calls()[name]
+    names = names.split()
+    need = {"partials": 2, "out": 3 if name == "clip_coef_gate" else 2}
+    with pytest.raises((AssertionError, TypeError)):                                 # well-formed host buffers pass every check but the last
+        call(**{k: torch.zeros(need.get(k, 72)) for k in names})
+    for which in names:
+        n = need.get(which, 72)
+        for bad in (torch.zeros(n, dtype=torch.float64), torch.zeros(n - 1), torch.zeros(2 * n)[::2]):
+            args = {k: (bad if k == which else torch.zeros(need.get(k, 72))) for k in names}
+            with pytest.raises(ValueError):
+                call(**args)
 
 
 # ------------------------------------------------------------------------------------------

@@ -4,11 +4,16 @@ walk; the finish (vbg_clip_coef_gate) against the fp32 restatement of tests/test
 open: the ungated bits, closed: (0, 1, 0) with the partials' canaries untouched; and `vbg.optim.clip_in_step(norm_type=..., when=...)`
 end to end against twins driven by a host `if`, twins that never clip, fp64 torch twins, through a closure step and under torch's
 sync-debug mode.  Shapes and the tolerance `close(..., 1e-6, 1e-7)` are those of tests/test_gpu_clip_step.py.  Needs a real MI355X."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 
 from test_clip_gate_host import INF, KINDS, finish_ref, gate_ref
 from test_gpu_clip_step import _flat_opts
@@ -136,6 +141,27 @@ def test_row_walk_past_the_grid_cap(ops):
     part, out, intact = _norm(ops, g, rows, n + 8, 2)
     table = ops.chunk_table(rows, 2, n + 8, dev())
     assert intact and torch.equal(bits(part), bits(ops.grad_sumsq_seg(g, table, torch.empty(3137, device=dev()))))
+
+
+@pytest.mark.parametrize("table", ["runs", "cap"])
+def test_bits_of_the_recorded_calls(ops, golden, table):
+    """every array of tests/golden/optim_bits.npz bit for bit: the calls of tests/golden/make_golden_optim_bits.py (both row-pass entries for
+    squares, grad_norm_seg of every kind with and without the flag, clip_coef and clip_coef_gate over them), recorded by the commit before
+    grad_sumsq_seg and clip_coef lost their own kernels; "cap" walks past the grid's 2048 blocks.  Canaries and g intact"""
+    import make_golden_optim_bits as M
+    fix = golden("optim_bits.npz")
+    g0 = torch.from_numpy(fix[f"g_{table}"].view(np.float32).copy())
+    cuts = sorted(k[len(f"rows_{table}_"):] for k in fix.files if k.startswith(f"rows_{table}_"))
+    assert cuts == {"runs": ["4096", "64"], "cap": ["8"]}[table]
+    for c in cuts:
+        rows = [tuple(int(v) for v in r) for r in fix[f"rows_{table}_{c}"]]
+        assert len(rows) == {"64": 72, "4096": 8, "8": 2051}[c] and (table != "cap" or len(rows) > 2048)
+        got, intact = M.record(ops, dev(), g0, rows)
+        assert intact, (table, c)
+        want = {k[len(f"{table}_{c}_"):]: fix[k] for k in fix.files if k.startswith(f"{table}_{c}_")}
+        assert sorted(want) == sorted(got) and len(want) == 10
+        for k in sorted(want):
+            assert torch.equal(torch.from_numpy(got[k].view(np.int32)), torch.from_numpy(want[k].view(np.int32))), (table, c, k)
 
 
 PLACES = {"first": 0, "last": 248 + 4104 - 1, "middle": 2300, "gap": 20}

@@ -9,11 +9,11 @@
 // (walk_chunks) and one stream loop (stream_chunk); vbg_sgd_step_seg / vbg_adamw_step_seg translate their groups into the default
 // case of the per-group options that vbg_sgd_step_seg_opt / vbg_adam_step_seg_opt take.  vbg_sgd_step_seg_amp / vbg_adam_step_seg_amp
 // are the AMP instantiation of the same two kernels (SegScale below), and vbg_sgd_step_seg_clip / vbg_adam_step_seg_clip the same
-// instantiation with one more device scalar, the coefficient of a gradient-norm clip that vbg_grad_sumsq_seg (per-row sums of squares
-// over the same chunk table) and vbg_clip_coef (their sum in double, torch's coefficient) leave in device memory.  The same row walk
-// carries GradScaler's own pass over the gradients: vbg_grad_unscale_check_seg (its inf check and unscale_) and vbg_grad_sumsq_seg_inf
-// (the norm pass with that check riding along).  vbg_grad_norm_seg / vbg_clip_coef_gate are the norm pass and its finish for norm types
-// 2, 1 and inf with the reference's loss gate (`if train_loss > loss_clip_tresh`) read from device memory by the kernels themselves.
+// instantiation with one more device scalar, the coefficient of a gradient-norm clip.  That coefficient comes from two more kernels on
+// the same chunk table: one row pass (grad_norm_seg_kernel: a partial per row, GradScaler's inf check and the reference's loss gate riding
+// along; entries vbg_grad_sumsq_seg, vbg_grad_sumsq_seg_inf, vbg_grad_norm_seg) and one finish (clip_coef_gate_kernel: the total norm and
+// torch's coefficient; entries vbg_clip_coef, vbg_clip_coef_gate).  vbg_grad_unscale_check_seg, GradScaler's own pass (it stores into g),
+// walks the same rows.
 #include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
@@ -271,11 +271,12 @@ __global__ void __launch_bounds__(SEG_THREADS) adam_seg_kernel(float* __restrict
     });
 }
 
-// ---- gradient-norm clipping on the device ------------------------------------------------------------------------------
-// The norm pass on the same row walk: block b on row c leaves partials[c] = sum of g[start .. start + length)^2, a plain store (no
-// atomics, nothing to zero beforehand, the same bits on every call).  A thread sums the squares of its own float4s in fp32 (a row of
-// 4096 elements: 4 float4s, 16 products), block_sum adds the 256 thread sums: a short fp32 chain per row, the long sum over rows is
-// left to clip_coef_kernel, in double.  The group field of a row is ignored; what no row covers is not read.
+// ---- gradient-norm clipping on the device: the row pass -----------------------------------------------------------------
+// One kernel on the row walk of the steps: block b on row c leaves partials[c], a plain store (no atomics, nothing to zero beforehand,
+// the same bits on every call).  KIND 2: the sum of g[start .. start + length)^2 -- a thread sums the squares of its own float4s in fp32
+// (a row of 4096 elements: 4 float4s, 16 products), block_sum adds the 256 thread sums: a short fp32 chain per row, the long sum over
+// rows is left to the finish, in double.  KIND 1 sums |g| the same way (fabsf rounds nothing), KIND 0 leaves max |g| of the row.  The
+// group field of a row is ignored; what no row covers is not read.
 // GradScaler's test of four elements, carried as a sum: x * 0 is a zero for a finite x and NaN for an inf or a NaN, so z stays a zero
 // exactly as long as everything folded into it was finite (torch's isfinite, element by element) -- one fused multiply-add per element,
 // the arithmetic of the norm pass's own loop, and nothing to branch on.  IEEE semantics: this library is not built with finite-math
@@ -294,91 +295,10 @@ __device__ __forceinline__ void raise_found_inf(bool bad, float* __restrict__ fo
     if (__syncthreads_or(bad) && threadIdx.x == 0) *found_inf = 1.f;
 }
 
-// CHECK (vbg_grad_sumsq_seg_inf): the same walk, sums and stores, with GradScaler's inf check riding in the loop -- decided per ELEMENT
-// (a row of finite values whose squares overflow leaves an inf partial and the flag alone).  found_inf is not read without CHECK.
-template <bool CHECK>
-__global__ void __launch_bounds__(SEG_THREADS) grad_sumsq_seg_kernel(const float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
-                                                                      float* __restrict__ partials, float* __restrict__ found_inf) {
-    __shared__ float sh[16];
-    int c = blockIdx.x;
-    float z = 0.f;
-    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
-        const float4* g4 = reinterpret_cast<const float4*>(g + ch.start);
-        const int n4 = ch.length >> 2;
-        float acc = 0.f;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-            const float4 gv = g4[i];
-            if constexpr (CHECK) fold_finite4(z, gv);
-            acc += gv.x * gv.x;
-            acc += gv.y * gv.y;
-            acc += gv.z * gv.z;
-            acc += gv.w * gv.w;
-        }
-        const float r = block_sum(acc, sh);
-        if (threadIdx.x == 0) partials[c] = r;
-        c += (int)gridDim.x;
-    });
-    if constexpr (CHECK) raise_found_inf(!(z == 0.f), found_inf);
-}
-
-// torch._amp_foreach_non_finite_check_and_unscale_ over the rows of a chunk table (GradScaler._unscale_grads_ on gradients that are views
-// of one flat buffer): every covered element is tested, then replaced by g * inv, one rounded product, non-finite ones included -- unless
-// inv is exactly 1 (GradScaler's check-only call), when g is only read: 4 B per element instead of 8.  inv is uniform over the launch.
-__global__ void __launch_bounds__(SEG_THREADS) grad_unscale_check_seg_kernel(float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
-                                                                              const float* __restrict__ inv_scale, float* __restrict__ found_inf) {
-    const float inv = *inv_scale;
-    const bool store = inv != 1.f;
-    float z = 0.f;
-    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
-        float4* g4 = reinterpret_cast<float4*>(g + ch.start);
-        const int n4 = ch.length >> 2;
-        if (store) {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
-                float4 gv = g4[i];
-                fold_finite4(z, gv);
-                gv.x = __fmul_rn(gv.x, inv); gv.y = __fmul_rn(gv.y, inv); gv.z = __fmul_rn(gv.z, inv); gv.w = __fmul_rn(gv.w, inv);
-                g4[i] = gv;
-            }
-        } else {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) fold_finite4(z, g4[i]);
-        }
-    });
-    raise_found_inf(!(z == 0.f), found_inf);
-}
-
-// The finish: partials[0 .. n) summed in double in a fixed order (thread t takes t, t + T, ...; then a fixed tree), and the two fp32
-// numbers a clip needs: out[0] = the total norm, out[1] = the coefficient in torch's own statements --
-// `max_norm / (total_norm + 1e-6)` is `(total_norm + 1e-6).reciprocal() * max_norm` there, then `clamp(max=1.0)`, which keeps a NaN
-// (fminf would not) and turns an inf norm into 0.
-constexpr int COEF_THREADS = 256;
-__global__ void __launch_bounds__(COEF_THREADS) clip_coef_kernel(const float* __restrict__ partials, int n, float max_norm, float norm_scale,
-                                                                  const float* __restrict__ grad_scale, float* __restrict__ out) {
-    __shared__ double sh[COEF_THREADS];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += COEF_THREADS) s += (double)partials[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = COEF_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float total = __fmul_rn((float)sqrt(sh[0]), norm_scale);
-        if (grad_scale) total = __fmul_rn(total, (float)(1.0 / (double)*grad_scale));          // (the gradients still hold scaled values)
-        const float c = __fmul_rn(__fdiv_rn(1.f, __fadd_rn(total, 1e-6f)), max_norm);
-        out[0] = total;
-        out[1] = c > 1.f ? 1.f : c;
-    }
-}
-
-// ---- the loss gate and the other norm types (vbg_grad_norm_seg / vbg_clip_coef_gate) ------------------------------------
-// The reference clips only `if train_loss > loss_clip_tresh` (pipeline/train_val_utils.py:281), a host read of a device scalar.  Here
-// the loss stays where it is: both kernels read it (one load, uniform over the launch) and take torch's own decision, `loss > threshold`
-// in the loss tensor's dtype -- strictly greater, so a NaN loss closes the gate and +inf opens it; thr32 is the threshold rounded to
-// fp32 on the host, which is what torch compares an fp32 tensor with.  loss NULL: no gate.
+// The loss gate.  The reference clips only `if train_loss > loss_clip_tresh` (pipeline/train_val_utils.py:281), a host read of a device
+// scalar.  Here the loss stays where it is: the row pass and the finish read it (one load, uniform over the launch) and take torch's own
+// decision, `loss > threshold` in the loss tensor's dtype -- strictly greater, so a NaN loss closes the gate and +inf opens it; thr32 is
+// the threshold rounded to fp32 on the host, which is what torch compares an fp32 tensor with.  loss NULL (ClipGate{}): no gate.
 struct ClipGate { const void* loss; double thr64; float thr32; int f64; };
 
 __device__ __forceinline__ bool gate_open(const ClipGate& gt) {
@@ -405,10 +325,9 @@ __device__ __forceinline__ unsigned block_max_bits(unsigned v, unsigned* sh) {
 
 __device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 
-// The row pass of grad_sumsq_seg_kernel for the three norm types: KIND 2 sums squares in its very statements (the same partials, bit
-// for bit), KIND 1 sums |g| the same way (fabsf rounds nothing), KIND 0 leaves max |g| of the row.  A plain store per row, no atomics.
-// Without CHECK a closed gate makes every block return before it touches g or partials; with CHECK (GradScaler's flag rides in the
-// loop) the rows always walk and only the finish reads the gate.
+// CHECK: GradScaler's inf check rides in the loop -- decided per ELEMENT (a row of finite values whose squares overflow leaves an inf
+// partial and the flag alone); found_inf is not read without CHECK.  Without CHECK a closed gate makes every block return before it
+// touches g or partials; with CHECK the rows always walk and only the finish reads the gate.
 template <int KIND, bool CHECK>
 __global__ void __launch_bounds__(SEG_THREADS) grad_norm_seg_kernel(const float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
                                                                      float* __restrict__ partials, float* __restrict__ found_inf, ClipGate gate) {
@@ -451,18 +370,50 @@ __global__ void __launch_bounds__(SEG_THREADS) grad_norm_seg_kernel(const float*
     if constexpr (CHECK) raise_found_inf(!(z == 0.f), found_inf);
 }
 
-// The finish of clip_coef_kernel for the three norm types and the gate: KIND 2 and 1 sum the partials in double in its fixed order
-// (then sqrt for 2), KIND 0 takes their maximum with a NaN kept; the statements after that are clip_coef_kernel's.  Three floats:
-// out[0] = total, out[1] = coefficient, out[2] = 1.0f (gate open, or no gate) / 0.0f.  A closed gate leaves (0, 1, 0) and reads no partial.
+// torch._amp_foreach_non_finite_check_and_unscale_ over the rows of a chunk table (GradScaler._unscale_grads_ on gradients that are views
+// of one flat buffer): every covered element is tested, then replaced by g * inv, one rounded product, non-finite ones included -- unless
+// inv is exactly 1 (GradScaler's check-only call), when g is only read: 4 B per element instead of 8.  inv is uniform over the launch.
+__global__ void __launch_bounds__(SEG_THREADS) grad_unscale_check_seg_kernel(float* __restrict__ g, const vbg_optim_chunk* __restrict__ tbl, int nchunks,
+                                                                              const float* __restrict__ inv_scale, float* __restrict__ found_inf) {
+    const float inv = *inv_scale;
+    const bool store = inv != 1.f;
+    float z = 0.f;
+    walk_chunks(tbl, nchunks, [&](const vbg_optim_chunk& ch) {
+        float4* g4 = reinterpret_cast<float4*>(g + ch.start);
+        const int n4 = ch.length >> 2;
+        if (store) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) {
+                float4 gv = g4[i];
+                fold_finite4(z, gv);
+                gv.x = __fmul_rn(gv.x, inv); gv.y = __fmul_rn(gv.y, inv); gv.z = __fmul_rn(gv.z, inv); gv.w = __fmul_rn(gv.w, inv);
+                g4[i] = gv;
+            }
+        } else {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int i = threadIdx.x; i < n4; i += SEG_THREADS) fold_finite4(z, g4[i]);
+        }
+    });
+    raise_found_inf(!(z == 0.f), found_inf);
+}
+
+// ---- gradient-norm clipping on the device: the finish ------------------------------------------------------------------
+// One block: partials[0 .. n) folded in double in a fixed order (thread t takes t, t + T, ...; then a fixed tree) -- summed for KIND 2
+// (then sqrt) and KIND 1, their maximum with a NaN kept for KIND 0 -- and the fp32 numbers a clip needs: out[0] = the total norm,
+// out[1] = the coefficient in torch's own statements -- `max_norm / (total_norm + 1e-6)` is `(total_norm + 1e-6).reciprocal() * max_norm`
+// there, then `clamp(max=1.0)`, which keeps a NaN (fminf would not) and turns an inf norm into 0 -- and, where nout == 3 (vbg_clip_coef
+// has two floats: nothing is stored behind out[1]), out[2] = 1.0f (gate open, or no gate) / 0.0f.  A closed gate leaves (0, 1, 0) and
+// reads no partial.
+constexpr int COEF_THREADS = 256;
 template <int KIND>
 __global__ void __launch_bounds__(COEF_THREADS) clip_coef_gate_kernel(const float* __restrict__ partials, int n, float max_norm, float norm_scale,
-                                                                       const float* __restrict__ grad_scale, ClipGate gate, float* __restrict__ out) {
+                                                                       const float* __restrict__ grad_scale, ClipGate gate, float* __restrict__ out, int nout) {
     __shared__ double sh[COEF_THREADS];
     if (!gate_open(gate)) {
         if (threadIdx.x == 0) {
             out[0] = 0.f;
             out[1] = 1.f;
-            out[2] = 0.f;
+            if (nout > 2) out[2] = 0.f;
         }
         return;
     }
@@ -497,7 +448,7 @@ __global__ void __launch_bounds__(COEF_THREADS) clip_coef_gate_kernel(const floa
         const float c = __fmul_rn(__fdiv_rn(1.f, __fadd_rn(total, 1e-6f)), max_norm);
         out[0] = total;
         out[1] = c > 1.f ? 1.f : c;
-        out[2] = 1.f;
+        if (nout > 2) out[2] = 1.f;
     }
 }
 
@@ -673,24 +624,44 @@ extern "C" int vbg_adam_step_seg_clip(float* p, float* g, float* m, float* v, fl
                                    stream);
 }
 
-extern "C" int vbg_grad_sumsq_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, void* stream) {
-    VBG_CHECK_ARG(nchunks >= 0);
+// ---- the entries of the row pass (three) and of the finish (two) ----------------------------------------------------------
+// kind 2 / 1 / 0 is norm type 2, 1 and inf; gate_loss: a device scalar, fp64 when gate_f64, fp32 otherwise, NULL for no gate
+static inline bool gate_args(const void* loss, int f64) { return (f64 == 0 || f64 == 1) && (uintptr_t)loss % (f64 ? 8 : 4) == 0; }
+static inline ClipGate make_gate(const void* loss, int f64, double threshold) { return ClipGate{loss, threshold, (float)threshold, f64}; }
+
+// a checked kind -> f(std::integral_constant<int, KIND>{}), the template argument of both kernels
+template <class F>
+static int with_kind(int kind, F f) {
+    if (kind == 2) return f(std::integral_constant<int, 2>{});
+    if (kind == 1) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 0>{});
+}
+
+// found_inf (4-byte aligned, checked by the entry) selects CHECK; an empty table launches nothing and looks at no other pointer
+template <int KIND>
+static int grad_norm_seg_launch(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, ClipGate gate,
+                                void* stream) {
     if (nchunks == 0) return VBG_OK;
     VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
-    VBG_LAUNCH(grad_sumsq_seg_kernel<false>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials,
-               (float*)nullptr);
+    if (found_inf)
+        VBG_LAUNCH((grad_norm_seg_kernel<KIND, true>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
+                   partials, found_inf, gate);
+    else
+        VBG_LAUNCH((grad_norm_seg_kernel<KIND, false>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
+                   partials, found_inf, gate);
     VBG_LAUNCH_RET();
 }
 
-// GradScaler's hooks (vbg.optim.fuse_scaler).  The two device scalars are required and 4-byte aligned, whatever nchunks is; the flag is
+extern "C" int vbg_grad_sumsq_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, void* stream) {
+    VBG_CHECK_ARG(nchunks >= 0);
+    return grad_norm_seg_launch<2>(g, chunks, nchunks, partials, nullptr, ClipGate{}, stream);
+}
+
+// GradScaler's hooks (vbg.optim.fuse_scaler).  Their device scalars are required and 4-byte aligned, whatever nchunks is; the flag is
 // only ever set.
 extern "C" int vbg_grad_sumsq_seg_inf(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, void* stream) {
     VBG_CHECK_ARG(nchunks >= 0 && found_inf && (uintptr_t)found_inf % 4 == 0);
-    if (nchunks == 0) return VBG_OK;
-    VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
-    VBG_LAUNCH(grad_sumsq_seg_kernel<true>, dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks, partials,
-               found_inf);
-    VBG_LAUNCH_RET();
+    return grad_norm_seg_launch<2>(g, chunks, nchunks, partials, found_inf, ClipGate{}, stream);
 }
 
 extern "C" int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunks, int nchunks, const float* inv_scale, float* found_inf, void* stream) {
@@ -702,51 +673,31 @@ extern "C" int vbg_grad_unscale_check_seg(float* g, const vbg_optim_chunk* chunk
     VBG_LAUNCH_RET();
 }
 
-extern "C" int vbg_clip_coef(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, float* out, void* stream) {
-    VBG_CHECK_ARG(n >= 0 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 && (uintptr_t)grad_scale % 4 == 0);
-    VBG_LAUNCH(clip_coef_kernel, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, out);
-    VBG_LAUNCH_RET();
-}
-
-// The row pass and the finish for norm types 2, 1 and inf (kind 2 / 1 / 0) with the loss gate of clip_in_step(when=...): gate_loss is a
-// device scalar (fp64 when gate_f64, fp32 otherwise; NULL: no gate), the gate is open when *gate_loss > gate_threshold in that dtype.
-// found_inf is optional here (NULL: no check); with it the rows walk whatever the gate says.
-static inline bool gate_args(const void* loss, int f64) { return (f64 == 0 || f64 == 1) && (uintptr_t)loss % (f64 ? 8 : 4) == 0; }
-static inline ClipGate make_gate(const void* loss, int f64, double threshold) { return ClipGate{loss, threshold, (float)threshold, f64}; }
-
-template <int KIND>
-static int grad_norm_seg_launch(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, float* found_inf, ClipGate gate,
-                                void* stream) {
-    if (found_inf)
-        VBG_LAUNCH((grad_norm_seg_kernel<KIND, true>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
-                   partials, found_inf, gate);
-    else
-        VBG_LAUNCH((grad_norm_seg_kernel<KIND, false>), dim3(ew_grid(nchunks, 1)), dim3(SEG_THREADS), 0, (hipStream_t)stream, g, chunks, nchunks,
-                   partials, found_inf, gate);
-    VBG_LAUNCH_RET();
-}
-
+// found_inf is optional here (NULL: no check); with it the rows walk whatever the gate says
 extern "C" int vbg_grad_norm_seg(const float* g, const vbg_optim_chunk* chunks, int nchunks, float* partials, int kind, float* found_inf,
                                  const void* gate_loss, int gate_f64, double gate_threshold, void* stream) {
     VBG_CHECK_ARG(nchunks >= 0 && kind >= 0 && kind <= 2 && (uintptr_t)found_inf % 4 == 0 && gate_args(gate_loss, gate_f64));
-    if (nchunks == 0) return VBG_OK;
-    VBG_CHECK_ARG(g && chunks && partials && ALIGNED16(g) && ALIGNED16(chunks) && (uintptr_t)partials % 4 == 0);
     const ClipGate gate = make_gate(gate_loss, gate_f64, gate_threshold);
-    if (kind == 2) return grad_norm_seg_launch<2>(g, chunks, nchunks, partials, found_inf, gate, stream);
-    if (kind == 1) return grad_norm_seg_launch<1>(g, chunks, nchunks, partials, found_inf, gate, stream);
-    return grad_norm_seg_launch<0>(g, chunks, nchunks, partials, found_inf, gate, stream);
+    return with_kind(kind, [&](auto k) { return grad_norm_seg_launch<k()>(g, chunks, nchunks, partials, found_inf, gate, stream); });
+}
+
+// one block whatever n is (n == 0: nothing is read); `out` has nout floats, 4-byte aligned like the other device scalars
+template <int KIND>
+static int clip_coef_launch(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, ClipGate gate, float* out,
+                            int nout, void* stream) {
+    VBG_CHECK_ARG(n >= 0 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 && (uintptr_t)grad_scale % 4 == 0);
+    VBG_LAUNCH(clip_coef_gate_kernel<KIND>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate,
+               out, nout);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_clip_coef(const float* partials, int n, float max_norm, float norm_scale, const float* grad_scale, float* out, void* stream) {
+    return clip_coef_launch<2>(partials, n, max_norm, norm_scale, grad_scale, ClipGate{}, out, 2, stream);
 }
 
 extern "C" int vbg_clip_coef_gate(const float* partials, int n, int kind, float max_norm, float norm_scale, const float* grad_scale,
                                   const void* gate_loss, int gate_f64, double gate_threshold, float* out, void* stream) {
-    VBG_CHECK_ARG(n >= 0 && kind >= 0 && kind <= 2 && out && (uintptr_t)out % 4 == 0 && (partials || n == 0) && (uintptr_t)partials % 4 == 0 &&
-                  (uintptr_t)grad_scale % 4 == 0 && gate_args(gate_loss, gate_f64));
+    VBG_CHECK_ARG(kind >= 0 && kind <= 2 && gate_args(gate_loss, gate_f64));
     const ClipGate gate = make_gate(gate_loss, gate_f64, gate_threshold);
-    if (kind == 2)
-        VBG_LAUNCH(clip_coef_gate_kernel<2>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
-    else if (kind == 1)
-        VBG_LAUNCH(clip_coef_gate_kernel<1>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
-    else
-        VBG_LAUNCH(clip_coef_gate_kernel<0>, dim3(1), dim3(COEF_THREADS), 0, (hipStream_t)stream, partials, n, max_norm, norm_scale, grad_scale, gate, out);
-    VBG_LAUNCH_RET();
+    return with_kind(kind, [&](auto k) { return clip_coef_launch<k()>(partials, n, max_norm, norm_scale, grad_scale, gate, out, 3, stream); });
 }

@@ -2800,12 +2800,55 @@ def chunk_table(chunks, ngroups, numel, device):
     return ChunkTable(rows, len(c), int(ngroups), int(numel))
 
 
+def _table_bufs(what, table, *bufs):
+    """every buffer a segmented launch walks: contiguous fp32 on the table's device, covering the table"""
+    for b in bufs:
+        if b.dtype != f32 or not b.is_contiguous() or b.numel() < table.numel or b.device != table.rows.device:
+            raise ValueError(f"{what}: contiguous fp32 buffers on the table's device, at least as long as the table's numel")
+
+
+def _row_pass_args(g, table, partials, optional=(), **found_inf):
+    """the operands of a row pass: g covering the table, one fp32 partial per row, GradScaler's flag where the entry takes one"""
+    _table_bufs("segmented gradient norm", table, g)
+    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
+        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
+    _one_f32("segmented inf check", table.rows.device, optional, **found_inf)
+
+
+def _one_f32(what, device, optional=(), **scalars):
+    """the device scalars of a launch, by name: one fp32 element each on `device`; those named in `optional` may be None"""
+    for name, t in scalars.items():
+        if t is None and name in optional:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != device:
+            raise ValueError(f"{what}: {name} must be one fp32 element on the launch's device ({device})")
+
+
 def _seg_args(table, groups, *bufs):
     if len(groups) != table.ngroups:
         raise ValueError(f"{len(groups)} sets of hyper-parameters for a chunk table over {table.ngroups} groups")
-    for b in bufs:
-        if b.dtype != f32 or not b.is_contiguous() or b.numel() < table.numel or b.device != table.rows.device:
-            raise ValueError("segmented optimizer step: contiguous fp32 buffers on the table's device, at least as long as the table's numel")
+    _table_bufs("segmented optimizer step", table, *bufs)
+
+
+def _sgd_opts(p, g, mom, table, groups, keep_mom=False, optional=(), **scalars):
+    """what the vbg_sgd_step_seg_{opt,amp,clip} wrappers share: the buffers (mom: None when no group needs it) and the launch's device
+    scalars checked -> the vbg_sgd_group_opt array of groups = [(lr, momentum, dampening, weight_decay, flags)]"""
+    _seg_args(table, groups, p, g, *(() if mom is None else (mom,)))
+    if mom is None and (keep_mom or any(float(h[1]) != 0.0 for h in groups)):
+        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
+    _one_f32("segmented optimizer step", table.rows.device, optional, **scalars)
+    return (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
+
+
+def _adam_opts(p, g, m, v, vmax, table, groups, optional=(), **scalars):
+    """the same for vbg_adam_step_seg_{opt,amp,clip} (vmax: None when no group has the amsgrad flag) -> the vbg_adam_group_opt array of
+    groups = [(lr, beta1, beta2, eps, weight_decay, step, flags)]"""
+    _seg_args(table, groups, p, g, m, v, *(() if vmax is None else (vmax,)))
+    if vmax is None and any(int(h[6]) & 1 for h in groups):
+        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
+    _one_f32("segmented optimizer step", table.rows.device, optional, **scalars)
+    return (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
+                                          for h in groups])
 
 
 def sgd_step_seg(p, g, mom, table, groups, first, grad_scale=1.0):
@@ -2825,148 +2868,76 @@ def adamw_step_seg(p, g, m, v, table, groups, step, grad_scale=1.0):
 def sgd_step_seg_opt(p, g, mom, table, groups, grad_scale=1.0):
     """vbg_sgd_step_seg_opt: groups = [(lr, momentum, dampening, weight_decay, flags)] per group of `table`, flags of vbg.lib SGD_*; one
     launch.  mom: None when every group has momentum 0 (the buffer is not touched then)"""
-    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
-    if mom is None and any(float(h[1]) != 0.0 for h in groups):
-        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
-    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
-    check(lib.vbg_sgd_step_seg_opt(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), grad_scale, _stream()),
-          "vbg_sgd_step_seg_opt")
+    hp = _sgd_opts(p, g, mom, table, groups)
+    check(lib.vbg_sgd_step_seg_opt(P(p), P(g), P(mom), P(table.rows), table.n, hp, len(groups), grad_scale, _stream()), "vbg_sgd_step_seg_opt")
 
 
 def adam_step_seg_opt(p, g, m, v, vmax, table, groups, grad_scale=1.0):
     """vbg_adam_step_seg_opt: groups = [(lr, beta1, beta2, eps, weight_decay, step, flags)] per group of `table`, flags of vbg.lib ADAM_*;
     one launch.  vmax: None when no group has the amsgrad flag"""
-    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
-    if vmax is None and any(int(h[6]) & 1 for h in groups):
-        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
-    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
-                                        for h in groups])
-    check(lib.vbg_adam_step_seg_opt(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), grad_scale,
-                                    _stream()), "vbg_adam_step_seg_opt")
-
-
-def _amp_scalars(table, grad_scale, found_inf):
-    """the two scalars of GradScaler's protocol: fp32, one element each, on the table's device; grad_scale may be None"""
-    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
-        if t is None and name == "grad_scale":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
-            raise ValueError(f"segmented AMP optimizer step: {name} must be one fp32 element on the table's device")
-    return (None if grad_scale is None else P(grad_scale)), P(found_inf)
+    hp = _adam_opts(p, g, m, v, vmax, table, groups)
+    check(lib.vbg_adam_step_seg_opt(P(p), P(g), P(m), P(v), P(vmax), P(table.rows), table.n, hp, len(groups), grad_scale, _stream()),
+          "vbg_adam_step_seg_opt")
 
 
 def sgd_step_seg_amp(p, g, mom, table, groups, grad_scale, found_inf):
     """vbg_sgd_step_seg_amp: sgd_step_seg_opt with the scale (a device scalar, or None: g is unscaled already) and GradScaler's inf flag
     (a device scalar; non-zero: the launch does nothing) read by the kernel; g is overwritten with the unscaled gradient"""
-    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
-    if mom is None and any(float(h[1]) != 0.0 for h in groups):
-        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
-    sc, fi = _amp_scalars(table, grad_scale, found_inf)
-    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
-    check(lib.vbg_sgd_step_seg_amp(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), sc, fi, _stream()),
+    hp = _sgd_opts(p, g, mom, table, groups, False, ("grad_scale",), grad_scale=grad_scale, found_inf=found_inf)
+    check(lib.vbg_sgd_step_seg_amp(P(p), P(g), P(mom), P(table.rows), table.n, hp, len(groups), P(grad_scale), P(found_inf), _stream()),
           "vbg_sgd_step_seg_amp")
 
 
 def adam_step_seg_amp(p, g, m, v, vmax, table, groups, grad_scale, found_inf):
     """vbg_adam_step_seg_amp: adam_step_seg_opt under the same protocol (see sgd_step_seg_amp)"""
-    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
-    if vmax is None and any(int(h[6]) & 1 for h in groups):
-        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
-    sc, fi = _amp_scalars(table, grad_scale, found_inf)
-    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
-                                        for h in groups])
-    check(lib.vbg_adam_step_seg_amp(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), sc, fi,
+    hp = _adam_opts(p, g, m, v, vmax, table, groups, ("grad_scale",), grad_scale=grad_scale, found_inf=found_inf)
+    check(lib.vbg_adam_step_seg_amp(P(p), P(g), P(m), P(v), P(vmax), P(table.rows), table.n, hp, len(groups), P(grad_scale), P(found_inf),
                                     _stream()), "vbg_adam_step_seg_amp")
 
 
-def _clip_scalars(table, grad_scale, found_inf, clip_coef):
-    """the device scalars of the *_seg_clip entries: fp32, one element each, on the table's device; only clip_coef is required"""
-    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf), ("clip_coef", clip_coef)):
-        if t is None and name != "clip_coef":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
-            raise ValueError(f"segmented clipping optimizer step: {name} must be one fp32 element on the table's device")
-    return (None if grad_scale is None else P(grad_scale)), (None if found_inf is None else P(found_inf)), P(clip_coef)
+def sgd_step_seg_clip(p, g, mom, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0, keep_mom=False):
+    """vbg_sgd_step_seg_clip: sgd_step_seg_amp with the clip coefficient (a device scalar, required) applied to g after the unscale;
+    found_inf may be None (no scaler); host_scale: the host float of sgd_step_seg_opt; keep_mom: momentum-0 groups write `mom` as in
+    sgd_step_seg.  g is overwritten with the unscaled, clipped gradient"""
+    hp = _sgd_opts(p, g, mom, table, groups, keep_mom, ("grad_scale", "found_inf"), grad_scale=grad_scale, found_inf=found_inf, clip_coef=clip_coef)
+    check(lib.vbg_sgd_step_seg_clip(P(p), P(g), P(mom), P(table.rows), table.n, hp, len(groups), P(grad_scale), P(found_inf), P(clip_coef),
+                                    float(host_scale), int(bool(keep_mom)), _stream()), "vbg_sgd_step_seg_clip")
 
 
-def grad_sumsq_seg(g, table, partials):
-    """vbg_grad_sumsq_seg: partials[c] = sum of squares of row c of `table` (a ChunkTable) over g, c in [0, table.n); one launch, plain
-    stores in a fixed order (the same code in deterministic mode)"""
-    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
-        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
-    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
-        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
-    check(lib.vbg_grad_sumsq_seg(P(g), P(table.rows), table.n, P(partials), _stream()), "vbg_grad_sumsq_seg")
-    return partials
-
-
-def _scaler_scalars(table, **scalars):
-    """the device scalars of GradScaler's hooks: fp32, one element each, on the table's device, all required"""
-    for name, t in scalars.items():
-        if not isinstance(t, torch.Tensor) or t.dtype != f32 or t.numel() != 1 or t.device != table.rows.device:
-            raise ValueError(f"segmented inf check: {name} must be one fp32 element on the table's device")
-
-
-def grad_unscale_check_seg(g, table, inv_scale, found_inf):
-    """vbg_grad_unscale_check_seg: torch._amp_foreach_non_finite_check_and_unscale_ over the rows of `table` (a ChunkTable) of g; one launch.
-    found_inf (a device scalar the caller zeroed) becomes 1.0 when a covered element is inf or NaN and is left alone otherwise;
-    inv_scale (a device scalar): exactly 1.0 -> g is only read, anything else -> every covered element is overwritten with g * inv_scale"""
-    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
-        raise ValueError("segmented inf check: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
-    _scaler_scalars(table, inv_scale=inv_scale, found_inf=found_inf)
-    _untag(g)          # (written through the raw pointer: torch's version counter does not move)
-    check(lib.vbg_grad_unscale_check_seg(P(g), P(table.rows), table.n, P(inv_scale), P(found_inf), _stream()), "vbg_grad_unscale_check_seg")
-    return found_inf
-
-
-def grad_sumsq_seg_inf(g, table, partials, found_inf):
-    """vbg_grad_sumsq_seg_inf: grad_sumsq_seg (the same partials, bit for bit) with GradScaler's inf check in the same pass over g:
-    found_inf as in grad_unscale_check_seg, decided by the elements, not by the sums"""
-    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
-        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
-    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
-        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
-    _scaler_scalars(table, found_inf=found_inf)
-    check(lib.vbg_grad_sumsq_seg_inf(P(g), P(table.rows), table.n, P(partials), P(found_inf), _stream()), "vbg_grad_sumsq_seg_inf")
-    return partials
-
-
-def clip_coef(partials, n, max_norm, norm_scale=1.0, grad_scale=None, out=None):
-    """vbg_clip_coef: -> out (2 fp32: total norm, clip coefficient) from partials[0 .. n); grad_scale: a device scalar when the gradients
-    still hold scaled values.  One small launch, no host sync"""
-    if partials.dtype != f32 or not partials.is_contiguous() or not 0 <= n <= partials.numel():
-        raise ValueError("clip coefficient: partials must be contiguous fp32 with at least n elements")
-    if out is None:
-        out = torch.empty((2,), device=partials.device, dtype=f32)
-    if out.dtype != f32 or not out.is_contiguous() or out.numel() < 2 or out.device != partials.device:
-        raise ValueError("clip coefficient: out must be two contiguous fp32 elements on the partials' device")
-    if grad_scale is not None and (not isinstance(grad_scale, torch.Tensor) or grad_scale.dtype != f32 or grad_scale.numel() != 1
-                                   or grad_scale.device != partials.device):
-        raise ValueError("clip coefficient: grad_scale must be one fp32 element on the partials' device")
-    check(lib.vbg_clip_coef(P(partials), int(n), float(max_norm), float(norm_scale), None if grad_scale is None else P(grad_scale), P(out),
-                            _stream()), "vbg_clip_coef")
-    return out
+def adam_step_seg_clip(p, g, m, v, vmax, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0):
+    """vbg_adam_step_seg_clip: adam_step_seg_amp with the clip coefficient, under the same rules (see sgd_step_seg_clip)"""
+    hp = _adam_opts(p, g, m, v, vmax, table, groups, ("grad_scale", "found_inf"), grad_scale=grad_scale, found_inf=found_inf, clip_coef=clip_coef)
+    check(lib.vbg_adam_step_seg_clip(P(p), P(g), P(m), P(v), P(vmax), P(table.rows), table.n, hp, len(groups), P(grad_scale), P(found_inf),
+                                     P(clip_coef), float(host_scale), _stream()), "vbg_adam_step_seg_clip")
 
 
 NORM_KINDS = (2, 1, 0)          # the `kind` of vbg_grad_norm_seg / vbg_clip_coef_gate: L2, L1, inf norm
 
 
-def _gate_args(gate, device, what):
-    """(loss, fp64 flag, threshold) of a checked loss gate `(loss, threshold)` -- loss: one fp64 or fp32 element on `device`, only ever read
-    by the kernels; threshold: a Python number -- or (None, 0, 0.0) for no gate"""
-    if gate is None:
-        return None, 0, 0.0
-    if not isinstance(gate, tuple) or len(gate) != 2:
-        raise TypeError(f"{what}: the gate is a pair (loss tensor, threshold)")
+def _check_gate(gate, device, what, pair=(tuple,)):
+    """the one statement of what a loss gate is, for vbg.optim.clip_in_step(when=...) and the two wrappers below: a pair (loss,
+    threshold) -- loss: one fp64 or fp32 element on `device`, only ever read by the kernels; threshold: a Python number -> the pair"""
+    if not isinstance(gate, pair) or len(gate) != 2:
+        raise TypeError(f"{what}: the gate is a pair (loss, threshold) -- a one-element device tensor and a Python number")
     loss, threshold = gate
     if not isinstance(loss, torch.Tensor):
         raise TypeError(f"{what}: the gate's loss must be a tensor, not {type(loss).__name__}")
     if loss.dtype not in (torch.float64, f32):
         raise TypeError(f"{what}: the gate's loss must be fp64 or fp32, not {loss.dtype}")
-    if loss.numel() != 1 or loss.device != device:
-        raise ValueError(f"{what}: the gate's loss must be one element on the buffers' device ({device})")
+    if loss.numel() != 1:
+        raise ValueError(f"{what}: the gate's loss must have one element, not {loss.numel()}")
+    if loss.device != device:
+        raise ValueError(f"{what}: the gate's loss lives on {loss.device}, the buffers' device is {device}")
     if isinstance(threshold, (bool, torch.Tensor)) or not isinstance(threshold, (int, float)):
         raise TypeError(f"{what}: the gate's threshold must be a Python number")
+    return loss, threshold
+
+
+def _gate_args(gate, device, what):
+    """(loss, fp64 flag, threshold) of a checked gate, or (None, 0, 0.0) for no gate: the last three arguments of the gated entries"""
+    if gate is None:
+        return None, 0, 0.0
+    loss, threshold = _check_gate(gate, device, what)
     return loss, int(loss.dtype == torch.float64), float(threshold)
 
 
@@ -2978,23 +2949,65 @@ def _device_memory(what, *tensors):
             raise TypeError(f"{what}: libvbg operates on device memory only, got a tensor on {t.device}")
 
 
+def grad_sumsq_seg(g, table, partials):
+    """vbg_grad_sumsq_seg: partials[c] = sum of squares of row c of `table` (a ChunkTable) over g, c in [0, table.n); one launch, plain
+    stores in a fixed order (the same code in deterministic mode)"""
+    _row_pass_args(g, table, partials)
+    check(lib.vbg_grad_sumsq_seg(P(g), P(table.rows), table.n, P(partials), _stream()), "vbg_grad_sumsq_seg")
+    return partials
+
+
+def grad_unscale_check_seg(g, table, inv_scale, found_inf):
+    """vbg_grad_unscale_check_seg: torch._amp_foreach_non_finite_check_and_unscale_ over the rows of `table` (a ChunkTable) of g; one launch.
+    found_inf (a device scalar the caller zeroed) becomes 1.0 when a covered element is inf or NaN and is left alone otherwise;
+    inv_scale (a device scalar): exactly 1.0 -> g is only read, anything else -> every covered element is overwritten with g * inv_scale"""
+    _table_bufs("segmented inf check", table, g)
+    _one_f32("segmented inf check", table.rows.device, inv_scale=inv_scale, found_inf=found_inf)
+    _untag(g)          # (written through the raw pointer: torch's version counter does not move)
+    check(lib.vbg_grad_unscale_check_seg(P(g), P(table.rows), table.n, P(inv_scale), P(found_inf), _stream()), "vbg_grad_unscale_check_seg")
+    return found_inf
+
+
+def grad_sumsq_seg_inf(g, table, partials, found_inf):
+    """vbg_grad_sumsq_seg_inf: grad_sumsq_seg (the same partials, bit for bit) with GradScaler's inf check in the same pass over g:
+    found_inf as in grad_unscale_check_seg, decided by the elements, not by the sums"""
+    _row_pass_args(g, table, partials, found_inf=found_inf)
+    check(lib.vbg_grad_sumsq_seg_inf(P(g), P(table.rows), table.n, P(partials), P(found_inf), _stream()), "vbg_grad_sumsq_seg_inf")
+    return partials
+
+
 def grad_norm_seg(g, table, partials, kind=2, found_inf=None, gate=None):
     """vbg_grad_norm_seg: the row pass of grad_sumsq_seg for kind 2 (sums of squares, the same bits), 1 (sums of |g|) or 0 (max |g|, a NaN
     kept); found_inf: GradScaler's flag as in grad_sumsq_seg_inf, optional; gate: (loss, threshold) -- a closed gate (not loss > threshold,
     decided on the device) without found_inf makes the launch return before it touches g or partials"""
     if kind not in NORM_KINDS:
         raise ValueError("segmented gradient norm: kind is 2 (L2), 1 (L1) or 0 (inf norm)")
-    if g.dtype != f32 or not g.is_contiguous() or g.numel() < table.numel or g.device != table.rows.device:
-        raise ValueError("segmented gradient norm: a contiguous fp32 buffer on the table's device, at least as long as the table's numel")
-    if partials.dtype != f32 or not partials.is_contiguous() or partials.numel() < table.n or partials.device != table.rows.device:
-        raise ValueError("segmented gradient norm: partials must be contiguous fp32 on the table's device, one element per row of the table")
-    if found_inf is not None:
-        _scaler_scalars(table, found_inf=found_inf)
+    _row_pass_args(g, table, partials, ("found_inf",), found_inf=found_inf)
     loss, f64, thr = _gate_args(gate, table.rows.device, "segmented gradient norm")
     _device_memory("segmented gradient norm", g, table.rows, partials, found_inf, loss)
-    check(lib.vbg_grad_norm_seg(P(g), P(table.rows), table.n, P(partials), int(kind), None if found_inf is None else P(found_inf), P(loss), f64, thr,
-                                _stream()), "vbg_grad_norm_seg")
+    check(lib.vbg_grad_norm_seg(P(g), P(table.rows), table.n, P(partials), int(kind), P(found_inf), P(loss), f64, thr, _stream()),
+          "vbg_grad_norm_seg")
     return partials
+
+
+def _finish_args(partials, n, nout, out, grad_scale):
+    """the operands of the finish, checked -> out (nout fp32, made here when None)"""
+    if partials.dtype != f32 or not partials.is_contiguous() or not 0 <= n <= partials.numel():
+        raise ValueError("clip coefficient: partials must be contiguous fp32 with at least n elements")
+    if out is None:
+        out = torch.empty((nout,), device=partials.device, dtype=f32)
+    if out.dtype != f32 or not out.is_contiguous() or out.numel() < nout or out.device != partials.device:
+        raise ValueError(f"clip coefficient: out must be {('two', 'three')[nout - 2]} contiguous fp32 elements on the partials' device")
+    _one_f32("clip coefficient", partials.device, ("grad_scale",), grad_scale=grad_scale)
+    return out
+
+
+def clip_coef(partials, n, max_norm, norm_scale=1.0, grad_scale=None, out=None):
+    """vbg_clip_coef: -> out (2 fp32: total norm, clip coefficient) from partials[0 .. n); grad_scale: a device scalar when the gradients
+    still hold scaled values.  One small launch, no host sync"""
+    out = _finish_args(partials, n, 2, out, grad_scale)
+    check(lib.vbg_clip_coef(P(partials), int(n), float(max_norm), float(norm_scale), P(grad_scale), P(out), _stream()), "vbg_clip_coef")
+    return out
 
 
 def clip_coef_gate(partials, n, max_norm, norm_scale=1.0, grad_scale=None, kind=2, gate=None, out=None):
@@ -3002,42 +3015,9 @@ def clip_coef_gate(partials, n, max_norm, norm_scale=1.0, grad_scale=None, kind=
     a closed gate leaves (0, 1, 0) and reads no partial.  One small launch, no host sync"""
     if kind not in NORM_KINDS:
         raise ValueError("clip coefficient: kind is 2 (L2), 1 (L1) or 0 (inf norm)")
-    if partials.dtype != f32 or not partials.is_contiguous() or not 0 <= n <= partials.numel():
-        raise ValueError("clip coefficient: partials must be contiguous fp32 with at least n elements")
-    if out is None:
-        out = torch.empty((3,), device=partials.device, dtype=f32)
-    if out.dtype != f32 or not out.is_contiguous() or out.numel() < 3 or out.device != partials.device:
-        raise ValueError("clip coefficient: out must be three contiguous fp32 elements on the partials' device")
-    if grad_scale is not None and (not isinstance(grad_scale, torch.Tensor) or grad_scale.dtype != f32 or grad_scale.numel() != 1
-                                   or grad_scale.device != partials.device):
-        raise ValueError("clip coefficient: grad_scale must be one fp32 element on the partials' device")
+    out = _finish_args(partials, n, 3, out, grad_scale)
     loss, f64, thr = _gate_args(gate, partials.device, "clip coefficient")
     _device_memory("clip coefficient", partials, out, grad_scale, loss)
-    check(lib.vbg_clip_coef_gate(P(partials), int(n), int(kind), float(max_norm), float(norm_scale), None if grad_scale is None else P(grad_scale),
-                                 P(loss), f64, thr, P(out), _stream()), "vbg_clip_coef_gate")
+    check(lib.vbg_clip_coef_gate(P(partials), int(n), int(kind), float(max_norm), float(norm_scale), P(grad_scale), P(loss), f64, thr, P(out),
+                                 _stream()), "vbg_clip_coef_gate")
     return out
-
-
-def sgd_step_seg_clip(p, g, mom, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0, keep_mom=False):
-    """vbg_sgd_step_seg_clip: sgd_step_seg_amp with the clip coefficient (a device scalar, required) applied to g after the unscale;
-    found_inf may be None (no scaler); host_scale: the host float of sgd_step_seg_opt; keep_mom: momentum-0 groups write `mom` as in
-    sgd_step_seg.  g is overwritten with the unscaled, clipped gradient"""
-    _seg_args(table, groups, *((p, g) if mom is None else (p, g, mom)))
-    if mom is None and (keep_mom or any(float(h[1]) != 0.0 for h in groups)):
-        raise ValueError("segmented SGD step: a group has momentum, the momentum buffer is missing")
-    sc, fi, cc = _clip_scalars(table, grad_scale, found_inf, clip_coef)
-    hp = (SgdGroupOpt * len(groups))(*[SgdGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), int(h[4])) for h in groups])
-    check(lib.vbg_sgd_step_seg_clip(P(p), P(g), None if mom is None else P(mom), P(table.rows), table.n, hp, len(groups), sc, fi, cc,
-                                    float(host_scale), int(bool(keep_mom)), _stream()), "vbg_sgd_step_seg_clip")
-
-
-def adam_step_seg_clip(p, g, m, v, vmax, table, groups, grad_scale, found_inf, clip_coef, host_scale=1.0):
-    """vbg_adam_step_seg_clip: adam_step_seg_amp with the clip coefficient, under the same rules (see sgd_step_seg_clip)"""
-    _seg_args(table, groups, *((p, g, m, v) if vmax is None else (p, g, m, v, vmax)))
-    if vmax is None and any(int(h[6]) & 1 for h in groups):
-        raise ValueError("segmented Adam step: a group has amsgrad, the max_exp_avg_sq buffer is missing")
-    sc, fi, cc = _clip_scalars(table, grad_scale, found_inf, clip_coef)
-    hp = (AdamGroupOpt * len(groups))(*[AdamGroupOpt(float(h[0]), float(h[1]), float(h[2]), float(h[3]), float(h[4]), int(h[5]), int(h[6]))
-                                        for h in groups])
-    check(lib.vbg_adam_step_seg_clip(P(p), P(g), P(m), P(v), None if vmax is None else P(vmax), P(table.rows), table.n, hp, len(groups), sc, fi,
-                                     cc, float(host_scale), _stream()), "vbg_adam_step_seg_clip")

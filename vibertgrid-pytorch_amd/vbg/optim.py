@@ -1111,22 +1111,11 @@ _NORM_KINDS = {2.0: 2, 1.0: 1, float("inf"): 0}          # norm_type -> the `kin
 
 
 def _clip_gate(when, dev):
-    """clip_in_step's `when`: None, or (loss, threshold) checked here -- the loss is handed on as it is and never read on the host"""
+    """clip_in_step's `when`: None, or (loss, threshold) checked by the statement the ops wrappers run -- the loss is handed on as it is and
+    never read on the host"""
     if when is None:
         return None
-    if not isinstance(when, (tuple, list)) or len(when) != 2:
-        raise TypeError("clip_in_step: when=(loss, threshold) -- a one-element device tensor and a Python number")
-    loss, threshold = when
-    if not isinstance(loss, torch.Tensor):
-        raise TypeError(f"clip_in_step: the gate's loss must be a tensor, not {type(loss).__name__}")
-    if loss.dtype not in (torch.float64, torch.float32):
-        raise TypeError(f"clip_in_step: the gate's loss must be fp64 or fp32, not {loss.dtype}")
-    if loss.numel() != 1:
-        raise ValueError(f"clip_in_step: the gate's loss must have one element, not {loss.numel()}")
-    if loss.device != dev:
-        raise ValueError(f"clip_in_step: the gate's loss lives on {loss.device}, the flat gradient buffers on {dev}")
-    if isinstance(threshold, (bool, torch.Tensor)) or not isinstance(threshold, (int, float)):
-        raise TypeError("clip_in_step: the gate's threshold must be a Python number")
+    loss, threshold = ops._check_gate(when, dev, "clip_in_step", pair=(tuple, list))
     return (loss.detach(), threshold)
 
 

@@ -27,21 +27,21 @@ f0, d0, w0 = ops.conv2d_fwd, ops.conv2d_dgrad, ops.conv2d_wgrad
 def fwd(x, w, stride, pad, *a, **k):
     B, H, W, Ci = x.shape
     Co, kh, kw, _ = w.shape
-    log[("fwd", H, W, Ci, Co, kh, stride, "conv3" if ops.conv3_ok(B, H, W, Ci, Co, kh, kw, stride, pad) else "generic")] += 1
+    log[("fwd", H, W, Ci, Co, kh, stride, ops.conv_fwd_plan(B, H, W, Ci, Co, kh, kw, stride, pad).kernel)] += 1
     return f0(x, w, stride, pad, *a, **k)
 
 
 def dgrad(dy, w, xs, stride, pad, *a, **k):
     B, H, W, Ci = xs
     Co, kh, kw, _ = w.shape
-    log[("dgrad", H, W, Ci, Co, kh, stride, "conv3" if ops.conv3_ok(B, H, W, Co, Ci, kh, kw, stride, pad) else "generic")] += 1
+    log[("dgrad", H, W, Ci, Co, kh, stride, ops.conv_dgrad_plan(B, H, W, Ci, Co, kh, kw, stride, pad).kernel)] += 1
     return d0(dy, w, xs, stride, pad, *a, **k)
 
 
 def wgrad(dy, x, dw, stride, pad, *a, **k):
     B, H, W, Ci = x.shape
     Co, kh, kw, _ = dw.shape
-    log[("wgrad", H, W, Ci, Co, kh, stride, "conv3" if ops.conv3w_ok(B, H, W, Ci, Co, kh, kw, stride, pad) else "generic")] += 1
+    log[("wgrad", H, W, Ci, Co, kh, stride, ops.conv_wgrad_plan(B, H, W, Ci, Co, kh, kw, stride, pad).kernel)] += 1
     return w0(dy, x, dw, stride, pad, *a, **k)
 
 

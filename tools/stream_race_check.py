@@ -99,8 +99,8 @@ def main():
                     + ([("bn_bwd_apply_fold: dres", dres.clone())] if dres is not None else [])
             return dx, dres
 
-        def dg(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, dy_amax=None, w_owner=None):
-            o = _dg(dy, w_ohwi, x_shape, stride, pad, out=out, accumulate=accumulate, dy_amax=dy_amax, w_owner=w_owner)
+        def dg(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, dy_amax=None, w_owner=None, plan=None):
+            o = _dg(dy, w_ohwi, x_shape, stride, pad, out=out, accumulate=accumulate, dy_amax=dy_amax, w_owner=w_owner, plan=plan)
             if TR["on"] and dy.shape[-1] == 64 and x_shape[-1] == 64:
                 TR["rec"] += [("conv2d_dgrad: dx", o.clone())] + ([("conv2d_dgrad: amax slot as read", dy_amax.clone())] if dy_amax is not None else [])
             return o

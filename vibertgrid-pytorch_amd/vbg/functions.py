@@ -262,53 +262,67 @@ class SegLinearFn(torch.autograd.Function):
 
 # ----------------------------------------------------------------------------------------------
 def _conv_any(x, w4, stride, pad, bias=None, want_stats=False, w_owner=None, x_amax=None, zero_slots=False, bn=None):
-    """x NHWC; w4 = OHWI weight.  Cin=3 stem goes through im2col (K=147, row stride 148).
-    want_stats: -> third result = BatchNorm slot workspace holding the output's column sums / sums of squares (fused into the GEMM
-    epilogue), or None when the product is one the library may split (the caller then runs ops.bn_stats).
+    """x NHWC; w4 = OHWI weight -> (y, col, stats): the forward of a convolution node, on the forward plan of its shape.
+    col: the im2col buffer of the Cin=3 stem (kept for its weight gradient), else None.
+    want_stats: stats = BatchNorm slot workspace holding the output's column sums / sums of squares (fused into the GEMM epilogue), or
+    None when the product is one the library may split (the caller then runs ops.bn_stats).
     bn: an ops.BnEpi -- frozen BatchNorm of the output in the epilogue of the one launch (the stem's im2col product included)."""
     B, H, W, Cin = x.shape
     Cout, kh, kw, _ = w4.shape
-    K = kh * kw * Cin
-    Ho, Wo = ops.conv_out_hw(H, W, kh, stride, pad)
+    plan = ops.conv_fwd_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, want_stats)
     # (zero_slots: the consumer folds the slot rows without clearing them -- rows from the zero pool instead of the persistent workspace)
-    stats = ((ops.bn_zero_slots(x.device, Cout) if zero_slots else ops._bn_workspace(x.device, Cout))
-             if (want_stats and ops.fuse_stats_ok(B * Ho * Wo, Cout, K)) else None)
-    if Cin % 16 != 0:
-        Kp = (K + 3) // 4 * 4
-        col = ops.im2col(x, kh, kw, stride, pad, Kp)
-        out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=f32)
-        ops.gemm_raw(B * Ho * Wo, Cout, K, col, Kp, OP_DENSE_K, w4, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, bn=bn)
-        return out, col, stats
-    return ops.conv2d_fwd(x, w4, stride, pad, bias, stats=stats, w_owner=w_owner, x_amax=x_amax, bn=bn), None, stats
+    stats = (ops.bn_zero_slots(x.device, Cout) if zero_slots else ops._bn_workspace(x.device, Cout)) if plan.fuse_stats else None
+    col = ops.conv_col(x, kh, kw, stride, pad) if plan.kernel == "im2col" else None
+    return ops.conv2d_fwd(x, w4, stride, pad, bias, stats=stats, w_owner=w_owner, x_amax=x_amax, bn=bn, plan=plan, col=col), col, stats
 
 
-def _conv_wgrad_any(dy, x, col, w4_shape, stride, pad, w_param=None, dy_amax=None, x_amax=None):
+def _conv_wgrad_any(dy, x, col, w4_shape, stride, pad, w_param=None, dy_amax=None, x_amax=None, plan=None):
     """-> OIHW-shaped gradient for autograd, or None when accumulated straight into the sunk flat gradient"""
     dst = wgrad_dest(w_param) if w_param is not None else None
     if dst is not None:
         dw = ohwi(dst)
         assert dw.data_ptr() == dst.data_ptr()
-        if col is not None:
-            Cout, kh, kw, Cin = w4_shape
-            K = kh * kw * Cin
-            sk = ops._pick_splitk(Cout, K, col.shape[0])
-            ops.gemm_raw(Cout, K, col.shape[0], dy, Cout, OP_DENSE_R, col, col.shape[1], OP_DENSE_R, dw, K, accumulate=True, splitk=sk)
-        else:
-            ops.conv2d_wgrad(dy, x, dw, stride, pad, accumulate=True, dy_amax=dy_amax, x_amax=x_amax)
-        wgrad_done(w_param)
-        return None
-    dw = torch.empty(w4_shape, device=dy.device, dtype=f32)
-    if col is not None:
-        Cout, kh, kw, Cin = w4_shape
-        K = kh * kw * Cin
-        Mpix = col.shape[0]
-        sk = ops._pick_splitk(Cout, K, Mpix)
-        if sk > 1:
-            dw.zero_()
-        ops.gemm_raw(Cout, K, Mpix, dy, Cout, OP_DENSE_R, col, col.shape[1], OP_DENSE_R, dw, K, accumulate=sk > 1, splitk=sk)
     else:
-        ops.conv2d_wgrad(dy, x, dw, stride, pad, accumulate=False, dy_amax=dy_amax, x_amax=x_amax)
-    return oihw_grad_like(dw)
+        dw = torch.empty(w4_shape, device=dy.device, dtype=f32)
+    ops.conv2d_wgrad(dy, x, dw, stride, pad, accumulate=dst is not None, dy_amax=dy_amax, x_amax=x_amax, plan=plan, col=col)
+    if dst is None:
+        return oihw_grad_like(dw)
+    wgrad_done(w_param)
+    return None
+
+
+def _bwd_plans(ctx, x, w4, stride, pad):
+    """(input-gradient plan or None, weight-gradient plan, does either want the largest magnitude of dy?), decided once at the top of a
+    node's backward: ONE amax word -- a vbg_amax pass, or the output of the kernel that writes dy -- serves both products"""
+    shape = (*x.shape, *w4.shape[:3], stride, pad)          # B, H, W, Cin, Cout, kh, kw, stride, pad
+    plan_d = ops.conv_dgrad_plan(*shape) if ctx.needs_input_grad[0] else None
+    plan_w = ops.conv_wgrad_plan(*shape)
+    return plan_d, plan_w, (plan_d is not None and plan_d.wants_amax) or plan_w.wants_amax
+
+
+def _conv_backward(ctx, level, dy, x, w4, col, stride, pad, dy_amax, plan_d, plan_w):
+    """(dx, dw) of a convolution node.  level: what ops.conv_wgrad_stream_enabled asks of the node (1: conv + BatchNorm, 2: plain)"""
+    def wgrad():
+        return _conv_wgrad_any(dy, x, col, tuple(w4.shape), stride, pad, ctx.w_ref, dy_amax=dy_amax, x_amax=ctx.x_amax, plan=plan_w)
+
+    if ctx.side_ok and ctx.needs_input_grad[0] and sinks(ctx.w_ref) and ops.conv_wgrad_stream_enabled(level, dy.numel() // dy.shape[-1]):
+        # the weight gradient goes straight into the flat gradient view and nothing else in this backward reads it: it runs on a
+        # stream of its own beside the input gradient, which the layer below waits for -- two launches that each leave most of the
+        # chip idle (the one-round launches of the late trunk stages) share it.  The operands stay reserved for that stream when this
+        # node releases them; JoinSideFn's end-of-backward callback / FlatReducer's staging stream wait for it.
+        cur, ws = torch.cuda.current_stream(dy.device), ops.side_stream(dy.device, "cwgrad")
+        ws.wait_stream(cur)
+        with torch.cuda.stream(ws):
+            dw = wgrad()
+            # (the amax slots too: they are views of the CALLER stream's slot pool, and a pool whose last view dies -- this node's
+            # release of ctx.x_amax / dy_amax can be that moment -- goes back to the caching allocator of the caller's stream, which may
+            # hand the 2 MB block to the next slot pool and zero it while this launch is still queued: the round-5 outlier, DESIGN 5)
+            ops.reserve_for(ws, dy, x, col, dy_amax, ctx.x_amax)
+        assert dw is None
+    else:
+        dw = wgrad()
+    dx = ops.conv2d_dgrad(dy, w4, tuple(x.shape), stride, pad, dy_amax=dy_amax, w_owner=ctx.w_ref, plan=plan_d) if plan_d is not None else None
+    return dx, dw
 
 
 class ConvFn(torch.autograd.Function):
@@ -330,23 +344,9 @@ class ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w4, col = ctx.saved_tensors
         dy = _c(dy)
-        B_, H_, W_, Cin_ = x.shape
-        Cout_, kh, kw, _ = w4.shape
-        # fp16-form products of the wide 3x3 convolutions: ONE pass for the largest magnitude of dy serves both gradients
-        f16_d = ctx.needs_input_grad[0] and ops.conv3_f16_bwd_ok(B_, H_, W_, Cout_, Cin_, kh, kw, ctx.stride, ctx.pad)
-        f16_w = col is None and ops.conv3_f16_wgrad_ok(B_, H_, W_, Cin_, Cout_, kh, kw, ctx.stride, ctx.pad)
-        dy_amax = ops.amax(dy) if (f16_d or f16_w) else None
-        if ctx.side_ok and ctx.needs_input_grad[0] and sinks(ctx.w_ref) and ops.conv_wgrad_stream_enabled(2, dy.numel() // dy.shape[-1]):
-            # (as in ConvBnFn: the weight gradient beside the input gradient, on the conv weight-gradient stream)
-            cur, ws = torch.cuda.current_stream(dy.device), ops.side_stream(dy.device, "cwgrad")
-            ws.wait_stream(cur)
-            with torch.cuda.stream(ws):
-                dw = _conv_wgrad_any(dy, x, col, tuple(w4.shape), ctx.stride, ctx.pad, ctx.w_ref, dy_amax=dy_amax, x_amax=ctx.x_amax)
-                ops.reserve_for(ws, dy, x, col, dy_amax, ctx.x_amax)
-            assert dw is None
-        else:
-            dw = _conv_wgrad_any(dy, x, col, tuple(w4.shape), ctx.stride, ctx.pad, ctx.w_ref, dy_amax=dy_amax, x_amax=ctx.x_amax)
-        dx = ops.conv2d_dgrad(dy, w4, tuple(x.shape), ctx.stride, ctx.pad, dy_amax=dy_amax, w_owner=ctx.w_ref) if ctx.needs_input_grad[0] else None
+        plan_d, plan_w, want_amax = _bwd_plans(ctx, x, w4, ctx.stride, ctx.pad)
+        dy_amax = ops.amax(dy) if want_amax else None
+        dx, dw = _conv_backward(ctx, 2, dy, x, w4, col, ctx.stride, ctx.pad, dy_amax, plan_d, plan_w)
         db = _bias_grad(ctx.b_ref, dy.view(-1, dy.shape[-1])) if ctx.has_bias else None
         return dx, dw, db, None, None
 
@@ -366,6 +366,21 @@ def _frozen_invstd(running_var, eps):
     return inv
 
 
+def bn_route(training, sync, C, needs_input_grad) -> str:
+    """the BatchNorm route of ConvBnFn.forward.  "epilogue": frozen statistics and no backward to come (inference(), the eval forward under
+    no_grad) -- BatchNorm, residual, ReLU and the amax word ride in the convolution's epilogue: one launch, no z, nothing kept; "frozen":
+    frozen statistics, apply kernel; "fold": training statistics of one rank -- finalize rides in the apply kernel's prologue, the
+    affine-gradient fold in the backward apply's; "stats": the same at a channel count the fold does not take (finalize, then apply);
+    "sync_fold" / "sync": SyncBatchNorm's all-reduced sums, finalized in the apply kernel's prologue / by a launch of their own"""
+    if ops.bn_epilogue_route(training, needs_input_grad, sync):
+        return "epilogue"
+    if not training:
+        return "frozen"
+    if sync:
+        return "sync_fold" if ops.bn_fold_ok(C) else "sync"
+    return "fold" if ops.bn_fold_ok(C) else "stats"
+
+
 class ConvBnFn(torch.autograd.Function):
     """conv (bias-free) -> BatchNorm2d (batch statistics in training, SyncBN-able) -> (+ residual) -> ReLU."""
 
@@ -375,56 +390,52 @@ class ConvBnFn(torch.autograd.Function):
         x = _c(x)
         sync = bool(sync) and SyncCtx.active()
         w4 = ohwi(w)
-        # one rank, training statistics: finalize rides in the apply kernel's prologue, the affine-gradient fold in the backward apply's
-        fold = training and ops.bn_fold_ok(w.shape[0], sync)
-        if ops.bn_epilogue_route(training, ctx.needs_input_grad, sync):
-            # frozen statistics and no backward to come (inference(), the eval forward under no_grad): the BatchNorm, the residual, the
-            # ReLU and the amax word ride in the convolution's epilogue -- one launch, no z, nothing kept
-            y_amax = ops.amax_slot(x.device) if ops.conv3_f16_enabled() else None
+        route = bn_route(training, sync, w.shape[0], ctx.needs_input_grad)
+        # the largest magnitude of y rides on the kernel that writes it: the scale of y as an operand of the next convolution's
+        # fp16-form weight gradient (the tag travels on the tensor object; a consumer that does not find one takes a vbg_amax pass)
+        # (grad mode is off inside forward(): whether a backward will come is what ctx.needs_input_grad says)
+        # ... and the scale of y as the ACTIVATION operand of the next convolution's fp16-form forward (an activation of 65520 or more no
+        # longer becomes inf): published whenever that form is on, inference and no_grad included (ADVICE r4)
+        want_y_amax = ops.conv_out_amax_wanted(ctx.needs_input_grad)
+        if route == "epilogue":
+            y_amax = ops.amax_slot(x.device) if want_y_amax else None
             r = None if res is None else _c(res)
             y, _, _ = _conv_any(x, w4, stride, pad, w_owner=w, x_amax=ctx.x_amax,
                                 bn=ops.BnEpi(running_mean, _frozen_invstd(running_var, eps), gamma, beta, r, relu, y_amax))
             if y_amax is not None:
                 y._vbg_amax = (y_amax, y._version)
             return y
+        fold = route == "fold"
         z, col, stats = _conv_any(x, w4, stride, pad, want_stats=training, w_owner=w, x_amax=ctx.x_amax, zero_slots=fold)
         C = z.shape[-1]
         z2 = z.view(-1, C)
         M = z2.shape[0]
         r2 = None if res is None else _c(res).view(-1, C)
-        # the largest magnitude of y rides on the kernel that writes it: the scale of y as an operand of the next convolution's
-        # fp16-form weight gradient (the tag travels on the tensor object; a consumer that does not find one takes a vbg_amax pass)
-        # (grad mode is off inside forward(): whether a backward will come is what ctx.needs_input_grad says)
-        # ... and the scale of y as the ACTIVATION operand of the next convolution's fp16-form forward (an activation of 65520 or more no
-        # longer becomes inf): published whenever that form is on, inference and no_grad included (ADVICE r4)
-        y_amax = ops.amax_slot(x.device) if (ops.conv3_f16_enabled() or (any(ctx.needs_input_grad) and ops.conv3_f16_bwd_enabled())) else None
-        if fold:
+        y_amax = ops.amax_slot(x.device) if want_y_amax else None
+        count, count_dev, y = float(M), None, None
+        if route == "frozen":
+            mean, invstd = running_mean, _frozen_invstd(running_var, eps)
+        elif route == "fold":
             if stats is None:
                 stats = ops.bn_stats(z2, ops.bn_zero_slots(x.device, C))
-            count, count_dev = float(M), None
             y, mean, invstd = ops.bn_apply_fold(z2, r2, stats, count, eps, momentum, running_mean, running_var, gamma, beta, relu, y_amax=y_amax)
-            y = y.view(z.shape)
         else:
-            if training:
-                if stats is None:
-                    stats = ops.bn_stats(z2)
-                count, count_dev = float(M), None
-                if sync:
-                    glob = ops.bn_fold_count(stats, C, M)        # [sum, sumsq, rows of this rank] from one launch
-                    SyncCtx.all_reduce(glob)
-                    count_dev = glob[2 * C:]                   # global row count stays on the device (no sync)
-                    if ops.bn_fold_ok(C):                      # finalize from the all-reduced sums in the apply kernel's prologue
-                        y, mean, invstd = ops.bn_apply_fold(z2, r2, glob, count, eps, momentum, running_mean, running_var, gamma, beta, relu,
-                                                            y_amax=y_amax, nslots=1, count_dev=count_dev)
-                        y = y.view(z.shape)
-                    else:
-                        mean, invstd = ops.bn_finalize(glob, C, 1, count, eps, momentum, running_mean, running_var, count_dev)
-                else:
-                    mean, invstd = ops.bn_finalize(stats, C, ops.bn_slots(), count, eps, momentum, running_mean, running_var)
+            if stats is None:
+                stats = ops.bn_stats(z2)
+            if route == "stats":
+                mean, invstd = ops.bn_finalize(stats, C, ops.bn_slots(), count, eps, momentum, running_mean, running_var)
             else:
-                mean, invstd, count, count_dev = running_mean, _frozen_invstd(running_var, eps), float(M), None
-            if not (training and sync and ops.bn_fold_ok(C)):
-                y = ops.bn_apply(z2, r2, mean, invstd, gamma, beta, relu, y_amax=y_amax).view(z.shape)
+                glob = ops.bn_fold_count(stats, C, M)        # [sum, sumsq, rows of this rank] from one launch
+                SyncCtx.all_reduce(glob)
+                count_dev = glob[2 * C:]                   # global row count stays on the device (no sync)
+                if route == "sync_fold":
+                    y, mean, invstd = ops.bn_apply_fold(z2, r2, glob, count, eps, momentum, running_mean, running_var, gamma, beta, relu,
+                                                        y_amax=y_amax, nslots=1, count_dev=count_dev)
+                else:
+                    mean, invstd = ops.bn_finalize(glob, C, 1, count, eps, momentum, running_mean, running_var, count_dev)
+        if y is None:          # (the folding applies have written it)
+            y = ops.bn_apply(z2, r2, mean, invstd, gamma, beta, relu, y_amax=y_amax)
+        y = y.view(z.shape)
         if y_amax is not None:
             y._vbg_amax = (y_amax, y._version)
         ctx.fold = fold
@@ -442,55 +453,28 @@ class ConvBnFn(torch.autograd.Function):
         dy2 = _c(dy).view(-1, C)
         z2 = z.view(-1, C)
         y2 = None if y is None else y.view(-1, C)
-        B_, H_, W_, Cin_ = x.shape
-        want_amax = (ctx.needs_input_grad[0] and ops.conv3_f16_bwd_ok(B_, H_, W_, C, Cin_, w4.shape[1], w4.shape[2], stride, pad)) or \
-            (col is None and ops.conv3_f16_wgrad_ok(B_, H_, W_, Cin_, C, w4.shape[1], w4.shape[2], stride, pad))
-        dz_amax = ops.amax_slot(dy2.device) if want_amax else None
+        plan_d, plan_w, want_amax = _bwd_plans(ctx, x, w4, stride, pad)
+        dz_amax = ops.amax_slot(dy2.device) if want_amax else None          # (written by the apply kernel that writes dz)
         dgamma, dbeta, sunk = _affine_dest(*ctx.affine)           # from the LOCAL sums: the gradient exchange averages them
         if ctx.fold and ops.bn_fold_ok(C, sync):
             # (training statistics on one rank: the fold of the slot rows and the affine gradients ride in the apply kernel's prologue)
             slots = ops.bn_bwd_reduce(dy2, y2, z2, mean, invstd, relu, ops.bn_zero_slots(dy2.device, C))
             dz2, dres2 = ops.bn_bwd_apply_fold(dy2, y2, z2, mean, invstd, gamma, slots, count, relu, has_res, dgamma, dbeta, dx_amax=dz_amax)
             dgamma, dbeta = _affine_done(*ctx.affine, dgamma, dbeta, sunk)
-            return ConvBnFn._finish_backward(ctx, dz2, dres2, dz_amax, dgamma, dbeta)
-        slots = ops.bn_bwd_reduce(dy2, y2, z2, mean, invstd, relu)
-        sums = ops.bn_param_grad(slots, C, dgamma, dbeta)
-        dgamma, dbeta = _affine_done(*ctx.affine, dgamma, dbeta, sunk)
-        if not training:
-            # frozen statistics (module in eval mode inside a training step): mean / var are constants, so the two batch-coupling
-            # terms of the input gradient vanish -> dz = gamma * invstd * dy (same kernel, zero sums); dgamma / dbeta as above
-            sums = torch.zeros_like(sums)
-        elif sync:
-            SyncCtx.all_reduce(sums)
-        dz2, dres2 = ops.bn_bwd_apply(dy2, y2, z2, mean, invstd, gamma, sums, count, relu, has_res, None, None, count_dev, dx_amax=dz_amax)
-        return ConvBnFn._finish_backward(ctx, dz2, dres2, dz_amax, dgamma, dbeta)
-
-    @staticmethod
-    def _finish_backward(ctx, dz2, dres2, dz_amax, dgamma, dbeta):
-        """the convolution's input / weight gradients from dz (the gradient in front of the BatchNorm), shared by both BatchNorm routes"""
-        x, w4, col, z, y, mean, invstd, gamma, count_dev = ctx.saved_tensors
-        stride, pad, relu, training, count, has_res, sync = ctx.cfg
-        dz = dz2.view(z.shape)
-        dres = dres2.view(z.shape) if has_res else None
-        if ctx.side_ok and ctx.needs_input_grad[0] and sinks(ctx.w_ref) and ops.conv_wgrad_stream_enabled(1, dz2.shape[0]):
-            # the weight gradient goes straight into the flat gradient view and nothing else in this backward reads it: it runs on a
-            # stream of its own beside the input gradient, which the layer below waits for -- two launches that each leave most of the
-            # chip idle (the one-round launches of the late trunk stages) share it.  The operands stay reserved for that stream when this
-            # node releases them; JoinSideFn's end-of-backward callback / FlatReducer's staging stream wait for it.
-            cur, ws = torch.cuda.current_stream(dz.device), ops.side_stream(dz.device, "cwgrad")
-            ws.wait_stream(cur)
-            with torch.cuda.stream(ws):
-                dw = _conv_wgrad_any(dz, x, col, tuple(w4.shape), stride, pad, ctx.w_ref, dy_amax=dz_amax, x_amax=ctx.x_amax)
-                # (the amax slots too: they are views of the CALLER stream's slot pool, and a pool whose last view dies -- this node's
-                # release of ctx.x_amax / dz_amax can be that moment -- goes back to the caching allocator of the caller's stream, which may
-                # hand the 2 MB block to the next slot pool and zero it while this launch is still queued: the round-5 outlier, DESIGN 5)
-                ops.reserve_for(ws, dz2, x, col, dz_amax, ctx.x_amax)
-            assert dw is None
-            dx = ops.conv2d_dgrad(dz, w4, tuple(x.shape), stride, pad, dy_amax=dz_amax, w_owner=ctx.w_ref)
-            return dx, None, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None
-        dx = ops.conv2d_dgrad(dz, w4, tuple(x.shape), stride, pad, dy_amax=dz_amax, w_owner=ctx.w_ref) if ctx.needs_input_grad[0] else None
-        dw = _conv_wgrad_any(dz, x, col, tuple(w4.shape), stride, pad, ctx.w_ref, dy_amax=dz_amax, x_amax=ctx.x_amax)
-        return dx, dw, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None
+        else:
+            slots = ops.bn_bwd_reduce(dy2, y2, z2, mean, invstd, relu)
+            sums = ops.bn_param_grad(slots, C, dgamma, dbeta)
+            dgamma, dbeta = _affine_done(*ctx.affine, dgamma, dbeta, sunk)
+            if not training:
+                # frozen statistics (module in eval mode inside a training step): mean / var are constants, so the two batch-coupling
+                # terms of the input gradient vanish -> dz = gamma * invstd * dy (same kernel, zero sums); dgamma / dbeta as above
+                sums = torch.zeros_like(sums)
+            elif sync:
+                SyncCtx.all_reduce(sums)
+            dz2, dres2 = ops.bn_bwd_apply(dy2, y2, z2, mean, invstd, gamma, sums, count, relu, has_res, None, None, count_dev, dx_amax=dz_amax)
+        # the convolution's input / weight gradients from dz (the gradient in front of the BatchNorm)
+        dx, dw = _conv_backward(ctx, 1, dz2.view(z.shape), x, w4, col, stride, pad, dz_amax, plan_d, plan_w)
+        return dx, dw, dgamma, dbeta, None, None, dres2.view(z.shape) if has_res else None, None, None, None, None, None, None, None
 
 
 class MaxPoolFn(torch.autograd.Function):

@@ -2,8 +2,10 @@
 memory and streams only; every function below launches hand-written HIP kernels on the CURRENT
 stream and never synchronises.  No fallbacks: tensors must live on a GPU."""
 import ctypes as C
+import functools
 
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -981,7 +983,13 @@ _CONV3_TICKETS = {}
 
 def conv3_split(B, H, W, Cs, N) -> int:
     """workgroups per tile the row-reuse kernel wants for this shape (1: no split; csrc/conv3.hip vbg_conv3x3_split)"""
-    return int(lib.vbg_conv3x3_split(B, H, W, Cs, N)) if _CONV3_SPLITK[0] else 1
+    return _lib_conv3_split(B, H, W, Cs, N) if _CONV3_SPLITK[0] else 1
+
+
+@functools.lru_cache(maxsize=1024)
+def _lib_conv3_split(B, H, W, Cs, N) -> int:
+    """(a pure host function of the shape, asked by conv3_ok / conv3_pw_ok for every late-stage product: one library call per shape)"""
+    return int(lib.vbg_conv3x3_split(B, H, W, Cs, N))
 
 
 def _conv3_tickets(device, tiles):
@@ -1274,36 +1282,6 @@ def conv3x3_wgrad(dy, x, dw_ohwi, slabs=True, f16x2=False, dy_amax=None, x_amax=
     return dw_ohwi
 
 
-def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=None, x_amax=None, bn=None):
-    """x NHWC [B,H,W,Cin] contiguous; w_ohwi [Cout,kh,kw,Cin] contiguous -> y NHWC [B,Ho,Wo,Cout].  bn: a BnEpi -- frozen BatchNorm
-    (+ residual, ReLU, amax) of the output in the epilogue of whichever kernel takes the convolution."""
-    _chk_f32(x, w_ohwi, bias)
-    B, H, W, Cin = x.shape
-    Cout, kh, kw, _ = w_ohwi.shape
-    assert x.is_contiguous() and w_ohwi.is_contiguous() and w_ohwi.shape[3] == Cin and Cin % 16 == 0
-    Ho, Wo = conv_out_hw(H, W, kh, stride, pad)
-    if out is None:
-        out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=f32)
-    M, K = B * Ho * Wo, kh * kw * Cin
-    if conv3_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, fwd=True):
-        late = conv3_late_choice(B, H, W, Cin, Cout) if _CONV3_F16[0] else None
-        if late is not None:
-            wp = conv3_planes(w_owner, w_ohwi, False, bn=late[0])
-            if wp is not None:
-                return conv3x3(x, w_ohwi, bias, out, stats, f16x2=True, w_planes=wp, x_amax=x_amax, nsplit=late[1], bn=late[0], bn_epi=bn)
-        wp = conv3_planes(w_owner, w_ohwi, False) if (_CONV3_F16[0] and conv3_pw_ok(B, H, W, Cin, Cout)) else None
-        # x_amax: the producer's amax slot of the activation, when it published one (bn_apply in a training step).  The fp16 form then
-        # scales x by the power of two that centres its largest magnitude in fp16's range, like a gradient operand: an activation of
-        # 65520 or more no longer becomes inf (VERDICT r3 weak 4), and small activations keep more bits -- exact either way
-        return conv3x3(x, w_ohwi, bias, out, stats, f16x2=_CONV3_F16[0], w_planes=wp, x_amax=x_amax if _CONV3_F16[0] else None, bn_epi=bn)
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0:
-        gemm_raw(M, Cout, K, x, Cin, OP_DENSE_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, f16=True, bn=bn)
-    else:
-        gemm_raw(M, Cout, K, x, Cin, OP_CONV_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias,
-                 geo=conv_geo(H, W, Cin, Ho, Wo, kh, kw, stride, pad, 0), stats=stats, f16=True, bn=bn)
-    return out
-
-
 _BWD_SPLIT = 0          # backward products run with grad mode off; they are training-only, so the library may always split them
 
 
@@ -1313,9 +1291,11 @@ def conv3_f16_bwd_enabled() -> bool:
     return _CONV3[0] and _SPLIT3[0] and not _amp_generic() and _CONV3_F16[0]
 
 
-def conv3_f16_bwd_ok(B, H, W, Cout, Cin, kh, kw, stride, pad) -> bool:
-    """will conv2d_dgrad of this convolution run the fp16 form (and want the largest magnitude of dy)?"""
-    return _CONV3_F16[0] and conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad)
+def conv_out_amax_wanted(needs_input_grad) -> bool:
+    """does a conv + BatchNorm node publish the largest magnitude of its output?  Whenever a consumer's plan MAY take it, whatever the
+    consumer's shape turns out to be: the activation operand of an fp16-form forward, or (a backward will come) of an fp16-form weight
+    gradient"""
+    return conv3_f16_enabled() or (any(needs_input_grad) and conv3_f16_bwd_enabled())
 
 
 def conv3_late_choice(B, H, W, Cs, N):
@@ -1350,34 +1330,168 @@ def conv3_pw_ok(B, H, W, Cs, N) -> bool:
     return (B * H * W // 128) * ((N + bn - 1) // bn) >= 240
 
 
-def conv2d_dgrad(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, dy_amax=None, w_owner=None):
+# ---- one plan per product: the kernel family that takes a convolution, and in which form (DESIGN.md "Convolution plans") ----------------
+class ConvPlan(NamedTuple):
+    """what conv2d_fwd / conv2d_dgrad / conv2d_wgrad launch for one shape under the switches of the moment: a pure function of the shape
+    (conv_fwd_plan / conv_dgrad_plan / conv_wgrad_plan), no tensor needed.  The nodes of vbg/functions.py compute it where they have to
+    know beforehand -- an amax word to take or publish, statistics to fuse, the stem's col buffer to keep -- and hand it down, so node
+    and dispatch cannot disagree."""
+    kernel: str                      # "conv3" (csrc/conv3.hip) | "gemm1x1" | "gemm_conv" (csrc/gemm.hip) | "im2col" (the stem: col buffer x filter)
+    f16: bool = False                # conv3: the two-piece fp16 form
+    bn: int = 0                      # conv3: filters per tile (0: the library's choice)
+    nsplit: Optional[int] = None     # conv3: workgroups per tile (None: the library's choice)
+    planes: Optional[str] = None     # conv3: the filter image to ask conv3_planes for -- "late" (bn-filter tiles), "plain", or None
+    wants_amax: bool = False         # the product scales its GRADIENT operand(s) by their largest magnitude (a device word)
+    fuse_stats: bool = False         # forward: BatchNorm statistics of the output may ride in the epilogue (fuse_stats_ok)
+
+
+def _conv3_f16_plan(B, H, W, Cs, N, wants_amax=False, fuse_stats=False) -> ConvPlan:
+    late = conv3_late_choice(B, H, W, Cs, N)
+    if late is not None:
+        return ConvPlan("conv3", True, late[0], late[1], "late", wants_amax, fuse_stats)
+    return ConvPlan("conv3", True, 0, None, "plain" if conv3_pw_ok(B, H, W, Cs, N) else None, wants_amax, fuse_stats)
+
+
+def _gemm_plan(kh, kw, stride, pad, fuse_stats=False) -> ConvPlan:
+    return ConvPlan("gemm1x1" if (kh == 1 and kw == 1 and stride == 1 and pad == 0) else "gemm_conv", False, 0, None, None, False, fuse_stats)
+
+
+def _plan_switches():
+    """every switch the shape predicates read.  The plans are memoised per (shape, switches): a single-document inference is bound by
+    the host, and walking the predicates costs 2-4 us per convolution -- a plan is never older than a switch, because the switches are
+    part of its key (tests/test_conv_plan_host.py flips each one on a cached shape; a predicate that comes to read another switch must
+    list it here).  The caches are bounded: the region maps' batch size varies from step to step"""
+    return (_CONV3[0], _CONV3_F16[0], _CONV3_SPLITK[0], _SPLIT3[0], _AMP[0] and not _AMP_FAST[0], _DET[0], _CONV3_MIN_TILES[0],
+            _CONV3_MIN_TILES_FWD[0], _CONV3_MIN_TILES_BWD[0], _CONV3W_MIN[0])
+
+
+def conv_fwd_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, stats=False) -> ConvPlan:
+    """stats: the caller would have BatchNorm statistics of the output fused into the product (-> fuse_stats)"""
+    return _fwd_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, bool(stats), _plan_switches())
+
+
+def conv_dgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad) -> ConvPlan:
+    """(B, H, W, Cin: the shape of x.)  The input gradient of a 3x3 / s1 / p1 convolution is the same convolution of dy with the turned,
+    channel-swapped filter; its fp16 form wants the largest magnitude of dy"""
+    return _dgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, _plan_switches())
+
+
+def conv_wgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad) -> ConvPlan:
+    """the fp16 form of the row-reuse weight gradient wants the largest magnitudes of dy and x"""
+    return _wgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, _plan_switches())
+
+
+@functools.lru_cache(maxsize=1024)
+def _fwd_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, stats, _switches) -> ConvPlan:
+    if stats:
+        Ho, Wo = conv_out_hw(H, W, kh, stride, pad)
+        stats = fuse_stats_ok(B * Ho * Wo, Cout, kh * kw * Cin)
+    if Cin % 16 != 0:
+        return ConvPlan("im2col", fuse_stats=stats)
+    if conv3_ok(B, H, W, Cin, Cout, kh, kw, stride, pad, fwd=True):
+        return _conv3_f16_plan(B, H, W, Cin, Cout, False, stats) if _CONV3_F16[0] else ConvPlan("conv3", fuse_stats=stats)
+    return _gemm_plan(kh, kw, stride, pad, stats)
+
+
+@functools.lru_cache(maxsize=1024)
+def _dgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, _switches) -> ConvPlan:
+    if conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad):
+        return _conv3_f16_plan(B, H, W, Cout, Cin, True) if _CONV3_F16[0] else ConvPlan("conv3")
+    return _gemm_plan(kh, kw, stride, pad)
+
+
+@functools.lru_cache(maxsize=1024)
+def _wgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, _switches) -> ConvPlan:
+    if Cin % 16 != 0:
+        return ConvPlan("im2col")
+    if conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad):
+        return ConvPlan("conv3", _CONV3_F16[0], wants_amax=_CONV3_F16[0])
+    return _gemm_plan(kh, kw, stride, pad)
+
+
+def conv3_f16_bwd_ok(B, H, W, Cout, Cin, kh, kw, stride, pad) -> bool:
+    """will conv2d_dgrad of this convolution run the fp16 form (and want the largest magnitude of dy)?"""
+    return conv_dgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad).wants_amax
+
+
+def conv3_f16_wgrad_ok(B, H, W, Cin, Cout, kh, kw, stride, pad) -> bool:
+    """will conv2d_wgrad of this convolution run the fp16 form (and want the largest magnitudes of dy and x)?"""
+    return conv_wgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad).wants_amax
+
+
+def _conv3_filter(plan, owner, w_ohwi, flip, B, H, W, Cs, N):
+    """(plane image or None, filters per tile, workgroups per tile) of a conv3 plan.  conv3_planes has no image for a filter without an
+    owner (tools, tests): the late tiles exist in the PW kernels only, so such a product takes the library's own tiles -- pre-split
+    where those are 128-pixel tiles, should the owner have an image of that kind."""
+    if plan.planes == "late":
+        wp = conv3_planes(owner, w_ohwi, flip, bn=plan.bn)
+        if wp is not None:
+            return wp, plan.bn, plan.nsplit
+    if plan.planes == "plain" or (plan.planes == "late" and conv3_pw_ok(B, H, W, Cs, N)):
+        return conv3_planes(owner, w_ohwi, flip), 0, None
+    return None, 0, None
+
+
+def conv_col(x, kh, kw, stride, pad):
+    """the im2col image of x that an "im2col" plan multiplies (K = 147 for the stem, row stride 148): conv2d_fwd builds it unless handed
+    one, and conv2d_wgrad of the same convolution multiplies it again"""
+    return im2col(x, kh, kw, stride, pad, (kh * kw * x.shape[3] + 3) // 4 * 4)
+
+
+def conv2d_fwd(x, w_ohwi, stride, pad, bias=None, out=None, stats=None, w_owner=None, x_amax=None, bn=None, plan=None, col=None):
+    """x NHWC [B,H,W,Cin] contiguous; w_ohwi [Cout,kh,kw,Cin] contiguous -> y NHWC [B,Ho,Wo,Cout].  bn: a BnEpi -- frozen BatchNorm
+    (+ residual, ReLU, amax) of the output in the epilogue of whichever kernel takes the convolution.  plan: conv_fwd_plan of the shape,
+    when the caller has it; col: conv_col(x, ...) of an "im2col" plan, when the caller keeps it for the weight gradient."""
+    _chk_f32(x, w_ohwi, bias)
+    B, H, W, Cin = x.shape
+    Cout, kh, kw, _ = w_ohwi.shape
+    assert x.is_contiguous() and w_ohwi.is_contiguous() and w_ohwi.shape[3] == Cin
+    if plan is None:
+        plan = conv_fwd_plan(B, H, W, Cin, Cout, kh, kw, stride, pad, stats is not None)
+    Ho, Wo = conv_out_hw(H, W, kh, stride, pad)
+    if out is None:
+        out = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=f32)
+    M, K = B * Ho * Wo, kh * kw * Cin
+    if plan.kernel == "conv3":
+        # x_amax: the producer's amax slot of the activation, when it published one (bn_apply in a training step).  The fp16 form then
+        # scales x by the power of two that centres its largest magnitude in fp16's range, like a gradient operand: an activation of
+        # 65520 or more no longer becomes inf (VERDICT r3 weak 4), and small activations keep more bits -- exact either way
+        wp, tile, nsplit = _conv3_filter(plan, w_owner, w_ohwi, False, B, H, W, Cin, Cout)
+        return conv3x3(x, w_ohwi, bias, out, stats, f16x2=plan.f16, w_planes=wp, x_amax=x_amax if plan.f16 else None, nsplit=nsplit, bn=tile, bn_epi=bn)
+    if plan.kernel == "im2col":
+        col = conv_col(x, kh, kw, stride, pad) if col is None else col
+        gemm_raw(M, Cout, K, col, col.shape[1], OP_DENSE_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, bn=bn)
+    elif plan.kernel == "gemm1x1":
+        gemm_raw(M, Cout, K, x, Cin, OP_DENSE_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias, stats=stats, f16=True, bn=bn)
+    else:
+        gemm_raw(M, Cout, K, x, Cin, OP_CONV_K, w_ohwi, K, OP_DENSE_K, out, Cout, bias=bias,
+                 geo=conv_geo(H, W, Cin, Ho, Wo, kh, kw, stride, pad, 0), stats=stats, f16=True, bn=bn)
+    return out
+
+
+def conv2d_dgrad(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, dy_amax=None, w_owner=None, plan=None):
     """dx NHWC [B,H,W,Cin] (+)= conv_transpose(dy NHWC [B,Ho,Wo,Cout], w).  dy_amax: device word with the bits of max |dy| when the
-    producer of dy wrote one (bn_bwd_apply); otherwise the fp16 form takes it with one vbg_amax pass over dy"""
+    producer of dy wrote one (bn_bwd_apply); otherwise a plan that wants it takes it with one vbg_amax pass over dy"""
     _chk_f32(dy, w_ohwi)
     B, H, W, Cin = x_shape
     Cout, kh, kw, _ = w_ohwi.shape
     Bq, Ho, Wo, Cq = dy.shape
     assert dy.is_contiguous() and w_ohwi.is_contiguous() and Cq == Cout and Bq == B
+    if plan is None:
+        plan = conv_dgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad)
     if out is None:
         assert not accumulate
         out = torch.empty(x_shape, device=dy.device, dtype=f32)
     M = B * H * W
-    if conv3_ok(B, H, W, Cout, Cin, kh, kw, stride, pad):
-        # the input gradient of a 3x3 / s1 / p1 convolution is the same convolution of dy with the turned, channel-swapped filter
-        if _CONV3_F16[0]:
-            late = conv3_late_choice(B, H, W, Cout, Cin)
-            if late is not None:
-                wp = conv3_planes(w_owner, w_ohwi, True, bn=late[0])
-                if wp is not None:
-                    return conv3x3(dy, w_ohwi, None, out, None, accumulate, f16x2=True, x_amax=dy_amax if dy_amax is not None else amax(dy),
-                                   w_planes=wp, n_out=Cin, nsplit=late[1], bn=late[0])
-            wp = conv3_planes(w_owner, w_ohwi, True) if conv3_pw_ok(B, H, W, Cout, Cin) else None
-            if wp is not None:       # the turned filter exists as plane image only: no fp32 copy of it is written
-                return conv3x3(dy, w_ohwi, None, out, None, accumulate, f16x2=True, x_amax=dy_amax if dy_amax is not None else amax(dy),
-                               w_planes=wp, n_out=Cin)
-            return conv3x3(dy, conv3x3_wflip(w_ohwi), None, out, None, accumulate, f16x2=True, x_amax=dy_amax if dy_amax is not None else amax(dy))
-        return conv3x3(dy, conv3x3_wflip(w_ohwi), None, out, None, accumulate)
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0:
+    if plan.kernel == "conv3":
+        # (the turned filter of a pre-split product exists as plane image only: no fp32 copy of it is written)
+        wp, tile, nsplit = _conv3_filter(plan, w_owner, w_ohwi, True, B, H, W, Cout, Cin)
+        w = w_ohwi if wp is not None else conv3x3_wflip(w_ohwi)
+        if plan.wants_amax and dy_amax is None:
+            dy_amax = amax(dy)
+        return conv3x3(dy, w, None, out, None, accumulate, f16x2=plan.f16, x_amax=dy_amax if plan.wants_amax else None, w_planes=wp,
+                       n_out=None if wp is None else Cin, nsplit=nsplit, bn=tile)
+    if plan.kernel == "gemm1x1":
         gemm_raw(M, Cin, Cout, dy, Cout, OP_DENSE_K, w_ohwi, Cin, OP_DENSE_R, out, Cin, accumulate=accumulate, splitk=_BWD_SPLIT)
     else:
         assert Cout % 16 == 0 and Cin % 4 == 0
@@ -1386,33 +1500,30 @@ def conv2d_dgrad(dy, w_ohwi, x_shape, stride, pad, out=None, accumulate=False, d
     return out
 
 
-def conv3_f16_wgrad_ok(B, H, W, Cin, Cout, kh, kw, stride, pad) -> bool:
-    """will conv2d_wgrad of this convolution run the fp16 form (and want the largest magnitudes of dy and x)?"""
-    return _CONV3_F16[0] and conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad)
-
-
-def conv2d_wgrad(dy, x, dw_ohwi, stride, pad, accumulate=True, dy_amax=None, x_amax=None):
-    """dw [Cout,kh,kw,Cin] (+)= sum over pixels dy^T * im2col(x)."""
+def conv2d_wgrad(dy, x, dw_ohwi, stride, pad, accumulate=True, dy_amax=None, x_amax=None, plan=None, col=None):
+    """dw [Cout,kh,kw,Cin] (+)= sum over pixels dy^T * im2col(x).  col: the col buffer the forward of an "im2col" plan built."""
     _chk_f32(dy, x, dw_ohwi)
     B, H, W, Cin = x.shape
     Cout, kh, kw, _ = dw_ohwi.shape
     _, Ho, Wo, _ = dy.shape
     assert dy.is_contiguous() and x.is_contiguous() and dw_ohwi.is_contiguous()
+    if plan is None:
+        plan = conv_wgrad_plan(B, H, W, Cin, Cout, kh, kw, stride, pad)
     Mpix, Kc = B * Ho * Wo, kh * kw * Cin
-    if conv3w_ok(B, H, W, Cin, Cout, kh, kw, stride, pad):
+    if plan.kernel == "conv3":
         if not accumulate:
             dw_ohwi.zero_()
-        if _CONV3_F16[0]:
-            return conv3x3_wgrad(dy, x, dw_ohwi, f16x2=True, dy_amax=dy_amax, x_amax=x_amax)
-        return conv3x3_wgrad(dy, x, dw_ohwi)
+        return conv3x3_wgrad(dy, x, dw_ohwi, f16x2=plan.f16, **(dict(dy_amax=dy_amax, x_amax=x_amax) if plan.f16 else {}))
     sk = _pick_splitk(Cout, Kc, Mpix)
     if not accumulate and sk > 1:
         dw_ohwi.zero_()
     acc = accumulate or sk > 1
-    if kh == 1 and kw == 1 and stride == 1 and pad == 0:
+    if plan.kernel == "im2col":
+        col = conv_col(x, kh, kw, stride, pad) if col is None else col
+        gemm_raw(Cout, Kc, Mpix, dy, Cout, OP_DENSE_R, col, col.shape[1], OP_DENSE_R, dw_ohwi, Kc, accumulate=acc, splitk=sk)
+    elif plan.kernel == "gemm1x1":
         gemm_raw(Cout, Kc, Mpix, dy, Cout, OP_DENSE_R, x, Cin, OP_DENSE_R, dw_ohwi, Kc, accumulate=acc, splitk=sk)
     else:
-        assert Cin % 16 == 0
         gemm_raw(Cout, Kc, Mpix, dy, Cout, OP_DENSE_R, x, Cin, OP_CONV_R, dw_ohwi, Kc, accumulate=acc, splitk=sk,
                  geo=conv_geo(H, W, Cin, Ho, Wo, kh, kw, stride, pad, 0))
     return dw_ohwi

@@ -87,7 +87,9 @@ typedef struct vbg_gemm_desc {
     int bk;                                                 /* k-tile depth: 0 auto, 16 or 32       */
     /* optional BatchNorm statistics of the OUTPUT, fused into the epilogue (the conv in front of a training-mode BatchNorm,
        model/ResNetFPN_ViBERTgrid.py:116-123): per column sum and sum of squares of the stored values are added (fp64 atomics) into
-       slot row (row-tile index % stats_slots) of stats[stats_slots][2*N]; needs splitk == 1, no accumulate, ldc % 4 == 0, C 16-B aligned */
+       slot row (row-tile index % stats_slots) of stats[stats_slots][2*N]; needs splitk == 1, no accumulate, ldc % 4 == 0, C 16-B aligned.
+       The statistics are added on the LDS-staged store path: a tile / bk request that names an instance without one (fp32 form, 128-row
+       tile, 16-deep k-tiles) runs the 64 x 64 tile of the same depth instead */
     double* stats; int stats_slots;
     /* arithmetic form of the products.
        0: v_mfma_f32_32x32x2_f32, exact fp32 products.
@@ -117,6 +119,14 @@ typedef struct vbg_gemm_desc {
 } vbg_gemm_desc;
 
 int vbg_gemm(const vbg_gemm_desc* desc, void* stream);
+/* Which kernel instance vbg_gemm would run for this descriptor, decided by the function vbg_gemm itself launches from: host only (no
+ * device call, no pointer of the descriptor is dereferenced, the automatic split zeroes nothing), the return codes of vbg_gemm.
+ *   out = { BM, BN, BK, vec (1: 16-byte loads, 0: the scalar-load path), prec (the arithmetic form that RUNS: 0 / 1 / 2 / 3 as
+ *           vbg_gemm_desc.bf16), splitk in effect (the automatic split's choice for splitk = 0), 1: the tile leaves through the LDS-staged
+ *           float4 store path / 0: per-lane stores or atomics, accumulate in effect (1 as well where the automatic split adds into a
+ *           zeroed C) }
+ * An empty problem (M, N or the group count 0) launches nothing: VBG_OK with out all zero. */
+int vbg_gemm_variant(const vbg_gemm_desc* desc, int out[8]);
 /* Measurement hooks (bench.py `roofline`; no reference counterpart): the same launch with the dispatch's own begin / end
  * timestamps delivered to two events (hipExtLaunchKernel start / stop events: no barrier packets around the kernel, the figure
  * rocprofv3's kernel trace reports), plus create / destroy / elapsed for those events (hipEvent_t passed as void*). */

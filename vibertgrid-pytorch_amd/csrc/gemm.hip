@@ -100,12 +100,13 @@ struct sched_pipe {
 
 // does this instance store its tile through LDS (gemm_kernel's STAGE_OK)?  The fp32 form's 16-deep k-tiles under a 128-row tile do not
 // have the room: they store per lane, and the frozen-BatchNorm epilogue does not exist there
-template <int BM, int BN, int BK, int AK, int BKD, int PREC>
-constexpr bool gemm_stages_tile() {
+constexpr bool gemm_stages_tile(int BM, int BN, int BK, int AK, int BKD, int PREC) {
     if (PREC != 0) return true;
-    constexpr bool A_KC = (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K), B_KC = (BKD == VBG_OP_DENSE_K);
+    const bool A_KC = (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K), B_KC = (BKD == VBG_OP_DENSE_K);
     return BM * (BN + 4) <= 2 * ((A_KC ? BM * (BK + 4) : BK * (BM + 4)) + (B_KC ? BN * (BK + 4) : BK * (BN + 4)));
 }
+template <int BM, int BN, int BK, int AK, int BKD, int PREC>
+constexpr bool gemm_stages_tile() { return gemm_stages_tile(BM, BN, BK, AK, BKD, PREC); }
 
 // PREC 3: fp32-grade products on the bf16 matrix cores.  Every operand element is split EXACTLY into three bf16 pieces
 // (x = hi + mid + lo: 8 + 8 + 8 significant bits, by truncation) held as three planes of the LDS tile, and a product is the sum
@@ -1095,13 +1096,17 @@ struct launch_timer { hipEvent_t start = nullptr, stop = nullptr; };
 
 template <int BM, int BN, int BK, int NT, int AK, int BKD, bool VEC, int PREC = 0>
 static int launch_one(const vbg_gemm_desc& d, int groups, int maxM, int maxN, hipStream_t s, const launch_timer& t) {
-    if (d.bn.mean && !gemm_stages_tile<BM, BN, BK, AK, BKD, PREC>()) return VBG_EARG;      // never a launch that would skip the epilogue
     dim3 g(cdiv(maxM, BM), cdiv(maxN, BN), groups * d.splitk);
     (void)hipGetLastError();
     if (t.start && t.stop) hipExtLaunchKernelGGL((gemm_kernel<BM, BN, BK, NT, AK, BKD, VEC, PREC>), g, dim3(NT), 0, s, t.start, t.stop, 0, d);
     else hipLaunchKernelGGL((gemm_kernel<BM, BN, BK, NT, AK, BKD, VEC, PREC>), g, dim3(NT), 0, s, d);
     return VBG_OK;
 }
+
+// ---- the dispatch decision: ONE function (gemm_decide) for vbg_gemm and for the query vbg_gemm_variant -------------------------------
+// the kernel instance a descriptor runs: gemm_kernel<BM, BN, BK, 256, a_kind, b_kind, vec, prec>
+struct gemm_variant { int BM, BN, BK, vec, prec; };
+constexpr int variant_key(int BM, int BN, int BK, int vec, int prec) { return (((BM * 1000 + BN) * 100 + BK) * 2 + vec) * 4 + prec; }
 
 // tile code: BM*1000+BN (128128, 128064, 64064); 0 = heuristic.  (A barrier-free one-wave-per-tile variant (NT = 64) was
 // measured 25-40 % slower than the 4-wave blocks on every shape and is not instantiated.)  bk: 16 / 32; 0 = heuristic.
@@ -1122,22 +1127,24 @@ static void pick_tile(const vbg_gemm_desc& d, int groups, int maxM, int maxN, in
     if (bk == 0) bk = (!d.grp && d.K <= 128) ? 16 : 32;
 }
 
-template <int AK, int BKD>
-static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, hipStream_t s, const launch_timer& t) {
-    int tile, bk, rc = VBG_OK;
+// tile and arithmetic form of an ADJUSTED descriptor (gemm_decide: splitk >= 1, bk forced where the geometry demands it, a_vec / b_vec of
+// the gathered operands set) whose kinds are one of the six instantiated pairs
+static gemm_variant pick_variant(const vbg_gemm_desc& d, int groups, int maxM, int maxN) {
+    const int AK = d.a_kind, BKD = d.b_kind;
+    const bool fwd = (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K;
+    int tile, bk;
     pick_tile(d, groups, maxM, maxN, tile, bk);
-    if (!(d.a_vec && d.b_vec)) {                         // unaligned operands: general scalar-load path
-        rc = launch_one<64, 64, 16, 256, AK, BKD, false>(d, groups, maxM, maxN, s, t);
-    } else if (d.bf16 == 2 && d.bk != 16 && (AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K &&
-               (d.tile == 0 ? !((long)cdiv(maxM, 128) * cdiv(maxN, 128) * groups * d.splitk >= 192 && maxN >= 128) : tile == 64064)) {
+    if (!(d.a_vec && d.b_vec)) return {64, 64, 16, 0, 0};          // unaligned operands: general scalar-load path
+    if (d.bf16 == 2 && d.bk != 16 && fwd &&
+        (d.tile == 0 ? !((long)cdiv(maxM, 128) * cdiv(maxN, 128) * groups * d.splitk >= 192 && maxN >= 128) : tile == 64064)) {
         // the fp16-pair form of the forward kinds (PREC 2), where the six-product form would run 64 x 64 tiles: 1024 x 1024 x 12544 163 -> 120 us,
         // the strided 3x3 convolutions 36 -> 29 / 41 -> 30 us.  On the 128 x 128 tiles it measured SLOWER than six products (131072 x 256 x 1024:
         // 391 -> 423 us; a second accumulator set on 304 registers, a VALU-heavier split): those keep PREC 3 (tools/gemm_f16_bench.py)
-        if constexpr ((AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K)
-            rc = launch_one<64, 64, 32, 256, AK, BKD, true, 2>(d, groups, maxM, maxN, s, t);
-    } else if ((d.bf16 == 3 || d.bf16 == 2) && d.bk != 16 &&
-               (AK != VBG_OP_DENSE_R || d.tile != 0 || BKD == VBG_OP_DENSE_R ||
-                (BKD == VBG_OP_CONV_R && d.K / d.splitk >= 2048 && maxM >= 128 && maxN >= 128))) {
+        return {64, 64, 32, 1, 2};
+    }
+    if ((d.bf16 == 3 || d.bf16 == 2) && d.bk != 16 &&
+        (AK != VBG_OP_DENSE_R || d.tile != 0 || BKD == VBG_OP_DENSE_R ||
+         (BKD == VBG_OP_CONV_R && d.K / d.splitk >= 2048 && maxM >= 128 && maxN >= 128))) {
         // fp32-grade split form (tools/gemm_bench.py; --fp32 for the other form).  Forward and dgrad kinds: 128x128x16 tiles (73 KB
         // of LDS, two blocks per CU) from ~200 tiles on -- 4128x3072x768 116 vs 163 us for the fp32 form, the 128x128-map 3x3
         // convs 760 vs 1160 us; at most one wave of tiles runs them 32 deep (123 KB, one block per CU; two tiles in flight) -- and
@@ -1150,10 +1157,11 @@ static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, h
             if (AK == VBG_OP_DENSE_R) tile = (BKD == VBG_OP_CONV_R) ? 128132 : 64064;
             else tile = (t128 >= 192 && maxN >= 128) ? (t128 <= 256 ? 128132 : 128128) : 64064;
         }
-        if (tile == 128132 || (tile == 128128 && d.bk == 32)) rc = launch_one<128, 128, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128128) rc = launch_one<128, 128, 16, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
-        else rc = launch_one<64, 64, 32, 256, AK, BKD, true, 3>(d, groups, maxM, maxN, s, t);
-    } else if (d.bf16 == 1 && (d.bk == 0 || d.bk == 32)) {
+        if (tile == 128132 || (tile == 128128 && d.bk == 32)) return {128, 128, 32, 1, 3};
+        if (tile == 128128) return {128, 128, 16, 1, 3};
+        return {64, 64, 32, 1, 3};
+    }
+    if (d.bf16 == 1 && (d.bk == 0 || d.bk == 32)) {
         // amp: bf16 matrix cores (fp32 operands rounded on the way into LDS).  The loop is bound by operand traffic, not by the
         // MFMAs, so the larger tile wins as soon as it fills the chip.  (Products forced to 16-deep k-tiles -- channel counts
         // that are not a multiple of 32 -- and unaligned operands stay on the fp32 form.)
@@ -1167,27 +1175,30 @@ static int launch_pair(const vbg_gemm_desc& d, int groups, int maxM, int maxN, h
             else big = t128 * d.splitk >= 512 && maxN >= 256;
             tile = big ? 128128 : 64064;
         }
-        if (tile == 128128) rc = launch_one<128, 128, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
-        else rc = launch_one<64, 64, 32, 256, AK, BKD, true, 1>(d, groups, maxM, maxN, s, t);
-    } else if (bk == 32) {
-        if (tile == 128128) rc = launch_one<128, 128, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128064) rc = launch_one<128, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else rc = launch_one<64, 64, 32, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-    } else {
-        if (tile == 128128) rc = launch_one<128, 128, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else if (tile == 128064) rc = launch_one<128, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
-        else rc = launch_one<64, 64, 16, 256, AK, BKD, true>(d, groups, maxM, maxN, s, t);
+        return tile == 128128 ? gemm_variant{128, 128, 32, 1, 1} : gemm_variant{64, 64, 32, 1, 1};
     }
-    if (rc != VBG_OK) return rc;
-    VBG_LAUNCH_RET();
+    const int BK = bk == 32 ? 32 : 16;
+    if (tile == 128128) return {128, 128, BK, 1, 0};
+    if (tile == 128064) return {128, 64, BK, 1, 0};
+    return {64, 64, BK, 1, 0};
 }
 
-}  // namespace vbg
+// everything vbg_gemm settles before its launch: the argument checks, the descriptor as the kernel receives it, the instance, and
+// whether the automatic split wants C zeroed first.  Host only: no pointer of the descriptor is dereferenced, nothing is enqueued
+struct gemm_decision {
+    vbg_gemm_desc d;
+    gemm_variant v;               // BM == 0: an empty problem, nothing to launch
+    int groups, maxM, maxN;
+    bool zero_c;                  // the automatic split is in effect: C[M][N] is zeroed before the launch
+    bool staged;                  // the tile leaves through the LDS-staged float4 stores (the kernel's own condition, epilogue section)
+};
 
-static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::launch_timer& t) {
-    using namespace vbg;
+static int gemm_decide(const vbg_gemm_desc* desc, gemm_decision& o) {
     VBG_CHECK_ARG(desc != nullptr);
-    vbg_gemm_desc d = *desc;
+    vbg_gemm_desc& d = o.d;
+    d = *desc;
+    o.v = gemm_variant{0, 0, 0, 0, 0};
+    o.zero_c = o.staged = false;
     VBG_CHECK_ARG(d.A && d.B && d.C);
     VBG_CHECK_ARG(d.M >= 0 && d.N >= 0 && d.K >= 0);
     VBG_CHECK_ARG(d.splitk >= 0);
@@ -1222,12 +1233,12 @@ static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::lau
             if (d.a_seg_shift[i] > 0) VBG_CHECK_ARG(d.a_H > 0 && d.a_W > 0);
         }
     }
-    const int groups = d.grp ? d.ngroups : 1;
-    VBG_CHECK_ARG(groups >= 1);
-    const int maxM = d.grp ? d.grp_maxM : d.M, maxN = d.grp ? d.grp_maxN : d.N;
-    if (maxM == 0 || maxN == 0 || groups == 0) return VBG_OK;
+    o.groups = d.grp ? d.ngroups : 1;
+    VBG_CHECK_ARG(o.groups >= 1);
+    o.maxM = d.grp ? d.grp_maxM : d.M;
+    o.maxN = d.grp ? d.grp_maxN : d.N;
+    if (o.maxM == 0 || o.maxN == 0 || o.groups == 0) return VBG_OK;
     if (d.K == 0 && !d.grp) return VBG_EARG;
-    hipStream_t s = (hipStream_t)stream;
     const bool conv = d.a_kind == VBG_OP_CONV_K || d.b_kind == VBG_OP_CONV_R || d.b_kind == VBG_OP_WT_R;
     if (conv) {
         VBG_CHECK_ARG(d.geo.Cs % 16 == 0 && d.geo.kh > 0 && d.geo.kw > 0 && d.geo.stride > 0);
@@ -1235,8 +1246,8 @@ static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::lau
         if (d.geo.Cs % 32 != 0) d.bk = 16;                      // a k-tile must stay inside one filter tap
     }
     // Automatic split-K for forward / dgrad products whose output has too few tiles to fill the chip but a long reduction
-    // (layer4 convolutions: 2048 x 512 outputs = 256 tiles, K = 4608: 73 -> 110 TF/s): the (small) output is zeroed here and the
-    // splits accumulate with atomics.  Only where the epilogue is linear (no ReLU / GELU; the bias is added by split 0).
+    // (layer4 convolutions: 2048 x 512 outputs = 256 tiles, K = 4608: 73 -> 110 TF/s): the (small) output is zeroed by the caller of
+    // this function (zero_c) and the splits accumulate with atomics.  Only where the epilogue is linear (no ReLU / GELU; the bias is added by split 0).
     // Opt-in (splitk == 0): the atomic accumulation order is not reproducible run to run, so inference paths keep splitk = 1.
     const bool auto_split = d.splitk == 0;
     if (d.splitk < 1) d.splitk = 1;
@@ -1250,8 +1261,7 @@ static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::lau
             if (sk > nkt / 12) sk = nkt / 12;
             if (sk > 8) sk = 8;
             if (sk >= 2) {
-                const hipError_t e = hipMemset2DAsync(d.C, (size_t)d.ldc * 4, 0, (size_t)d.N * 4, (size_t)d.M, s);
-                if (e != hipSuccess) return (int)e;
+                o.zero_c = true;
                 d.splitk = sk;
                 d.accumulate = 1;
             }
@@ -1261,16 +1271,88 @@ static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::lau
     if (d.a_kind == VBG_OP_CONV_K) { VBG_CHECK_ARG((uintptr_t)d.A % 16 == 0); d.a_vec = 1; }
     if (d.b_kind == VBG_OP_CONV_R) { VBG_CHECK_ARG((uintptr_t)d.B % 16 == 0 && d.N % 4 == 0); d.b_vec = 1; }
     if (d.b_kind == VBG_OP_WT_R) { VBG_CHECK_ARG((uintptr_t)d.B % 16 == 0 && d.N % 4 == 0 && d.geo.dgrad == 1); d.b_vec = 1; }
-    if (d.a_kind == VBG_OP_DENSE_K && d.b_kind == VBG_OP_DENSE_K) return launch_pair<VBG_OP_DENSE_K, VBG_OP_DENSE_K>(d, groups, maxM, maxN, s, t);
-    if (d.a_kind == VBG_OP_DENSE_K && d.b_kind == VBG_OP_DENSE_R) return launch_pair<VBG_OP_DENSE_K, VBG_OP_DENSE_R>(d, groups, maxM, maxN, s, t);
-    if (d.a_kind == VBG_OP_DENSE_R && d.b_kind == VBG_OP_DENSE_R) return launch_pair<VBG_OP_DENSE_R, VBG_OP_DENSE_R>(d, groups, maxM, maxN, s, t);
-    if (d.a_kind == VBG_OP_CONV_K && d.b_kind == VBG_OP_DENSE_K) return launch_pair<VBG_OP_CONV_K, VBG_OP_DENSE_K>(d, groups, maxM, maxN, s, t);
-    if (d.a_kind == VBG_OP_CONV_K && d.b_kind == VBG_OP_WT_R) return launch_pair<VBG_OP_CONV_K, VBG_OP_WT_R>(d, groups, maxM, maxN, s, t);
-    if (d.a_kind == VBG_OP_DENSE_R && d.b_kind == VBG_OP_CONV_R) {
-        VBG_CHECK_ARG(d.N == d.geo.kh * d.geo.kw * d.geo.Cs);
-        return launch_pair<VBG_OP_DENSE_R, VBG_OP_CONV_R>(d, groups, maxM, maxN, s, t);
+    const int ak = d.a_kind, bkd = d.b_kind;
+    VBG_CHECK_ARG((ak == VBG_OP_DENSE_K && (bkd == VBG_OP_DENSE_K || bkd == VBG_OP_DENSE_R)) ||
+                  (ak == VBG_OP_DENSE_R && (bkd == VBG_OP_DENSE_R || bkd == VBG_OP_CONV_R)) ||
+                  (ak == VBG_OP_CONV_K && (bkd == VBG_OP_DENSE_K || bkd == VBG_OP_WT_R)));
+    if (bkd == VBG_OP_CONV_R) VBG_CHECK_ARG(d.N == d.geo.kh * d.geo.kw * d.geo.Cs);
+    gemm_variant v = pick_variant(d, o.groups, o.maxM, o.maxN);
+    // the fused statistics are added on the staged store path only: an instance that cannot stage its tile (the fp32 form's 16-deep
+    // k-tiles under a 128-row tile) would store C and leave the statistics untouched, so such a product runs the 64 x 64 tile of the
+    // same depth, which stages for every kind pair
+    if (d.stats && !gemm_stages_tile(v.BM, v.BN, v.BK, ak, bkd, v.prec)) v.BM = v.BN = 64;
+    const bool stages = gemm_stages_tile(v.BM, v.BN, v.BK, ak, bkd, v.prec);
+    if (d.bn.mean && !stages) return VBG_EARG;                 // never a launch that would skip the epilogue
+    o.staged = stages && !(d.accumulate && d.splitk > 1) && (d.ldc & 3) == 0 && (d.slab_stride & 3) == 0 && ((uintptr_t)d.C & 15) == 0 &&
+               (d.epi != VBG_EPI_GELU_DUAL || ((uintptr_t)d.C2 & 15) == 0);
+    o.v = v;
+    return VBG_OK;
+}
+
+// the launch: a switch over the decision.  Every case is one instantiation of gemm_kernel for the pair (tests/test_gemm_variant_host.py
+// keeps the same list); the fp16-pair form exists for the two forward pairs only
+template <int AK, int BKD>
+static int launch_pair(const gemm_decision& o, hipStream_t s, const launch_timer& t) {
+    const vbg_gemm_desc& d = o.d;
+    const int groups = o.groups, maxM = o.maxM, maxN = o.maxN;
+    int rc = VBG_EARG;
+#define VBG_GEMM_CASE(BM, BN, BK, VEC, PREC) \
+    case variant_key(BM, BN, BK, VEC, PREC): rc = launch_one<BM, BN, BK, 256, AK, BKD, (VEC != 0), PREC>(d, groups, maxM, maxN, s, t); break;
+    switch (variant_key(o.v.BM, o.v.BN, o.v.BK, o.v.vec, o.v.prec)) {
+        VBG_GEMM_CASE(64, 64, 16, 0, 0)
+        VBG_GEMM_CASE(64, 64, 16, 1, 0)
+        VBG_GEMM_CASE(128, 64, 16, 1, 0)
+        VBG_GEMM_CASE(128, 128, 16, 1, 0)
+        VBG_GEMM_CASE(64, 64, 32, 1, 0)
+        VBG_GEMM_CASE(128, 64, 32, 1, 0)
+        VBG_GEMM_CASE(128, 128, 32, 1, 0)
+        VBG_GEMM_CASE(64, 64, 32, 1, 1)
+        VBG_GEMM_CASE(128, 128, 32, 1, 1)
+        VBG_GEMM_CASE(64, 64, 32, 1, 3)
+        VBG_GEMM_CASE(128, 128, 16, 1, 3)
+        VBG_GEMM_CASE(128, 128, 32, 1, 3)
+        case variant_key(64, 64, 32, 1, 2):
+            if constexpr ((AK == VBG_OP_DENSE_K || AK == VBG_OP_CONV_K) && BKD == VBG_OP_DENSE_K)
+                rc = launch_one<64, 64, 32, 256, AK, BKD, true, 2>(d, groups, maxM, maxN, s, t);
+            break;
+        default: break;
     }
+#undef VBG_GEMM_CASE
+    if (rc != VBG_OK) return rc;
+    VBG_LAUNCH_RET();
+}
+
+}  // namespace vbg
+
+static int gemm_dispatch(const vbg_gemm_desc* desc, void* stream, const vbg::launch_timer& t) {
+    using namespace vbg;
+    gemm_decision o;
+    const int rc = gemm_decide(desc, o);
+    if (rc != VBG_OK || o.v.BM == 0) return rc;
+    const vbg_gemm_desc& d = o.d;
+    hipStream_t s = (hipStream_t)stream;
+    if (o.zero_c) {
+        const hipError_t e = hipMemset2DAsync(d.C, (size_t)d.ldc * 4, 0, (size_t)d.N * 4, (size_t)d.M, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (d.a_kind == VBG_OP_DENSE_K && d.b_kind == VBG_OP_DENSE_K) return launch_pair<VBG_OP_DENSE_K, VBG_OP_DENSE_K>(o, s, t);
+    if (d.a_kind == VBG_OP_DENSE_K && d.b_kind == VBG_OP_DENSE_R) return launch_pair<VBG_OP_DENSE_K, VBG_OP_DENSE_R>(o, s, t);
+    if (d.a_kind == VBG_OP_DENSE_R && d.b_kind == VBG_OP_DENSE_R) return launch_pair<VBG_OP_DENSE_R, VBG_OP_DENSE_R>(o, s, t);
+    if (d.a_kind == VBG_OP_CONV_K && d.b_kind == VBG_OP_DENSE_K) return launch_pair<VBG_OP_CONV_K, VBG_OP_DENSE_K>(o, s, t);
+    if (d.a_kind == VBG_OP_CONV_K && d.b_kind == VBG_OP_WT_R) return launch_pair<VBG_OP_CONV_K, VBG_OP_WT_R>(o, s, t);
+    if (d.a_kind == VBG_OP_DENSE_R && d.b_kind == VBG_OP_CONV_R) return launch_pair<VBG_OP_DENSE_R, VBG_OP_CONV_R>(o, s, t);
     return VBG_EARG;
+}
+
+extern "C" int vbg_gemm_variant(const vbg_gemm_desc* desc, int out[8]) {
+    VBG_CHECK_ARG(out != nullptr);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    vbg::gemm_decision o;
+    const int rc = vbg::gemm_decide(desc, o);
+    if (rc != VBG_OK || o.v.BM == 0) return rc;
+    out[0] = o.v.BM; out[1] = o.v.BN; out[2] = o.v.BK; out[3] = o.v.vec; out[4] = o.v.prec;
+    out[5] = o.d.splitk; out[6] = o.staged ? 1 : 0; out[7] = o.d.accumulate;
+    return VBG_OK;
 }
 
 extern "C" int vbg_gemm(const vbg_gemm_desc* desc, void* stream) { return gemm_dispatch(desc, stream, vbg::launch_timer{}); }

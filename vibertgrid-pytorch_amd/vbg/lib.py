@@ -181,6 +181,7 @@ EPI_NONE, EPI_RELU, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD = 0, 1, 2, 3
 SIGNATURES = {
     "vbg_version": (c_int, []),
     "vbg_gemm": (c_int, [C.POINTER(GemmDesc), c_vp]),
+    "vbg_gemm_variant": (c_int, [C.POINTER(GemmDesc), C.POINTER(c_int * 8)]),
     "vbg_gemm_timed": (c_int, [C.POINTER(GemmDesc), c_vp, c_vp, c_vp]),
     "vbg_timer_create": (c_int, [c_vp]),
     "vbg_timer_destroy": (c_int, [c_vp]),

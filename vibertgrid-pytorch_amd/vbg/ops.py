@@ -186,12 +186,11 @@ class BnEpi:
         return e
 
 
-def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, epi=EPI_NONE, C2=None, accumulate=False,
-             splitk=1, geo=None, segs=None, a_hw=(0, 0), a_relu_scale=None, grp=None, ngroups=0, grp_max=(0, 0), tile=0,
-             alpha=1.0, a_ptr_off=0, b_ptr_off=0, c_ptr_off=0, bk=0, stats=None, slab_stride=0, f16=False, bn=None):
-    """A, B, Cout: tensors (their data_ptr + element offsets are used).  stats: BatchNorm slot workspace [slots*2N] fp64 that receives the
-    per-column sum / sum of squares of the output (fused into the epilogue; the launch is then never split).  bn: a BnEpi -- frozen
-    BatchNorm of the output in the epilogue (the launch is never split; the library rejects what cannot go with it)."""
+def _gemm_desc(seen, M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, epi=EPI_NONE, C2=None, accumulate=False,
+               splitk=1, geo=None, segs=None, a_hw=(0, 0), a_relu_scale=None, grp=None, ngroups=0, grp_max=(0, 0), tile=0,
+               alpha=1.0, a_ptr_off=0, b_ptr_off=0, c_ptr_off=0, bk=0, stats=None, slab_stride=0, f16=False, bn=None):
+    """the vbg_gemm_desc of a gemm_raw call, from the library state gemm_raw runs under (_AMP / _SPLIT3 / _GEMM_F16 / _DET / the forced
+    tile): shared by gemm_raw (seen = _seen, the dispatch log) and gemm_variant (seen = a no-op: a query is no dispatch)"""
     d = GemmDesc()
     d.M, d.N, d.K = int(M), int(N), int(K)
     ap = A.data_ptr() + 4 * a_ptr_off
@@ -222,8 +221,8 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
         d.stats, d.stats_slots = stats.data_ptr(), bn_slots()
     if bn is not None:
         bn.fill(d.bn)
-        _seen("bn:epilogue")
-        _seen("bn:epilogue_gemm")
+        seen("bn:epilogue")
+        seen("bn:epilogue_gemm")
     if splitk == 1 and not accumulate and torch.is_grad_enabled() and stats is None and bn is None:
         splitk = 0          # training: let the library split few-tile / long-K products; no_grad (inference, eval) stays bit-reproducible
     if splitk == 0 and accumulate:
@@ -231,13 +230,11 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
     if splitk == 0 or (accumulate and splitk > 1):
         if _DET[0]:
             splitk = 1
-            _seen("det:gemm_splitk")
+            seen("det:gemm_splitk")
         else:
-            _seen("fatomic:gemm_splitk")
+            seen("fatomic:gemm_splitk")
     if stats is not None:
-        _seen("fatomic:gemm_stats")
-    if accumulate:
-        _untag(Cout)
+        seen("fatomic:gemm_stats")
     d.epi, d.alpha, d.accumulate, d.splitk, d.tile = epi, float(alpha), int(bool(accumulate)), int(splitk), int(tile)
     d.bk = int(bk)
     d.slab_stride = int(slab_stride)          # (> 0: split s stores its partial product at Cout + s * slab_stride; slab_reduce adds them)
@@ -246,7 +243,7 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
         # vbg_gemm_desc.bf16 = 2, round 6) -- half the matrix-core work of the six-product form; the library runs it for the forward kinds only
         d.bf16 = 1 if _AMP[0] else (2 if (f16 and _GEMM_F16[0] and grp is None) else 3)
         if _DISPATCH[0] is not None and not _AMP[0] and grp is None:
-            _seen("gemm:f16x2" if d.bf16 == 2 else "gemm:bf16x3")
+            seen("gemm:f16x2" if d.bf16 == 2 else "gemm:bf16x3")
         if bk == 16:
             d.bk = 0        # (the 16-deep k-tiles are an fp32-form tuning)
         if grp is not None and not _AMP[0]:
@@ -256,13 +253,47 @@ def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, *, bias=None, e
     if grp is not None:
         d.grp, d.ngroups = grp.data_ptr(), int(ngroups)
         d.grp_maxM, d.grp_maxN = int(grp_max[0]), int(grp_max[1])
+    return d
+
+
+def gemm_raw(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, **kw):
+    """A, B, Cout: tensors (their data_ptr + element offsets are used).  Keywords: _gemm_desc's.  stats: BatchNorm slot workspace
+    [slots*2N] fp64 that receives the per-column sum / sum of squares of the output (fused into the epilogue; the launch is then never
+    split).  bn: a BnEpi -- frozen BatchNorm of the output in the epilogue (the launch is never split; the library rejects what cannot
+    go with it)."""
+    d = _gemm_desc(_seen, M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, **kw)
+    if d.accumulate:
+        _untag(Cout)
     prof = _GEMM_PROF
-    if prof is not None and prof.match(a_kind, b_kind, grp is not None):
+    if prof is not None and prof.match(a_kind, b_kind, d.grp is not None):
         e0, e1 = prof.events()
         check(lib.vbg_gemm_timed(C.byref(d), _stream(), e0, e1), "vbg_gemm_timed")
         prof.add(2.0 * M * N * K, e0, e1, 1 if (_AMP[0] or not _SPLIT3[0]) else 6)
         return
     check(lib.vbg_gemm(C.byref(d), _stream()), "vbg_gemm")
+
+
+class GemmVariant(NamedTuple):
+    """include/vbg.h vbg_gemm_variant: the kernel instance (tile, k-tile depth, vector loads, arithmetic form that runs) and the split /
+    store path / accumulate in effect"""
+    BM: int
+    BN: int
+    BK: int
+    vec: int
+    prec: int
+    splitk: int
+    staged: int
+    accumulate: int
+
+
+def gemm_variant(M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, **kw) -> GemmVariant:
+    """which kernel instance gemm_raw(the same arguments) runs, under the same library state: the library's own dispatch decision, taken
+    on the host.  Nothing is launched, logged or zeroed and no pointer is followed, so the tensors may live on the CPU (only their
+    addresses' alignment counts).  An argument error of vbg_gemm raises the same VbgError here."""
+    d = _gemm_desc(lambda key: None, M, N, K, A, lda, a_kind, B, ldb, b_kind, Cout, ldc, **kw)
+    out = (C.c_int * 8)()
+    check(lib.vbg_gemm_variant(C.byref(d), C.byref(out)), "vbg_gemm_variant")
+    return GemmVariant(*out)
 
 
 # ----------------------------------------------------------------------------------------------

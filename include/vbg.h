@@ -754,6 +754,25 @@ int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const 
  * atomics: the same bits with and without the deterministic mode.  Emissions holding NaN or infinities are outside the contract. */
 int vbg_crf_posterior(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                       int stop_tag, void* ws, int* path, float* score, float* logz, float* marginals, void* stream);
+/* Log posteriors of a GIVEN tag path under the same CRF, row by row, for all documents in ONE launch: what a span confidence
+ * P(y_s .. y_e = the path's tags | x) is added up from.  emissions, doc_off (device), trans and the START / STOP conventions are
+ * vbg_crf_posterior's; path int32 [N] holds any tags in [0, ntag) -- the Viterbi path, a gold sequence, an alternative.
+ *   lm [N]   lm[t] = log p(y_t = path[t] | x): from a_t + b_t with the row's own maximum and sum, vbg_crf_posterior's arithmetic for
+ *            its row (expf / logf, tag order);
+ *   lc [N]   lc[t] = log p(y_t = path[t] | y_{t-1} = path[t-1], x) for a row with a row of its document in front of it,
+ *                  = trans[path[t]][path[t-1]] + (em_t[path[t]] + b_t[path[t]] - max_k(em_t[k] + b_t[k])) - b_{t-1}[path[t-1]],
+ *            with b the backward vector re-centred at every step, b_{t-1}[j] = log sum_i exp(trans[i][j] + em_t[i] + b_t[i]) - the same
+ *            maximum; lc of a document's first row is its lm.
+ * So lm[s] + sum of lc[s+1 .. e] = log P(y_s .. y_e | x), and the sum of lc over a document = path score - log Z.  Every term is
+ * of the size of an emission + a transition + log ntag: log Z is never formed and nothing grows with the row index.
+ * ws: workspace of N * ntag 4-byte words (the forward vectors), contents undefined afterwards.  An empty document touches no row.  A
+ * path entry outside [0, ntag) gives lm = lc = -INFINITY on its row and lc = -INFINITY on the next row of its document; it is compared
+ * and clamped, never used as an address.  START / STOP in the path are legal and give values near -10000.  No atomics: the same
+ * bits with and without the deterministic mode.  Emissions holding NaN or infinities are outside the contract.
+ * Argument errors, before any launch: NULL doc_off / trans, ntag outside [1, 64], ndoc < 0, start_tag / stop_tag outside [0, ntag),
+ * NULL emissions / path / ws / lm / lc with ndoc > 0 (the row count lies on the device).  ndoc == 0 is a no-op. */
+int vbg_crf_path_logp(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
+                      int stop_tag, const int* path, void* ws, float* lm, float* lc, void* stream);
 /* The training loss of the same CRF with a gradient whose error does not grow with the document's length (vbg_crf_nll_bwd forms every
  * marginal as exp(alpha + beta - logZ) from unnormalised vectors: DESIGN.md, section 8).  Documents, row ranges, trans, the -10000
  * initial vector and the START / STOP conventions are vbg_crf_nll_fwd's.  ONE launch for all documents gives
@@ -821,6 +840,27 @@ int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int 
 int vbg_field_decode_tags(const float* marginals, const int* path, const int* h_doc_off, int ndoc, int ntag, int C,
                           const int* h_tag_class, const int* h_tag_begin, int use_thresh, double thresh, int* cls, float* score,
                           vbg_decode_rec* best, void* stream);
+/* EVERY run of every document instead of the winners -- a page with dozens of `question` / `answer` entities has dozens of runs per
+ * class.  Rows, cls, score, the threshold in double, run heads (a class change; in the tags form also a begin tag) and run means are
+ * vbg_field_decode's / vbg_field_decode_tags's, the means bit for bit; the limits (C and ntag <= 64, fewer than 2^20 rows per
+ * document, HOST h_doc_off, 512 documents to a launch) and the argument errors are theirs too.
+ *   runs [N]  one vbg_run_rec per ROW.  The record at a run's first row holds the run: start (relative to the document), len, cls,
+ *             mean, logp; every other row's record has len == 0 (all fields 0).  The records with len > 0 are the document's runs in
+ *             row order.  Each record has exactly one writer: nothing depends on scheduling.
+ *   filing    every run under its OWN class, the last one included, in both forms (the `prev_class` quirk is the winner loop's);
+ *             class-0 runs and, in the tags form, runs whose integer sum is 0 are listed as well.
+ *   logp      tags form: lm[s] + the fp64 sum of lc[s+1 .. e] over the run's rows s .. e, with lm / lc vbg_crf_path_logp's for the
+ *             same path: log P(y_s .. y_e = the path's tags | x).  Taken as a difference of fp64 prefix sums: equal to the
+ *             sequential sum within ~1e-9.  -INFINITY or NaN in lm / lc make their document's logp meaningless; nothing faults.
+ *             Scores form: 0.0.
+ * A call without rows (ndoc == 0, or only empty documents) launches nothing and needs no buffer.  NULL x / cls / score / runs -- and in
+ * the tags form path / lm / lc -- with rows present is an argument error. */
+typedef struct vbg_run_rec { int start; int len; int cls; int pad; double mean; double logp; } vbg_run_rec;   /* 32 bytes */
+int vbg_field_runs(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls, float* score,
+                   vbg_run_rec* runs, void* stream);
+int vbg_field_runs_tags(const float* marginals, const int* path, const float* lm, const float* lc, const int* h_doc_off, int ndoc,
+                        int ntag, int C, const int* h_tag_class, const int* h_tag_begin, int use_thresh, double thresh, int* cls,
+                        float* score, vbg_run_rec* runs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Validation counts of `validate` (csrc/metrics.hip): what pipeline/criteria.py's token_F1_criteria, token_classification_criteria and

@@ -377,6 +377,132 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
     }
 }
 
+// Log posteriors of a GIVEN tag path (vbg_crf_path_logp): one wave per document, lane i owns tag i, crf_posterior_kernel's shape
+// without its Viterbi chain and its marginal rows -- transitions in registers, the previous vector broadcast from LDS, both
+// recursions in log space and re-centred at every step, loads one step ahead.  The re-centred backward vector gives the chain's
+// conditionals directly:
+//     log p(y_t = i | y_{t-1} = j, x) = tr[i][j] + (em_t[i] + b_t[i] - max_k(em_t[k] + b_t[k])) - b_{t-1}[j],
+// b_{t-1}[j] = log sum_i exp(tr[i][j] + em_t[i] + b_t[i]) - the same maximum: the step that forms b_{t-1} has all three terms in
+// hand.  The two it needs per row are picked without a data-dependent address that could leave the tables: em_t + b_t from the LDS
+// vector at the clamped tag, b_{t-1} from the lane of the clamped tag.  The path itself stays off the chain: its tags wait in
+// registers, 64 positions to a load and a tile ahead, and a step takes its two with v_readlane -- a load per step whose address is the
+// same in every lane becomes a scalar load, which returns out of order and makes every LDS wait of the step wait for it as well.  The
+// step leaves its part of the conditional in the lane of its tile row (a select); the transition is added where the rows go out.
+// log Z never enters and the forward pass carries no sum of maxima.  The marginal of the path's tag is taken from a_t + b_t as
+// crf_posterior_kernel takes its rows: 64 rows wait in an LDS tile (odd row stride), one lane per row forms maximum and sum in tag
+// order (expf / logf: off the chain) and writes the row's lm and lc.
+template <int NTP, bool HALF>
+__global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restrict__ em, const int* __restrict__ doc_off,
+                                                           const float* __restrict__ trans, int ntag, int start, int stop,
+                                                           const int* __restrict__ path, float* __restrict__ ws,
+                                                           float* __restrict__ lm, float* __restrict__ lc) {
+    static_assert(!HALF || NTP <= 32, "two lanes per tag need ntag <= 32");
+    constexpr int JW = HALF ? NTP / 2 : NTP;                // previous tags per lane
+    static_assert(JW % 4 == 0, "the vectors are read four values at a time");
+    __shared__ __attribute__((aligned(16))) float s_a[2][CRF_MAX_TAGS];
+    __shared__ float s_tile[CRF_TILE_ROWS * CRF_TILE_STRIDE];
+    const int d = blockIdx.x, lane = threadIdx.x;
+    const int i = HALF ? (lane & 31) : lane;                // the lane's tag
+    const int j0 = HALF ? (lane >> 5) * JW : 0;             // first previous tag of the lane's slice
+    const int r0 = doc_off[d], n = doc_off[d + 1] - r0;
+    if (n <= 0) return;
+    const bool own = lane < ntag;                           // the lanes that store: one per tag
+    const int ic = i < ntag ? i : ntag - 1;                 // lanes past the tags repeat the last tag's loads and store nothing
+    const float NEG = -INFINITY;
+
+    float tw[JW];
+#pragma unroll
+    for (int j = 0; j < JW; ++j) tw[j] = j0 + j < ntag ? trans[ic * ntag + j0 + j] : NEG;
+    s_a[0][lane] = own ? (lane == start ? 0.f : -10000.f) : NEG;
+    s_a[1][lane] = NEG;
+    __syncthreads();
+
+    // ---- forward, t = 0 .. n - 1: a_t[i] = em + log sum_j exp(prev[j] + tr[i][j]) - max(prev), crf_posterior_kernel's statement
+    float e_next = em[(long long)r0 * ntag + ic];
+    for (int t = 0; t < n; ++t) {
+        const float e = e_next;
+        if (t + 1 < n) e_next = em[(long long)(r0 + t + 1) * ntag + ic];
+        float mx, m2, s;
+        lse_slice<JW>(s_a[t & 1] + j0, tw, mx, m2, s);
+        lse_join<HALF>(mx, m2, s);
+        const float a = e + ((m2 - mx) + __logf(s));
+        s_a[(t + 1) & 1][lane] = own ? a : NEG;
+        if (own) ws[(long long)(r0 + t) * ntag + lane] = a;
+        __syncthreads();
+    }
+
+    // ---- backward, t = n - 1 .. 0.  tw becomes the lane's slice of tag i's COLUMN: tw[k] = score of i -> j0 + k
+#pragma unroll
+    for (int k = 0; k < JW; ++k) tw[k] = j0 + k < ntag ? trans[(j0 + k) * ntag + ic] : NEG;
+    float b = own ? trans[stop * ntag + lane] : NEG;        // beta of the last position: the transition to STOP
+    long long row = (long long)(r0 + n - 1);
+    float a_next = ws[row * ntag + ic], e_next_b = em[row * ntag + ic];
+    // the path's tags, a tile of positions at a time and a tile ahead: lane k holds the tag of position top - k (yv) and of the
+    // position in front of it (yq), top = the position of tile row 0; yc / qc are the same two clamped into the table
+    const int last = ntag - 1;
+    int yv = 0, yq = 0, yc = 0, qc = 0, yv_next, yq_next;
+    {
+        const int p = n - 1 - lane;
+        yv_next = p >= 0 ? path[r0 + p] : 0;
+        yq_next = p >= 1 ? path[r0 + p - 1] : 0;
+    }
+    float part = 0.f;                                       // lane k: (em_t + b_t)[y_t] - max - b_{t-1}[y_{t-1}] of tile row k
+    int slot = 0;                                           // rows waiting in the tile: tile row k holds position t + slot - 1 - k
+    for (int t = n - 1; t >= 0; --t) {
+        const float a = a_next, e = e_next_b;
+        if (t > 0) {
+            row = (long long)(r0 + t - 1);
+            a_next = ws[row * ntag + ic];
+            e_next_b = em[row * ntag + ic];
+        }
+        if (slot == 0) {
+            yv = yv_next;
+            yq = yq_next;
+            yc = min(max(yv, 0), last);
+            qc = min(max(yq, 0), last);
+            const int p = t - CRF_TILE_ROWS - lane;
+            yv_next = p >= 0 ? path[r0 + p] : 0;
+            yq_next = p >= 1 ? path[r0 + p - 1] : 0;
+        }
+        if (own) s_tile[slot * CRF_TILE_STRIDE + lane] = a + b;
+        if (t > 0) {
+            // beta of position t - 1: b[i] = log sum_k exp(tr[k][i] + em_t[k] + b_t[k]) - max(em_t + b_t), and what row t's
+            // conditional takes from the two vectors
+            const int yt = __builtin_amdgcn_readlane(yc, slot), yp = __builtin_amdgcn_readlane(qc, slot);
+            float* nbuf = s_a[t & 1];
+            nbuf[lane] = own ? e + b : NEG;
+            __syncthreads();
+            float mx, m2, s;
+            lse_slice<JW>(nbuf + j0, tw, mx, m2, s);
+            lse_join<HALF>(mx, m2, s);
+            const float nby = nbuf[yt];
+            b = (m2 - mx) + __logf(s);
+            const float bp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), yp));     // (the builtin moves 32 bits as an integer)
+            if (lane == slot) part = (nby - mx) - bp;
+        }
+        ++slot;
+        if (slot == CRF_TILE_ROWS || t == 0) {
+            __syncthreads();
+            if (lane < slot) {                              // one lane per row: maximum and sum in tag order, the path's tag picked
+                const float* p = s_tile + lane * CRF_TILE_STRIDE;
+                const int pos = t + slot - 1 - lane;
+                const bool in = (unsigned)yv < (unsigned)ntag;
+                float mx = p[0];
+                for (int k = 1; k < ntag; ++k) mx = fmaxf(mx, p[k]);
+                float s = 0.f;
+                for (int k = 0; k < ntag; ++k) s += expf(p[k] - mx);
+                const float v = in ? (p[yc] - mx) - logf(s) : NEG;
+                lm[r0 + pos] = v;
+                float c = v;                                // the document's first row has no row in front: its conditional is its marginal
+                if (pos > 0) c = in && (unsigned)yq < (unsigned)ntag ? trans[yc * ntag + qc] + part : NEG;
+                lc[r0 + pos] = c;
+            }
+            slot = 0;
+            __syncthreads();
+        }
+    }
+}
+
 // Training loss and gradient that hold at any length (vbg_crf_nll_stable): one wave per document, lane i owns tag i.
 //
 // Nothing that grows with the row index is ever formed.  The forward vectors are crf_posterior_kernel's: log space, the maximum of
@@ -666,6 +792,24 @@ extern "C" int vbg_crf_posterior(const float* emissions, const int* doc_off, int
     else if (ntag <= 48) VBG_CRF_POST(48, false);
     else VBG_CRF_POST(64, false);
 #undef VBG_CRF_POST
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_crf_path_logp(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
+                                 int stop_tag, const int* path, void* ws, float* lm, float* lc, void* stream) {
+    VBG_CHECK_ARG(doc_off && trans && ndoc >= 0);
+    VBG_CHECK_ARG(ntag >= 1 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    if (ndoc == 0) return VBG_OK;
+    VBG_CHECK_ARG(emissions && path && ws && lm && lc);
+    float* w = static_cast<float*>(ws);
+#define VBG_CRF_PLOGP(NTP, HALF) VBG_LAUNCH((crf_path_logp_kernel<NTP, HALF>), dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, \
+                                            start_tag, stop_tag, path, w, lm, lc)
+    if (ntag <= 8) VBG_CRF_PLOGP(8, true);
+    else if (ntag <= 16) VBG_CRF_PLOGP(16, true);
+    else if (ntag <= 32) VBG_CRF_PLOGP(32, true);
+    else if (ntag <= 48) VBG_CRF_PLOGP(48, false);
+    else VBG_CRF_PLOGP(64, false);
+#undef VBG_CRF_PLOGP
     VBG_LAUNCH_RET();
 }
 

@@ -204,6 +204,155 @@ __global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* 
     }
 }
 
+// EVERY run of a document, not the winners (vbg_field_runs / vbg_field_runs_tags): field_decode_kernel's rows, heads and prefix sums,
+// and in place of its winner tables one vbg_run_rec per ROW.  The record of a run lies at the run's first row and is written by the
+// thread that closes the run -- the next head, which knows where the run in front of it began, or after the walk thread 0 for the
+// last run; every row that is no head writes its own record with len 0.  One writer per record, no ranking, no compaction: the host
+// keeps the records with len > 0, and they stand in row order.  Every run is filed under its own class in both instances: the
+// reference's `prev_class` quirk belongs to its winner loop, not to a listing.
+// TAGS adds the run's log posterior under the CRF from vbg_crf_path_logp's rows: lm of the first row + the fp64 sum of lc over the
+// rest, the sum taken as a difference of a second prefix sum L (inclusive, fp64): rows h1 + 1 .. h2 - 1 hold L(h2 - 1) - L(h1).
+template <bool TAGS>
+__global__ __launch_bounds__(DEC_THREADS) void field_runs_kernel(const float* __restrict__ x, const int* __restrict__ path,
+                                                                 const float* __restrict__ lm, const float* __restrict__ lc, dec_docs docs,
+                                                                 dec_tags tags, int cols, int use_thresh, double thresh,
+                                                                 int* __restrict__ cls_out, float* __restrict__ score_out,
+                                                                 vbg_run_rec* __restrict__ runs) {
+    using sum_t = std::conditional_t<TAGS, long long, double>;
+    __shared__ int s_cls[DEC_THREADS];                      // class of the chunk's rows
+    __shared__ sum_t s_pb[DEC_THREADS];                     // sum of the document's scores in front of the row
+    __shared__ double s_pl[DEC_THREADS];                    // TAGS: sum of the document's lc up to and including the row
+    __shared__ sum_t s_wtot[DEC_WAVES];
+    __shared__ double s_wtot_l[DEC_WAVES];
+    __shared__ int s_whead[DEC_WAVES];                      // last run head inside the wave's rows, or -1
+    __shared__ int s_tc[DEC_MAX_C], s_tb[DEC_MAX_C];        // TAGS: the two tag tables
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int r0 = docs.off[blockIdx.x], n = docs.off[blockIdx.x + 1] - r0;
+    if constexpr (TAGS) {
+        if (t < DEC_MAX_C) { s_tc[t] = tags.cls[t]; s_tb[t] = tags.begin[t]; }
+    }
+    __syncthreads();
+
+    // carried from chunk to chunk, the same in every thread
+    sum_t total = 0;         // sum of the scores of the rows in front of the chunk
+    double total_l = 0.0;    // sum of lc over the rows in front of the chunk
+    int open_head = -1;      // first row of the run that is open at the chunk's start
+    sum_t open_pb = 0;       // sum of the scores in front of that row
+    double open_pl = 0.0;    // sum of lc up to and including that row
+    int prev_last = -1;      // class of the row in front of the chunk (-1: none, so row 0 is a head)
+    int last_cls = 0;        // class of the document's last row
+    for (int base = 0; base < n; base += DEC_THREADS) {
+        const int g = base + t;
+        const bool valid = g < n;
+        int c = -1;
+        bool begin = false;
+        float sc = 0.f;
+        double own_l = 0.0;
+        if (valid) {                                        // the row, as field_decode_kernel forms it
+            const float* p = x + (long long)(r0 + g) * cols;
+            if constexpr (TAGS) {
+                const int tag = path[r0 + g];
+                c = 0;
+                if (tag >= 0 && tag < cols) {               // (a tag outside the table: class 0, score 0)
+                    c = s_tc[tag];
+                    begin = s_tb[tag] != 0;
+                    for (int k = 0; k < cols; ++k)
+                        if (s_tc[k] == c) sc += p[k];
+                }
+                own_l = (double)lc[r0 + g];
+            } else {
+                float mx;
+                const float inv = row_softmax_norm(p, cols, mx);
+                c = 0;
+                sc = row_softmax_prob(p[0], mx, inv);
+                for (int k = 1; k < cols; ++k) {
+                    const float v = row_softmax_prob(p[k], mx, inv);
+                    if (v > sc) { sc = v; c = k; }
+                }
+            }
+            if (use_thresh && (double)sc < thresh) c = 0;
+            cls_out[r0 + g] = c;
+            score_out[r0 + g] = sc;
+        }
+        sum_t own;
+        if constexpr (TAGS) own = __double2ll_rn((double)sc * DEC_FIX);
+        else own = (double)sc;
+        sum_t incl = own;
+        double incl_l = own_l;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const sum_t up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+            if constexpr (TAGS) {
+                const double up_l = __shfl_up(incl_l, o, 64);
+                if (lane >= o) incl_l += up_l;
+            }
+        }
+        s_cls[t] = c;
+        if (lane == 63) { s_wtot[w] = incl; s_wtot_l[w] = incl_l; }
+        __syncthreads();                                                            // 1: classes and wave totals of the chunk
+        sum_t pb = total + (incl - own), chunk_total = 0;
+        double pl = total_l + incl_l, chunk_total_l = 0.0;
+#pragma unroll
+        for (int k = 0; k < DEC_WAVES; ++k) {
+            const sum_t wt = s_wtot[k];
+            const double wl = s_wtot_l[k];
+            if (k < w) { pb += wt; pl += wl; }
+            chunk_total += wt;
+            chunk_total_l += wl;
+        }
+        const int left = t > 0 ? s_cls[t - 1] : prev_last;
+        const bool head = valid && (c != left || begin);
+        if (base + DEC_THREADS >= n) last_cls = s_cls[n - 1 - base];
+        const int chunk_last = s_cls[DEC_THREADS - 1];
+        s_pb[t] = pb;
+        s_pl[t] = pl;
+        const unsigned long long hm = __ballot(head);
+        if (lane == 0) s_whead[w] = hm ? base + w * 64 + highest_bit(hm) : -1;
+        __syncthreads();                                                            // 2: prefix sums and wave heads
+        if (head && g > 0) {                                // a head closes the run in front of it: that run's record, at its first row
+            const unsigned long long lower = hm & ((1ull << lane) - 1ull);
+            int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
+            for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
+            sum_t ppb;
+            double ppl;
+            if (ph >= 0) { ppb = s_pb[ph - base]; ppl = s_pl[ph - base]; }
+            else { ph = open_head; ppb = open_pb; ppl = open_pl; }
+            vbg_run_rec r;
+            r.start = ph;
+            r.len = g - ph;
+            r.cls = left;
+            r.pad = 0;
+            r.mean = run_mean(pb - ppb, r.len);
+            r.logp = 0.0;
+            if constexpr (TAGS) r.logp = (double)lm[r0 + ph] + ((pl - own_l) - ppl);
+            runs[r0 + ph] = r;
+        } else if (valid && !head) {
+            vbg_run_rec r;
+            r.start = 0; r.len = 0; r.cls = 0; r.pad = 0; r.mean = 0.0; r.logp = 0.0;
+            runs[r0 + g] = r;
+        }
+        int lh = -1;
+        for (int k = DEC_WAVES - 1; k >= 0 && lh < 0; --k) lh = s_whead[k];
+        if (lh >= 0) { open_head = lh; open_pb = s_pb[lh - base]; open_pl = s_pl[lh - base]; }
+        total += chunk_total;
+        total_l += chunk_total_l;
+        prev_last = chunk_last;
+        __syncthreads();                                                            // 3: the chunk's tables are free again
+    }
+    if (n > 0 && t == 0) {                                  // the last run
+        vbg_run_rec r;
+        r.start = open_head;
+        r.len = n - open_head;
+        r.cls = last_cls;
+        r.pad = 0;
+        r.mean = run_mean(total - open_pb, r.len);
+        r.logp = 0.0;
+        if constexpr (TAGS) r.logp = (double)lm[r0 + open_head] + (total_l - open_pl);
+        runs[r0 + open_head] = r;
+    }
+}
+
 }  // namespace vbg
 
 using namespace vbg;
@@ -235,6 +384,48 @@ extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, 
                                 float* score, vbg_decode_rec* best, void* stream) {
     VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
     return decode_launch<false>(x, nullptr, h_doc_off, ndoc, dec_tags{}, C, C, use_thresh, thresh, cls, score, best, stream);
+}
+
+// the listing entries' share: decode_launch's checks of the row ranges, and the launches
+template <bool TAGS>
+static int runs_launch(const float* x, const int* path, const float* lm, const float* lc, const int* h_doc_off, int ndoc,
+                       const dec_tags& tags, int cols, int use_thresh, double thresh, int* cls, float* score, vbg_run_rec* runs,
+                       void* stream) {
+    VBG_CHECK_ARG(h_doc_off[0] >= 0);
+    for (int d = 0; d < ndoc; ++d) {
+        const long long nd = (long long)h_doc_off[d + 1] - h_doc_off[d];
+        VBG_CHECK_ARG(nd >= 0 && nd < (1ll << DEC_ROW_BITS));
+    }
+    if (ndoc == 0 || h_doc_off[ndoc] == h_doc_off[0]) return VBG_OK;
+    VBG_CHECK_ARG(x && cls && score && runs && (!TAGS || (path && lm && lc)));
+    for (int d0 = 0; d0 < ndoc; d0 += DEC_DOCS) {
+        const int nd = ndoc - d0 < DEC_DOCS ? ndoc - d0 : DEC_DOCS;
+        dec_docs docs;
+        for (int i = 0; i <= nd; ++i) docs.off[i] = h_doc_off[d0 + i];
+        for (int i = nd + 1; i <= DEC_DOCS; ++i) docs.off[i] = docs.off[nd];
+        VBG_LAUNCH(field_runs_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, lm, lc, docs, tags, cols,
+                   use_thresh, thresh, cls, score, runs);
+    }
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_field_runs(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
+                              float* score, vbg_run_rec* runs, void* stream) {
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
+    return runs_launch<false>(x, nullptr, nullptr, nullptr, h_doc_off, ndoc, dec_tags{}, C, use_thresh, thresh, cls, score, runs, stream);
+}
+
+extern "C" int vbg_field_runs_tags(const float* marginals, const int* path, const float* lm, const float* lc, const int* h_doc_off,
+                                   int ndoc, int ntag, int C, const int* h_tag_class, const int* h_tag_begin, int use_thresh,
+                                   double thresh, int* cls, float* score, vbg_run_rec* runs, void* stream) {
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C && ntag >= 1 && ntag <= DEC_MAX_C && h_tag_class && h_tag_begin);
+    dec_tags tags = {};
+    for (int k = 0; k < ntag; ++k) {
+        VBG_CHECK_ARG(h_tag_class[k] >= 0 && h_tag_class[k] < C && (h_tag_begin[k] == 0 || h_tag_begin[k] == 1));
+        tags.cls[k] = (unsigned char)h_tag_class[k];
+        tags.begin[k] = (unsigned char)h_tag_begin[k];
+    }
+    return runs_launch<true>(marginals, path, lm, lc, h_doc_off, ndoc, tags, ntag, use_thresh, thresh, cls, score, runs, stream);
 }
 
 extern "C" int vbg_field_decode_tags(const float* marginals, const int* path, const int* h_doc_off, int ndoc, int ntag, int C,

@@ -302,6 +302,11 @@ class ViBERTgridNet(nn.Module):
         row ranges are the box table's offsets, already on the device."""
         if self.classifier_mode != "crf":
             raise ValueError(f"inference_posterior needs classifier_mode 'crf', this model has {self.classifier_mode!r}")
+        em, doc_off, _ = self._crf_emissions(image, seg_indices, coors, corpus, mask)
+        return self.field_type_classification_head.crf_layer.posterior(em, doc_off)
+
+    def _crf_emissions(self, image, seg_indices, coors, corpus, mask):
+        """the crf mode's prediction trunk -> (emissions [N, ntag], device row ranges of the call's documents, segments per document)"""
         ops.set_amp(torch.is_autocast_enabled("cuda"))
         ops.latch_deterministic()
         self.BERTgrid_generator.prefetch_host(corpus, mask, seg_indices)
@@ -315,8 +320,33 @@ class ViBERTgridNet(nn.Module):
         fuse = self.late_fusion_net(roi, emb_cat)
         head = self.field_type_classification_head
         em = head.category_classification_net(fuse.reshape((-1, head.fuse_embedding_channel))).detach()
-        doc_off = packed[1] if packed is not None else head._doc_off([0 if c is None else c.shape[0] for c in icoors], em.device)
-        return head.crf_layer.posterior(em, doc_off)
+        lens = [0 if c is None else int(c.shape[0]) for c in icoors]
+        doc_off = packed[1] if packed is not None else head._doc_off(lens, em.device)
+        return em, doc_off, lens
+
+    def inference_entities(self, image: Tuple[torch.Tensor], seg_indices: Tuple[torch.Tensor], coors: torch.Tensor,
+                           corpus: torch.Tensor, mask: torch.Tensor, thresh=None, table=None):
+        """EVERY decoded field of every document of the call -> vbg.decode.FieldRuns (`runs[d]`: document d's runs in row order; strings:
+        vbg.decode.entity_strings).  classifier_mode "crf": the trunk, then the posterior, the log posteriors of the Viterbi path
+        and the listing -- three launches behind the emissions, one device-to-host copy -- each run with `logp` = log P(its tags | x);
+        `table` (vbg.decode.tag_table(tag_to_idx, category_list)) is required.  "simp" / "full": `inference()`, then list_fields over
+        its scores.  The host row ranges are the segment counts of `coors`."""
+        from vbg import decode as D
+        if self.classifier_mode == "crf":
+            if table is None:
+                raise ValueError("inference_entities needs table=vbg.decode.tag_table(tag_to_idx, category_list) with classifier_mode 'crf'")
+            em, doc_off, lens = self._crf_emissions(image, seg_indices, coors, corpus, mask)
+            crf = self.field_type_classification_head.crf_layer
+            post = crf.posterior(em, doc_off)
+            logp = crf.path_logp(em, doc_off, post.path)
+            off = [0]
+            for n in lens:
+                off.append(off[-1] + n)
+            return D.list_crf_fields(post, logp, table, max(table.tag_class) + 1, thresh=thresh, doc_off=off)
+        off = [0]
+        for c in coors:
+            off.append(off[-1] + (0 if c is None else int(c.shape[0])))
+        return D.list_fields(self.inference(image, seg_indices, coors, corpus, mask), thresh=thresh, doc_off=off)
 
     def forward(self, image: Tuple[torch.Tensor], seg_indices: Tuple[torch.Tensor], segment_classes: Tuple[torch.Tensor],
                 coors: torch.Tensor, corpus: torch.Tensor, mask: torch.Tensor):

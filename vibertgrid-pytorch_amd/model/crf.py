@@ -5,7 +5,8 @@ per-document API (`forward(feats, tags)` -> (log Z - gold score) / len, `inferen
 `decode` take all documents of a batch at once (row ranges `doc_off`), one launch each: forward algorithm + gold score,
 backward = (marginals - gold indicators), Viterbi with first-maximum tie breaking like `torch.max`.  `posterior` adds what the
 reference's prediction path lacks: the same Viterbi path and score together with log Z and the posterior marginals
-p(y_t = i | x) of every row, from one launch (vbg_crf_posterior).  With ops.set_crf_stable(True) / VBG_CRF_STABLE=1 `nll` -- and so
+p(y_t = i | x) of every row, from one launch (vbg_crf_posterior); `path_logp` the row-by-row log posteriors of a given path, from
+which the confidence of any span of it is a sum (vbg_crf_path_logp).  With ops.set_crf_stable(True) / VBG_CRF_STABLE=1 `nll` -- and so
 `forward(feats, tags)` -- takes Fn.CrfNllStableFn: the same loss with a gradient whose error does not grow with the document's length.
 """
 from collections import namedtuple
@@ -51,6 +52,12 @@ class CRF(nn.Module):
         """`decode`'s path and score, bit for bit, with log Z per document and the marginals of every row: one launch"""
         s, e = self._ends()
         return CrfPosterior(*ops.crf_posterior(feats.detach().contiguous(), doc_off, self.transitions.detach().contiguous(), s, e))
+
+    def path_logp(self, feats: torch.Tensor, doc_off: torch.Tensor, path: torch.Tensor):
+        """-> (lm [N], lc [N]): the log marginal of path[t] and its log conditional given path[t-1], row by row (lc of a document's
+        first row is its lm): lm[s] + lc[s+1 .. e].sum() = log P(y_s .. y_e = path[s .. e] | x).  path: int32 [N], any tags.  One launch"""
+        s, e = self._ends()
+        return ops.crf_path_logp(feats.detach().contiguous(), doc_off, self.transitions.detach().contiguous(), s, e, path)
 
     def forward(self, feats, tags):
         off = torch.tensor([0, feats.shape[0]], dtype=torch.int32).to(feats.device)

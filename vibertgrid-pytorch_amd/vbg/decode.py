@@ -19,7 +19,14 @@ CRF (ViBERTgridNet.inference_posterior / CRF.posterior: Viterbi path + marginals
 A segment's class is the class of its Viterbi tag, its score the posterior of that CLASS (the sum of the marginals of the class's
 tags); runs also break in front of a begin tag, means are exact (fixed-point sums), every run is filed under its own class -- the
 last-run quirk of the score loop is not carried over -- and a run whose scores all round to 0 leaves no record (decode_tags ->
-vbg_field_decode_tags, include/vbg.h).  Two launches and one device-to-host copy per document or batch."""
+vbg_field_decode_tags, include/vbg.h).  Two launches and one device-to-host copy per document or batch.
+
+Both tables keep ONE run per class: the SROIE / EPHOIE protocol, where a key occurs once per receipt.  A page with dozens of
+question / answer / header entities needs every run -- list_fields / list_crf_fields (vbg_field_runs / vbg_field_runs_tags), and in
+the crf mode each with the probability that its tags hold jointly, P(y_s .. y_e = the decoded tags | x), from CRF.path_logp:
+
+    runs = net.inference_entities(image, seg_indices, coors, corpus, mask, table=tag_table(tag_to_idx, category_list))
+    for cls, text, mean, prob in entity_strings(runs.runs[0], ocr_text[0]): ..."""
 from collections import namedtuple
 
 import numpy as np
@@ -153,3 +160,65 @@ def crf_field_strings(posterior, table, num_classes, ocr_text, thresh=None, join
     if len(texts) != marginals.shape[0]:
         raise ValueError(f"{len(texts)} segment texts for {marginals.shape[0]} rows")
     return join_winners(decode_tags(posterior, table, num_classes, thresh).best[0], texts, join)
+
+
+# ---- every run, not the winners: pages with many fields per class (FUNSD-style question / answer / header)
+# one record of the listing: first segment of the run (relative to its document), its length, its class, its mean score and, in the
+# crf mode, the log posterior of its tags holding jointly (the score modes have none: NaN in list_fields' records)
+RUN = np.dtype([("start", "<i4"), ("len", "<i4"), ("cls", "<i4"), ("pad", "<i4"), ("mean", "<f8"), ("logp", "<f8")])
+
+# cls int32 [N], score fp32 [N]: device tensors; runs: one RUN array per document, its runs in row order (host); doc_off: host row ranges
+FieldRuns = namedtuple("FieldRuns", ["cls", "score", "runs", "doc_off"])
+
+
+def _split_runs(runs, off, has_logp):
+    rec = runs.cpu().numpy().view(RUN).reshape(-1)                          # the one device-to-host copy
+    if not has_logp:
+        rec["logp"] = np.nan                                                # (the kernel writes 0.0: log 1, which no score claims)
+    out = []
+    for lo, hi in zip(off[:-1], off[1:]):
+        doc = rec[lo:hi]
+        out.append(doc[doc["len"] > 0])
+    return out
+
+
+def list_fields(pred_label, thresh=None, doc_off=None):
+    """decode_fields' classes, scores and runs with EVERY run listed -> FieldRuns (`logp` is NaN: class scores carry no joint
+    probability).  Every run stands under its own class, the last one included.  One launch, one device-to-host copy."""
+    _check_pred_label(pred_label)
+    n = pred_label.shape[0]
+    off = [0, n] if doc_off is None else [int(v) for v in doc_off]
+    cls, score, runs = ops.field_runs(pred_label, off, thresh)
+    return FieldRuns(cls, score, _split_runs(runs, off, False), off)
+
+
+def list_crf_fields(posterior, path_logp, table, num_classes, thresh=None, doc_off=None):
+    """posterior: a CrfPosterior or (marginals, path); path_logp: the (lm, lc) pair of CRF.path_logp for that path; table: tag_table's
+    -> FieldRuns: decode_tags' classes, scores and runs with EVERY run listed, `logp` = log P(the run's tags | x) -- the constrained
+    forward-backward confidence of the field.  One launch, one device-to-host copy."""
+    marginals, path = _posterior_parts(posterior)
+    lm, lc = path_logp
+    n = marginals.shape[0]
+    for name, v in (("lm", lm), ("lc", lc)):
+        if not (torch.is_tensor(v) and v.dtype == torch.float32 and tuple(v.shape) == (n,) and v.is_cuda):
+            raise TypeError(f"{name} must be a float32 device tensor of {n} values (CRF.path_logp's)")
+    off = [0, n] if doc_off is None else [int(v) for v in doc_off]
+    cls, score, runs = ops.field_runs_tags(marginals, path, lm, lc, table.tag_class, table.tag_begin, num_classes, off, thresh)
+    return FieldRuns(cls, score, _split_runs(runs, off, True), off)
+
+
+def entity_strings(doc_runs, texts, join="space_before", keep_background=False):
+    """one document's RUN array + its segment texts -> [(cls, text, mean, prob)] in row order, prob = exp(logp), None where logp is
+    NaN (the runs of list_fields; a crf document whose lm / lc held NaN); class-0 runs are left out unless keep_background."""
+    if join not in JOIN:
+        raise ValueError(f"join must be one of {sorted(JOIN)}, got {join!r}")
+    rule = JOIN[join]
+    out = []
+    for r in doc_runs:
+        c, s, ln = int(r["cls"]), int(r["start"]), int(r["len"])
+        if c == 0 and not keep_background:
+            continue
+        if s < 0 or s + ln > len(texts):
+            raise ValueError(f"run {s} .. {s + ln} does not fit {len(texts)} segment texts")
+        out.append((c, rule(texts[s:s + ln]), float(r["mean"]), None if np.isnan(r["logp"]) else float(np.exp(r["logp"]))))
+    return out

@@ -290,6 +290,10 @@ SIGNATURES = {
     "vbg_crf_nll_stable_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "vbg_field_decode_tags": (c_int, [c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int, c_d,
                                       c_vp, c_vp, c_vp, c_vp]),
+    "vbg_crf_path_logp": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_field_runs": (c_int, [c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_d, c_vp, c_vp, c_vp, c_vp]),
+    "vbg_field_runs_tags": (c_int, [c_vp, c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int),
+                                    c_int, c_d, c_vp, c_vp, c_vp, c_vp]),
     "vbg_seq_metrics": (c_int, [c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, TagTable, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),

@@ -2788,7 +2788,33 @@ def crf_posterior(em, doc_off, trans, start, stop):
     return path, score, logz, marg
 
 
-_CRF_STABLE = [os.environ.get("VBG_CRF_STABLE", "0") not in ("", "0")]
+def crf_path_logp(em, doc_off, trans, start, stop, path):
+    """-> (lm [N], lc [N]) in ONE launch (vbg_crf_path_logp, include/vbg.h): lm[t] = log p(y_t = path[t] | x), lc[t] =
+    log p(y_t = path[t] | y_{t-1} = path[t-1], x), lc of a document's first row its lm -- lm[s] + lc[s+1 .. e].sum() is the log posterior
+    of the span s .. e holding the path's tags.  path: int32 [N], any tags (crf_posterior's, gold, an alternative).  No atomics: the
+    deterministic mode takes the same route."""
+    _chk_f32(em)
+    _chk_f32(trans)
+    N, ntag = em.shape
+    ndoc = doc_off.numel() - 1
+    if tuple(trans.shape) != (ntag, ntag) or doc_off.dtype != i32:
+        raise VbgError(f"vbg_crf_path_logp: trans {tuple(trans.shape)} / doc_off {doc_off.dtype} do not fit emissions [{N}, {ntag}]")
+    if not torch.is_tensor(path) or path.dtype != i32 or tuple(path.shape) != (N,) or path.device != em.device:
+        what = (path.dtype, tuple(path.shape), path.device) if torch.is_tensor(path) else type(path)
+        raise VbgError(f"vbg_crf_path_logp: path must be int32 [{N}] on {em.device}, got {what}")
+    ws = torch.empty((max(N, 1), ntag), device=em.device, dtype=f32)
+    lm = torch.empty((max(N, 1),), device=em.device, dtype=f32)
+    lc = torch.empty((max(N, 1),), device=em.device, dtype=f32)
+    if N == 0:                                              # no row to touch: the checks alone (the entry wants buffers with ndoc > 0)
+        check(lib.vbg_crf_path_logp(None, P(doc_off), 0, P(trans.contiguous()), ntag, start, stop, None, None, None, None, _stream()),
+              "vbg_crf_path_logp")
+        return lm[:0], lc[:0]
+    check(lib.vbg_crf_path_logp(P(em.contiguous()), P(doc_off), ndoc, P(trans.contiguous()), ntag, start, stop, P(path.contiguous()),
+                                P(ws), P(lm), P(lc), _stream()), "vbg_crf_path_logp")
+    return lm, lc
+
+
+_CRF_STABLE =[os.environ.get("VBG_CRF_STABLE", "0") not in ("", "0")]
 
 
 def set_crf_stable(on: bool):
@@ -2871,6 +2897,54 @@ def field_decode_tags(marginals, path, tag_class, tag_begin, num_classes, doc_of
                                     int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(best),
                                     _stream()), "vbg_field_decode_tags")
     return cls, score, best
+
+
+def field_runs(x, doc_off=None, thresh=None):
+    """x [N, C] fp32 class scores (device) -> (cls int32 [N], score fp32 [N], runs float64 [N, 4]) in ONE launch (vbg_field_runs,
+    include/vbg.h): field_decode's rows and runs, EVERY run listed.  A row of `runs` is one 32-byte vbg_run_rec (int32 start, len, cls,
+    pad; float64 mean, logp) carried as four doubles: vbg.decode views it after its one copy to the host.  doc_off, thresh: as in
+    field_decode."""
+    _chk_f32(x)
+    N, ncls = x.shape
+    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
+    ndoc = len(off) - 1
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"vbg_field_runs: doc_off {off[:4]}... does not fit {N} rows")
+    cls = torch.empty(N, dtype=i32, device=x.device)
+    score = torch.empty(N, dtype=f32, device=x.device)
+    runs = torch.empty(N, 4, dtype=torch.float64, device=x.device)
+    check(lib.vbg_field_runs(P(x.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, int(thresh is not None),
+                             0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs")
+    return cls, score, runs
+
+
+def field_runs_tags(marginals, path, lm, lc, tag_class, tag_begin, num_classes, doc_off=None, thresh=None):
+    """marginals [N, ntag] fp32 and path [N] int32 (crf_posterior's), lm / lc [N] fp32 (crf_path_logp's for that path) -> (cls, score,
+    runs) as field_runs gives them, in ONE launch (vbg_field_runs_tags, include/vbg.h): field_decode_tags' rows and runs, EVERY run
+    listed, with logp = lm[s] + the fp64 sum of lc over the run's other rows."""
+    _chk_f32(marginals)
+    _chk_f32(lm)
+    _chk_f32(lc)
+    N, ntag = marginals.shape
+    if path.dtype != i32 or tuple(path.shape) != (N,) or path.device != marginals.device:
+        raise VbgError(f"vbg_field_runs_tags: path must be int32 [{N}] on {marginals.device}, got {path.dtype} {tuple(path.shape)}")
+    if tuple(lm.shape) != (N,) or tuple(lc.shape) != (N,) or lm.device != marginals.device or lc.device != marginals.device:
+        raise VbgError(f"vbg_field_runs_tags: lm {tuple(lm.shape)} / lc {tuple(lc.shape)} must be fp32 [{N}] on {marginals.device}")
+    if len(tag_class) != ntag or len(tag_begin) != ntag:
+        raise VbgError(f"vbg_field_runs_tags: {len(tag_class)} / {len(tag_begin)} table entries for {ntag} tags")
+    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
+    ndoc = len(off) - 1
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"vbg_field_runs_tags: doc_off {off[:4]}... does not fit {N} rows")
+    cls = torch.empty(N, dtype=i32, device=marginals.device)
+    score = torch.empty(N, dtype=f32, device=marginals.device)
+    runs = torch.empty(N, 4, dtype=torch.float64, device=marginals.device)
+    tc = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_class])
+    tb = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_begin])
+    check(lib.vbg_field_runs_tags(P(marginals.contiguous()), P(path.contiguous()), P(lm.contiguous()), P(lc.contiguous()),
+                                  (C.c_int * (ndoc + 1))(*off), ndoc, ntag, int(num_classes), tc, tb, int(thresh is not None),
+                                  0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs_tags")
+    return cls, score, runs
 
 
 def _sum_det(x, out, squares):

@@ -1,5 +1,5 @@
 """The element-wise, pooling / resampling, loss / selection, grid and optimizer kernels (csrc/convaux.hip, loss.hip, optim.hip,
-grid.hip, the row gather / scatter of crf.hip, row_softmax of rowops.hip) at the edges the one-small-shape tests of
+grid.hip, the row gather / scatter of loss.hip, row_softmax of rowops.hip) at the edges the one-small-shape tests of
 test_gpu_kernels.py do not reach: a second trip of the grid-stride loop, destinations that are accumulated into or written exactly
 once, tied maxima, dropped trailing rows, empty inputs.  References are plain torch on the CPU in fp64 (or the oracle); every
 tolerance is written where it is used.  Needs a real MI355X.

@@ -1,10 +1,13 @@
 // Linear-chain CRF of the `crf` classifier head (reference model/crf.py:33-157, called per document at
-// model/field_type_classification_head.py:690-716) and the row gather / scatter of the two-stage `full` classifier
-// (model/field_type_classification_head.py:371, 389-395: `fuse_embeddings[pred_pos_neg_mask]`).
+// model/field_type_classification_head.py:690-716).
 //
-// CRF: one 64-thread block per document, lane i owns tag i (ntag <= 64).  The recursions are sequential in the segment
+// One 64-thread block per document, lane i owns tag i (ntag <= 64).  The recursions are sequential in the segment
 // index (S <= a few hundred), each step is ntag x ntag flops: latency-bound by design, the point is to stay on the device
 // and to batch all documents of the rank into one launch.  trans[i*ntag + j] = score of the transition j -> i.
+//
+// The file in order: crf_nll_fwd / crf_nll_bwd / crf_viterbi, the default training and decode route in the reference's arithmetic; the
+// wave kernels crf_posterior and crf_path_logp behind the description and the functions they share; the length-stable loss crf_nll_stable
+// with its scaling launch; the entries, behind their one tag-range check and one ntag dispatch.
 #include "vbg_common.h"
 #include "../../include/vbg.h"
 
@@ -156,24 +159,23 @@ __global__ __launch_bounds__(64) void crf_viterbi_kernel(const float* __restrict
     }
 }
 
-// Posterior marginals + Viterbi + log Z in one launch (vbg_crf_posterior): one wave per document, lane i owns tag i.
-//
-// The grid is a handful of waves and the time is the serial chain, rows x work per step, so the kernel is shaped by what sits on it:
+// ---- the wave kernels (vbg_crf_posterior, vbg_crf_path_logp): one wave per document, lane i owns tag i -------------------------------
+// The grid is a handful of waves and the time is the serial chain, rows x work per step, so both kernels are shaped by what sits on it.
+// What they share is described once, here.  As functions they share lse_slice, lse_join, the re-centring (crf_recentred) and the log Z
+// end; the lane geometry, the transition loads, the beta step's store and the tile rows stand in each kernel's own text, because
+// behind a helper the compiler orders them otherwise and the chains get 0.2 - 3.5 % longer (profiles/crf_decode_shared.txt).
 //   transitions  lane i keeps ITS row (forward, Viterbi) and later its column (backward) in registers: tw[], ntag rounded up to a
 //                template size NTP, the tail filled with -inf (a term that never wins a maximum and adds exp(-inf) == 0 to a sum);
 //   vectors      the previous step's vector lies in LDS (two buffers, one barrier per step) and the lanes read it at the same
 //                addresses -- a broadcast, no bank conflict -- four values to a read;
-//   lanes        up to 32 tags, two lanes share a tag: each walks half of the previous tags, and one exchange across the halves per
-//                step joins the two partial sums (and the two Viterbi candidates, the lower half winning ties: the first maximum);
-//   emissions    loaded one step ahead, as are the forward vector and the back pointers in the backward pass;
-//   back trace   walked inside the backward pass, from the row of back pointers that pass has already fetched: no chain of
-//                dependent global loads behind the recursions.
+//   lanes        up to 32 tags, two lanes share a tag (HALF): lane l and lane l + 32 own tag l, each walks half of the previous tags,
+//                and one exchange across the halves per step joins the two partial sums -- half the instructions on the chain;
+//   loads        emissions arrive one step ahead, as does the forward vector in the backward pass.
 // Forward and backward run in log space and are re-centred at every step: the maximum of the previous vector -- which the lanes
-// have in hand from the broadcast read, so no reduction over the tags -- is taken out of the step's result, and the forward pass
-// carries these maxima into log Z in double.  The magnitudes stay at (emission + transition + log ntag) whatever the length.
+// have in hand from the broadcast read, so no reduction over the tags -- is taken out of the step's result.  The magnitudes stay at
+// (emission + transition + log ntag) whatever the length.
 // Position t's marginals are exp(a_t + b_t - max) / sum: 64 rows of a_t + b_t are gathered in an LDS tile (odd row stride), then one
-// lane per row takes maximum and sum in tag order and the tile goes out in whole rows.
-// The Viterbi chain repeats crf_viterbi_kernel's arithmetic on the unnormalised values: prev[j] + tr[i][j], first maximum, + em.
+// lane per row takes maximum and sum in tag order (expf / logf: off the chain).
 constexpr int CRF_TILE_ROWS = 64;
 constexpr int CRF_TILE_STRIDE = CRF_MAX_TAGS + 1;
 
@@ -198,8 +200,7 @@ __device__ __forceinline__ void lse_slice(const float* __restrict__ v, const flo
     for (int j = 0; j < JW; ++j) s += __expf(pr[j] - m2);
 }
 
-// HALF: two lanes per tag (ntag <= 32).  Lane l and lane l + 32 own tag l; each walks one half of the previous tags and the two
-// exchange their partial results once per step and chain (one cross-half shuffle each way) -- half the instructions on the chain.
+// HALF: the two lanes of a tag exchange their partial results (one cross-half shuffle each way)
 template <bool HALF>
 __device__ __forceinline__ void lse_join(float& mx_v, float& m2, float& s) {
     if (HALF) {
@@ -211,6 +212,28 @@ __device__ __forceinline__ void lse_join(float& mx_v, float& m2, float& s) {
     }
 }
 
+// the re-centring, stated once: the log of a step's sum (m2, s) less mx, the maximum of the vector the step read.  Forward:
+// a_t[i] = em + crf_recentred(lse of prev[j] + tr[i][j]); backward: b_{t-1}[i] = crf_recentred(lse of tr[k][i] + em_t[k] + b_t[k]).
+__device__ __forceinline__ float crf_recentred(float mx, float m2, float s) { return (m2 - mx) + __logf(s); }
+
+// log Z from the last forward vector pa, the transitions to STOP ps and the sum of the maxima taken out (the same value in every lane)
+__device__ __forceinline__ double crf_log_z_end(const float* pa, const float* ps, int ntag, double carry) {
+    float mx = pa[0];
+    for (int j = 1; j < ntag; ++j) mx = fmaxf(mx, pa[j]);
+    float m2 = (pa[0] - mx) + ps[0];
+    for (int j = 1; j < ntag; ++j) m2 = fmaxf(m2, (pa[j] - mx) + ps[j]);
+    float s = 0.f;
+    for (int j = 0; j < ntag; ++j) s += expf((pa[j] - mx) + ps[j] - m2);
+    return carry + (double)mx + (double)(m2 + logf(s));
+}
+
+// Posterior marginals + Viterbi + log Z in one launch (vbg_crf_posterior).  On top of the shared shape:
+//   log Z        the forward pass carries the maxima it takes out into log Z in double;
+//   Viterbi      the chain repeats crf_viterbi_kernel's arithmetic on the unnormalised values: prev[j] + tr[i][j], first maximum, + em;
+//                of the two candidates of a tag's two lanes the lower half wins ties: the first maximum;
+//   back trace   walked inside the backward pass, from the row of back pointers that pass has already fetched (a step ahead, like
+//                the forward vector): no chain of dependent global loads behind the recursions;
+//   marginals    the lane of a tile row divides it by its sum, and the tile goes out in whole rows.
 template <int NTP, bool HALF>
 __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restrict__ em, const int* __restrict__ doc_off,
                                                            const float* __restrict__ trans, int ntag, int start, int stop,
@@ -245,7 +268,6 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
     for (int t = 0; t < n; ++t) {
         const float e = e_next;
         if (t + 1 < n) e_next = em[(long long)(r0 + t + 1) * ntag + ic];
-        // forward: a_t[i] = em + log sum_j exp(prev[j] + tr[i][j]) - max(prev)
         float mx, m2, s;
         lse_slice<JW>(s_a[t & 1] + j0, tw, mx, m2, s);
         // Viterbi: crf_viterbi_kernel's additions in its order, the first maximum of the lane's slice
@@ -284,7 +306,7 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
             best = bhi > blo ? bhi : blo;
             bj = bhi > blo ? jhi : jlo;
         }
-        const float a = e + ((m2 - mx) + __logf(s));
+        const float a = e + crf_recentred(mx, m2, s);
         carry += (double)mx;
         best += e;
         const int nb = (t + 1) & 1;
@@ -300,15 +322,8 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
     // ---- the end of both chains: every lane forms the same two values, lane 0 writes them
     int cur = 0;
     {
-        const float* pa = s_a[n & 1];
         const float* pv = s_v[n & 1];
-        float mx = pa[0];
-        for (int j = 1; j < ntag; ++j) mx = fmaxf(mx, pa[j]);
-        float m2 = (pa[0] - mx) + s_stop[0];
-        for (int j = 1; j < ntag; ++j) m2 = fmaxf(m2, (pa[j] - mx) + s_stop[j]);
-        float s = 0.f;
-        for (int j = 0; j < ntag; ++j) s += expf((pa[j] - mx) + s_stop[j] - m2);
-        const float z = (float)(carry + (double)mx + (double)(m2 + logf(s)));
+        const float z = (float)crf_log_z_end(s_a[n & 1], s_stop, ntag, carry);
         float best = pv[0] + s_stop[0];
         for (int j = 1; j < ntag; ++j) {
             const float v = pv[j] + s_stop[j];
@@ -372,15 +387,13 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
             float mx, m2, s;
             lse_slice<JW>(nbuf + j0, tw, mx, m2, s);
             lse_join<HALF>(mx, m2, s);
-            b = (m2 - mx) + __logf(s);
+            b = crf_recentred(mx, m2, s);
         }
     }
 }
 
-// Log posteriors of a GIVEN tag path (vbg_crf_path_logp): one wave per document, lane i owns tag i, crf_posterior_kernel's shape
-// without its Viterbi chain and its marginal rows -- transitions in registers, the previous vector broadcast from LDS, both
-// recursions in log space and re-centred at every step, loads one step ahead.  The re-centred backward vector gives the chain's
-// conditionals directly:
+// Log posteriors of a GIVEN tag path (vbg_crf_path_logp): the shared shape without a Viterbi chain and without marginal rows.  The
+// re-centred backward vector gives the chain's conditionals directly:
 //     log p(y_t = i | y_{t-1} = j, x) = tr[i][j] + (em_t[i] + b_t[i] - max_k(em_t[k] + b_t[k])) - b_{t-1}[j],
 // b_{t-1}[j] = log sum_i exp(tr[i][j] + em_t[i] + b_t[i]) - the same maximum: the step that forms b_{t-1} has all three terms in
 // hand.  The two it needs per row are picked without a data-dependent address that could leave the tables: em_t + b_t from the LDS
@@ -388,9 +401,8 @@ __global__ __launch_bounds__(64) void crf_posterior_kernel(const float* __restri
 // registers, 64 positions to a load and a tile ahead, and a step takes its two with v_readlane -- a load per step whose address is the
 // same in every lane becomes a scalar load, which returns out of order and makes every LDS wait of the step wait for it as well.  The
 // step leaves its part of the conditional in the lane of its tile row (a select); the transition is added where the rows go out.
-// log Z never enters and the forward pass carries no sum of maxima.  The marginal of the path's tag is taken from a_t + b_t as
-// crf_posterior_kernel takes its rows: 64 rows wait in an LDS tile (odd row stride), one lane per row forms maximum and sum in tag
-// order (expf / logf: off the chain) and writes the row's lm and lc.
+// log Z never enters and the forward pass carries no sum of maxima.  The marginal of the path's tag is taken from the tile rows of
+// a_t + b_t: the lane of a row picks the path's tag and writes the row's lm and lc.
 template <int NTP, bool HALF>
 __global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restrict__ em, const int* __restrict__ doc_off,
                                                            const float* __restrict__ trans, int ntag, int start, int stop,
@@ -417,7 +429,7 @@ __global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restri
     s_a[1][lane] = NEG;
     __syncthreads();
 
-    // ---- forward, t = 0 .. n - 1: a_t[i] = em + log sum_j exp(prev[j] + tr[i][j]) - max(prev), crf_posterior_kernel's statement
+    // ---- forward, t = 0 .. n - 1: a_t[i] = em + log sum_j exp(prev[j] + tr[i][j]) - max(prev)
     float e_next = em[(long long)r0 * ntag + ic];
     for (int t = 0; t < n; ++t) {
         const float e = e_next;
@@ -425,7 +437,7 @@ __global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restri
         float mx, m2, s;
         lse_slice<JW>(s_a[t & 1] + j0, tw, mx, m2, s);
         lse_join<HALF>(mx, m2, s);
-        const float a = e + ((m2 - mx) + __logf(s));
+        const float a = e + crf_recentred(mx, m2, s);
         s_a[(t + 1) & 1][lane] = own ? a : NEG;
         if (own) ws[(long long)(r0 + t) * ntag + lane] = a;
         __syncthreads();
@@ -466,8 +478,7 @@ __global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restri
         }
         if (own) s_tile[slot * CRF_TILE_STRIDE + lane] = a + b;
         if (t > 0) {
-            // beta of position t - 1: b[i] = log sum_k exp(tr[k][i] + em_t[k] + b_t[k]) - max(em_t + b_t), and what row t's
-            // conditional takes from the two vectors
+            // beta of position t - 1, and what row t's conditional takes from the two vectors
             const int yt = __builtin_amdgcn_readlane(yc, slot), yp = __builtin_amdgcn_readlane(qc, slot);
             float* nbuf = s_a[t & 1];
             nbuf[lane] = own ? e + b : NEG;
@@ -476,7 +487,7 @@ __global__ __launch_bounds__(64) void crf_path_logp_kernel(const float* __restri
             lse_slice<JW>(nbuf + j0, tw, mx, m2, s);
             lse_join<HALF>(mx, m2, s);
             const float nby = nbuf[yt];
-            b = (m2 - mx) + __logf(s);
+            b = crf_recentred(mx, m2, s);
             const float bp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b), yp));     // (the builtin moves 32 bits as an integer)
             if (lane == slot) part = (nby - mx) - bp;
         }
@@ -526,6 +537,19 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// log-sum-exp over n terms v[k] + w[k * step] of two LDS vectors, as (max, sum of exp(. - max)), with the maximum of v alone on the
+// side: the forward step (w the lane's row of the transitions, step 1) and the beta step (its column, step CRF_ST_STRIDE)
+__device__ __forceinline__ void lse_lds(const float* v, const float* w, int step, int n, float& mx, float& m2, float& s) {
+    mx = v[0];
+    m2 = v[0] + w[0];
+    for (int k = 1; k < n; ++k) {
+        mx = fmaxf(mx, v[k]);
+        m2 = fmaxf(m2, v[k] + w[k * step]);
+    }
+    s = 0.f;
+    for (int k = 0; k < n; ++k) s += expf((v[k] + w[k * step]) - m2);
+}
+
 // one entry of the pairwise table before its maximum is taken out; the ONE statement of this sum (three passes use it)
 __device__ __forceinline__ float crf_pair_arg(float a_prev_j, float tr_ij, float nb_i) { return (a_prev_j + tr_ij) + nb_i; }
 
@@ -560,14 +584,8 @@ __global__ __launch_bounds__(64) void crf_nll_stable_kernel(const float* __restr
         const float e = e_next;
         if (t + 1 < n) e_next = em[(long long)(r0 + t + 1) * ntag + ic];
         const float emax = wave_max(own ? e : NEG);
-        const float* prev = s_a[t & 1];
-        float mx = prev[0], m2 = prev[0] + trow[0];
-        for (int j = 1; j < ntag; ++j) {
-            mx = fmaxf(mx, prev[j]);
-            m2 = fmaxf(m2, prev[j] + trow[j]);
-        }
-        float s = 0.f;
-        for (int j = 0; j < ntag; ++j) s += expf((prev[j] + trow[j]) - m2);
+        float mx, m2, s;
+        lse_lds(s_a[t & 1], trow, 1, ntag, mx, m2, s);
         const float a = (e - emax) + ((m2 - mx) + logf(s));
         carry += (double)mx + (double)emax;
         s_a[(t + 1) & 1][lane] = own ? a : NEG;
@@ -576,18 +594,7 @@ __global__ __launch_bounds__(64) void crf_nll_stable_kernel(const float* __restr
     }
 
     // ---- log Z (every lane forms the same value) and the gold score: lane l takes rows l, l + 64, ...; the sums are double
-    double zd;
-    {
-        const float* pa = s_a[n & 1];
-        const float* ps = s_tr + stop * CRF_ST_STRIDE;
-        float mx = pa[0];
-        for (int j = 1; j < ntag; ++j) mx = fmaxf(mx, pa[j]);
-        float m2 = (pa[0] - mx) + ps[0];
-        for (int j = 1; j < ntag; ++j) m2 = fmaxf(m2, (pa[j] - mx) + ps[j]);
-        float s = 0.f;
-        for (int j = 0; j < ntag; ++j) s += expf((pa[j] - mx) + ps[j] - m2);
-        zd = carry + (double)mx + (double)(m2 + logf(s));
-    }
+    const double zd = crf_log_z_end(s_a[n & 1], s_tr + stop * CRF_ST_STRIDE, ntag, carry);
     double gold = 0.0;
     for (int t = lane; t < n; t += 64) {
         const int ct = tags[r0 + t], pt = t > 0 ? tags[r0 + t - 1] : start;
@@ -657,14 +664,8 @@ __global__ __launch_bounds__(64) void crf_nll_stable_kernel(const float* __restr
         }
         if (t > 0) {
             // beta of position t - 1: b[j] = log sum_k exp(tr[k][j] + nb[k]) - max(nb), the lane's COLUMN of the transitions
-            const float* tcol = s_tr + ic;
-            float mx = s_nb[0], m2 = s_nb[0] + tcol[0];
-            for (int k = 1; k < ntag; ++k) {
-                mx = fmaxf(mx, s_nb[k]);
-                m2 = fmaxf(m2, s_nb[k] + tcol[k * CRF_ST_STRIDE]);
-            }
-            float s = 0.f;
-            for (int k = 0; k < ntag; ++k) s += expf((s_nb[k] + tcol[k * CRF_ST_STRIDE]) - m2);
+            float mx, m2, s;
+            lse_lds(s_nb, s_tr + ic, CRF_ST_STRIDE, ntag, mx, m2, s);
             b = (m2 - mx) + logf(s);
         }
         __syncthreads();
@@ -709,38 +710,30 @@ __global__ __launch_bounds__(256) void crf_nll_stable_bwd_kernel(const float* __
     for (long long e = (long long)c * 256 + threadIdx.x; e < total; e += CRF_ST_CHUNKS * 256) dem[base + e] = g * dem_unit[base + e];
 }
 
-__global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* __restrict__ dst) {
-    const long long total = n * C;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const long long r = e / C;
-        dst[e] = src[(long long)idx[r] * C + (e - r * C)];
-    }
-}
-
-__global__ void scatter_rows_add_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* dst) {
-    const long long total = n * C;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-        const long long r = e / C;
-        unsafeAtomicAdd(dst + (long long)idx[r] * C + (e - r * C), src[e]);
-    }
-}
-
-static inline int rows_grid(long long n) {
-    long long g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
 }  // namespace vbg
 
 using namespace vbg;
 #define S_ ((hipStream_t)stream)
 
+// the tag range every entry holds its arguments to; min_ntag is the entry's own lower bound
+static inline bool crf_tags_ok(int min_ntag, int ntag, int start_tag, int stop_tag) {
+    return ntag >= min_ntag && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag;
+}
+
+// a wave kernel's instance for ntag: two lanes per tag up to 32 tags, the template size the next multiple of 8 / 16
+#define VBG_CRF_DISPATCH(KERNEL, ...)                                                              \
+    do {                                                                                           \
+        if (ntag <= 8) VBG_LAUNCH((KERNEL<8, true>), dim3(ndoc), dim3(64), 0, S_, __VA_ARGS__);           \
+        else if (ntag <= 16) VBG_LAUNCH((KERNEL<16, true>), dim3(ndoc), dim3(64), 0, S_, __VA_ARGS__);    \
+        else if (ntag <= 32) VBG_LAUNCH((KERNEL<32, true>), dim3(ndoc), dim3(64), 0, S_, __VA_ARGS__);    \
+        else if (ntag <= 48) VBG_LAUNCH((KERNEL<48, false>), dim3(ndoc), dim3(64), 0, S_, __VA_ARGS__);   \
+        else VBG_LAUNCH((KERNEL<64, false>), dim3(ndoc), dim3(64), 0, S_, __VA_ARGS__);                   \
+    } while (0)
+
 extern "C" int vbg_crf_nll_fwd(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
                                int start_tag, int stop_tag, float* alpha, float* logz, float* nll, void* stream) {
     VBG_CHECK_ARG(emissions && tags && doc_off && trans && alpha && logz && nll && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(2, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_nll_fwd_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, alpha, logz,
                nll);
@@ -751,7 +744,7 @@ extern "C" int vbg_crf_nll_bwd(const float* emissions, const int* tags, const in
                                int start_tag, int stop_tag, const float* alpha, const float* logz, const float* gout, float* demissions,
                                float* dtrans_accum, void* stream) {
     VBG_CHECK_ARG(emissions && tags && doc_off && trans && alpha && logz && gout && demissions && dtrans_accum && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(2, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_nll_bwd_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, alpha, logz,
                gout, demissions, dtrans_accum, (float*)nullptr);
@@ -762,7 +755,7 @@ extern "C" int vbg_crf_nll_bwd_det(const float* emissions, const int* tags, cons
                                    int start_tag, int stop_tag, const float* alpha, const float* logz, const float* gout, float* demissions,
                                    float* dtrans_part, void* stream) {
     VBG_CHECK_ARG(emissions && tags && doc_off && trans && alpha && logz && gout && demissions && dtrans_part && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(2, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_nll_bwd_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, tags, doc_off, trans, ntag, start_tag, stop_tag, alpha, logz,
                gout, demissions, (float*)nullptr, dtrans_part);
@@ -772,7 +765,7 @@ extern "C" int vbg_crf_nll_bwd_det(const float* emissions, const int* tags, cons
 extern "C" int vbg_crf_viterbi(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                                int stop_tag, int* backptr, int* path, float* score, void* stream) {
     VBG_CHECK_ARG(emissions && doc_off && trans && backptr && path && score && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(2, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     VBG_LAUNCH(crf_viterbi_kernel, dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, start_tag, stop_tag, backptr, path, score);
     VBG_LAUNCH_RET();
@@ -781,41 +774,27 @@ extern "C" int vbg_crf_viterbi(const float* emissions, const int* doc_off, int n
 extern "C" int vbg_crf_posterior(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                                  int stop_tag, void* ws, int* path, float* score, float* logz, float* marginals, void* stream) {
     VBG_CHECK_ARG(emissions && doc_off && trans && ws && path && score && logz && marginals && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 2 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(2, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     float* w = static_cast<float*>(ws);
-#define VBG_CRF_POST(NTP, HALF) VBG_LAUNCH((crf_posterior_kernel<NTP, HALF>), dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, \
-                                           start_tag, stop_tag, w, path, score, logz, marginals)
-    if (ntag <= 8) VBG_CRF_POST(8, true);
-    else if (ntag <= 16) VBG_CRF_POST(16, true);
-    else if (ntag <= 32) VBG_CRF_POST(32, true);
-    else if (ntag <= 48) VBG_CRF_POST(48, false);
-    else VBG_CRF_POST(64, false);
-#undef VBG_CRF_POST
+    VBG_CRF_DISPATCH(crf_posterior_kernel, emissions, doc_off, trans, ntag, start_tag, stop_tag, w, path, score, logz, marginals);
     VBG_LAUNCH_RET();
 }
 
 extern "C" int vbg_crf_path_logp(const float* emissions, const int* doc_off, int ndoc, const float* trans, int ntag, int start_tag,
                                  int stop_tag, const int* path, void* ws, float* lm, float* lc, void* stream) {
     VBG_CHECK_ARG(doc_off && trans && ndoc >= 0);
-    VBG_CHECK_ARG(ntag >= 1 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(1, ntag, start_tag, stop_tag));
     if (ndoc == 0) return VBG_OK;
     VBG_CHECK_ARG(emissions && path && ws && lm && lc);
     float* w = static_cast<float*>(ws);
-#define VBG_CRF_PLOGP(NTP, HALF) VBG_LAUNCH((crf_path_logp_kernel<NTP, HALF>), dim3(ndoc), dim3(64), 0, S_, emissions, doc_off, trans, ntag, \
-                                            start_tag, stop_tag, path, w, lm, lc)
-    if (ntag <= 8) VBG_CRF_PLOGP(8, true);
-    else if (ntag <= 16) VBG_CRF_PLOGP(16, true);
-    else if (ntag <= 32) VBG_CRF_PLOGP(32, true);
-    else if (ntag <= 48) VBG_CRF_PLOGP(48, false);
-    else VBG_CRF_PLOGP(64, false);
-#undef VBG_CRF_PLOGP
+    VBG_CRF_DISPATCH(crf_path_logp_kernel, emissions, doc_off, trans, ntag, start_tag, stop_tag, path, w, lm, lc);
     VBG_LAUNCH_RET();
 }
 
 extern "C" int vbg_crf_nll_stable(const float* emissions, const int* tags, const int* doc_off, int ndoc, const float* trans, int ntag,
                                   int start_tag, int stop_tag, float* nll, float* logz, float* dem_unit, float* dtrans_unit, void* stream) {
-    VBG_CHECK_ARG(ntag >= 1 && ntag <= CRF_MAX_TAGS && start_tag >= 0 && start_tag < ntag && stop_tag >= 0 && stop_tag < ntag);
+    VBG_CHECK_ARG(crf_tags_ok(1, ntag, start_tag, stop_tag));
     VBG_CHECK_ARG(ndoc >= 0 && (dem_unit == nullptr) == (dtrans_unit == nullptr));
     if (ndoc == 0) return VBG_OK;
     VBG_CHECK_ARG(emissions && tags && doc_off && trans && nll && logz);
@@ -832,21 +811,5 @@ extern "C" int vbg_crf_nll_stable_bwd(const float* dem_unit, const float* dtrans
     const int tr_blocks = cdiv(ntag * ntag, 256);
     VBG_LAUNCH(crf_nll_stable_bwd_kernel, dim3(tr_blocks + ndoc * CRF_ST_CHUNKS), dim3(256), 0, S_, dem_unit, dtrans_unit, doc_off, ndoc,
                ntag, tr_blocks, gout, demissions, dtrans_accum);
-    VBG_LAUNCH_RET();
-}
-
-extern "C" int vbg_gather_rows(const float* src, const int* idx, long long n, int C, float* dst, void* stream) {
-    VBG_CHECK_ARG(n >= 0 && C > 0);
-    if (n == 0) return VBG_OK;
-    VBG_CHECK_ARG(src && idx && dst);
-    VBG_LAUNCH(gather_rows_kernel, dim3(rows_grid(n * C)), dim3(256), 0, S_, src, idx, n, C, dst);
-    VBG_LAUNCH_RET();
-}
-
-extern "C" int vbg_scatter_rows_add(const float* src, const int* idx, long long n, int C, float* dst_accum, void* stream) {
-    VBG_CHECK_ARG(n >= 0 && C > 0);
-    if (n == 0) return VBG_OK;
-    VBG_CHECK_ARG(src && idx && dst_accum);
-    VBG_LAUNCH(scatter_rows_add_kernel, dim3(rows_grid(n * C)), dim3(256), 0, S_, src, idx, n, C, dst_accum);
     VBG_LAUNCH_RET();
 }

@@ -4,7 +4,8 @@
 // run and the best run of every class -- in ONE launch, one 256-thread workgroup per document.  The strings stay on the host
 // (vbg/decode.py joins them for the winning runs only).
 //
-// The document is walked in chunks of 256 rows, one row per thread, with four barriers per chunk:
+// The document is walked in chunks of 256 rows, one row per thread, with four barriers per chunk (field_runs_kernel, the listing of
+// EVERY run, walks the same chunks and keeps no winner tables):
 //   rows      each thread forms its row's softmax with the helper row_softmax_kernel uses (vbg_common.h: same bits), takes the first
 //             index of the largest probability and applies the threshold in DOUBLE (the reference compares two Python floats);
 //   run heads a row whose left neighbour has another class starts a run.  Wave ballots give every head the head in front of it;
@@ -63,6 +64,20 @@ struct dec_tags { unsigned char cls[DEC_MAX_C]; unsigned char begin[DEC_MAX_C]; 
 // a run's mean from its sum: the one rounding of either instance
 __device__ __forceinline__ double run_mean(double sum, int len) { return sum / (double)len; }
 __device__ __forceinline__ double run_mean(long long sum, int len) { return (double)sum * (1.0 / DEC_FIX) / (double)len; }
+
+// the head in front of the head in `lane` of wave w: in the wave's ballot hm, else in an earlier wave, else -1 (in an earlier chunk)
+__device__ __forceinline__ int dec_prev_head(unsigned long long hm, int lane, int w, int base, const int* s_whead) {
+    const unsigned long long lower = hm & ((1ull << lane) - 1ull);
+    int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
+    for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
+    return ph;
+}
+
+__device__ __forceinline__ vbg_run_rec run_rec(int start, int len, int cls, double mean, double logp) {
+    vbg_run_rec r;
+    r.start = start; r.len = len; r.cls = cls; r.pad = 0; r.mean = mean; r.logp = logp;
+    return r;
+}
 
 // TAGS == false: x = class scores [N, cols], cols == C, `path` and `tags` unused.  TAGS == true: x = marginals [N, cols], cols == ntag.
 template <bool TAGS>
@@ -157,9 +172,7 @@ __global__ __launch_bounds__(DEC_THREADS) void field_decode_kernel(const float* 
         unsigned long long bits = 0ull, key = 0ull;
         int fc = -1;
         if (head && g > 0) {
-            const unsigned long long lower = hm & ((1ull << lane) - 1ull);
-            int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
-            for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
+            int ph = dec_prev_head(hm, lane, w, base, s_whead);
             sum_t ppb;
             if (ph >= 0) ppb = s_pb[ph - base];
             else { ph = open_head; ppb = open_pb; }
@@ -311,26 +324,17 @@ __global__ __launch_bounds__(DEC_THREADS) void field_runs_kernel(const float* __
         if (lane == 0) s_whead[w] = hm ? base + w * 64 + highest_bit(hm) : -1;
         __syncthreads();                                                            // 2: prefix sums and wave heads
         if (head && g > 0) {                                // a head closes the run in front of it: that run's record, at its first row
-            const unsigned long long lower = hm & ((1ull << lane) - 1ull);
-            int ph = lower ? base + w * 64 + highest_bit(lower) : -1;
-            for (int k = w - 1; k >= 0 && ph < 0; --k) ph = s_whead[k];
+            int ph = dec_prev_head(hm, lane, w, base, s_whead);
             sum_t ppb;
             double ppl;
             if (ph >= 0) { ppb = s_pb[ph - base]; ppl = s_pl[ph - base]; }
             else { ph = open_head; ppb = open_pb; ppl = open_pl; }
-            vbg_run_rec r;
-            r.start = ph;
-            r.len = g - ph;
-            r.cls = left;
-            r.pad = 0;
-            r.mean = run_mean(pb - ppb, r.len);
-            r.logp = 0.0;
-            if constexpr (TAGS) r.logp = (double)lm[r0 + ph] + ((pl - own_l) - ppl);
-            runs[r0 + ph] = r;
+            const double mean = run_mean(pb - ppb, g - ph);
+            double logp = 0.0;
+            if constexpr (TAGS) logp = (double)lm[r0 + ph] + ((pl - own_l) - ppl);
+            runs[r0 + ph] = run_rec(ph, g - ph, left, mean, logp);
         } else if (valid && !head) {
-            vbg_run_rec r;
-            r.start = 0; r.len = 0; r.cls = 0; r.pad = 0; r.mean = 0.0; r.logp = 0.0;
-            runs[r0 + g] = r;
+            runs[r0 + g] = run_rec(0, 0, 0, 0.0, 0.0);
         }
         int lh = -1;
         for (int k = DEC_WAVES - 1; k >= 0 && lh < 0; --k) lh = s_whead[k];
@@ -341,15 +345,10 @@ __global__ __launch_bounds__(DEC_THREADS) void field_runs_kernel(const float* __
         __syncthreads();                                                            // 3: the chunk's tables are free again
     }
     if (n > 0 && t == 0) {                                  // the last run
-        vbg_run_rec r;
-        r.start = open_head;
-        r.len = n - open_head;
-        r.cls = last_cls;
-        r.pad = 0;
-        r.mean = run_mean(total - open_pb, r.len);
-        r.logp = 0.0;
-        if constexpr (TAGS) r.logp = (double)lm[r0 + open_head] + (total_l - open_pl);
-        runs[r0 + open_head] = r;
+        const double mean = run_mean(total - open_pb, n - open_head);
+        double logp = 0.0;
+        if constexpr (TAGS) logp = (double)lm[r0 + open_head] + (total_l - open_pl);
+        runs[r0 + open_head] = run_rec(open_head, n - open_head, last_cls, mean, logp);
     }
 }
 
@@ -357,56 +356,71 @@ __global__ __launch_bounds__(DEC_THREADS) void field_runs_kernel(const float* __
 
 using namespace vbg;
 
-// the part the two entries share: the row ranges' checks and the launches, 512 documents each
-template <bool TAGS>
-static int decode_launch(const float* x, const int* path, const int* h_doc_off, int ndoc, const dec_tags& tags, int cols, int C,
-                         int use_thresh, double thresh, int* cls, float* score, vbg_decode_rec* best, void* stream) {
-    VBG_CHECK_ARG(h_doc_off[0] >= 0);
+// the row ranges: ascending from a row >= 0, every document shorter than 2^20 rows
+static bool dec_rows_ok(const int* h_doc_off, int ndoc) {
+    if (h_doc_off[0] < 0) return false;
     for (int d = 0; d < ndoc; ++d) {
         const long long nd = (long long)h_doc_off[d + 1] - h_doc_off[d];
-        VBG_CHECK_ARG(nd >= 0 && nd < (1ll << DEC_ROW_BITS));
+        if (!(nd >= 0 && nd < (1ll << DEC_ROW_BITS))) return false;
     }
-    if (ndoc == 0) return VBG_OK;
-    VBG_CHECK_ARG(best);
-    if (h_doc_off[ndoc] > h_doc_off[0]) VBG_CHECK_ARG(x && cls && score && (path || !TAGS));
+    return true;
+}
+
+// the two host tables of a *_tags entry, checked, as the kernels take them
+static bool dec_make_tags(dec_tags& tags, int ntag, int C, const int* h_tag_class, const int* h_tag_begin) {
+    if (!(C >= 1 && C <= DEC_MAX_C && ntag >= 1 && ntag <= DEC_MAX_C && h_tag_class && h_tag_begin)) return false;
+    tags = {};
+    for (int k = 0; k < ntag; ++k) {
+        if (!(h_tag_class[k] >= 0 && h_tag_class[k] < C && (h_tag_begin[k] == 0 || h_tag_begin[k] == 1))) return false;
+        tags.cls[k] = (unsigned char)h_tag_class[k];
+        tags.begin[k] = (unsigned char)h_tag_begin[k];
+    }
+    return true;
+}
+
+// the launches, DEC_DOCS documents each: launch(docs, nd, d0) starts the kernel for documents d0 .. d0 + nd - 1
+template <class Launch>
+static int dec_batches(const int* h_doc_off, int ndoc, Launch launch) {
     for (int d0 = 0; d0 < ndoc; d0 += DEC_DOCS) {
         const int nd = ndoc - d0 < DEC_DOCS ? ndoc - d0 : DEC_DOCS;
         dec_docs docs;
         for (int i = 0; i <= nd; ++i) docs.off[i] = h_doc_off[d0 + i];
         for (int i = nd + 1; i <= DEC_DOCS; ++i) docs.off[i] = docs.off[nd];
-        VBG_LAUNCH(field_decode_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, docs, tags, d0, cols, C,
-                   use_thresh, thresh, cls, score, best);
+        launch(docs, nd, d0);
     }
     VBG_LAUNCH_RET();
+}
+
+template <bool TAGS>
+static int decode_launch(const float* x, const int* path, const int* h_doc_off, int ndoc, const dec_tags& tags, int cols, int C,
+                         int use_thresh, double thresh, int* cls, float* score, vbg_decode_rec* best, void* stream) {
+    VBG_CHECK_ARG(dec_rows_ok(h_doc_off, ndoc));
+    if (ndoc == 0) return VBG_OK;
+    VBG_CHECK_ARG(best);
+    if (h_doc_off[ndoc] > h_doc_off[0]) VBG_CHECK_ARG(x && cls && score && (path || !TAGS));
+    return dec_batches(h_doc_off, ndoc, [&](const dec_docs& docs, int nd, int d0) {
+        VBG_LAUNCH(field_decode_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, docs, tags, d0, cols, C,
+                   use_thresh, thresh, cls, score, best);
+    });
+}
+
+template <bool TAGS>
+static int runs_launch(const float* x, const int* path, const float* lm, const float* lc, const int* h_doc_off, int ndoc,
+                       const dec_tags& tags, int cols, int use_thresh, double thresh, int* cls, float* score, vbg_run_rec* runs,
+                       void* stream) {
+    VBG_CHECK_ARG(dec_rows_ok(h_doc_off, ndoc));
+    if (ndoc == 0 || h_doc_off[ndoc] == h_doc_off[0]) return VBG_OK;
+    VBG_CHECK_ARG(x && cls && score && runs && (!TAGS || (path && lm && lc)));
+    return dec_batches(h_doc_off, ndoc, [&](const dec_docs& docs, int nd, int) {
+        VBG_LAUNCH(field_runs_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, lm, lc, docs, tags, cols,
+                   use_thresh, thresh, cls, score, runs);
+    });
 }
 
 extern "C" int vbg_field_decode(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
                                 float* score, vbg_decode_rec* best, void* stream) {
     VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C);
     return decode_launch<false>(x, nullptr, h_doc_off, ndoc, dec_tags{}, C, C, use_thresh, thresh, cls, score, best, stream);
-}
-
-// the listing entries' share: decode_launch's checks of the row ranges, and the launches
-template <bool TAGS>
-static int runs_launch(const float* x, const int* path, const float* lm, const float* lc, const int* h_doc_off, int ndoc,
-                       const dec_tags& tags, int cols, int use_thresh, double thresh, int* cls, float* score, vbg_run_rec* runs,
-                       void* stream) {
-    VBG_CHECK_ARG(h_doc_off[0] >= 0);
-    for (int d = 0; d < ndoc; ++d) {
-        const long long nd = (long long)h_doc_off[d + 1] - h_doc_off[d];
-        VBG_CHECK_ARG(nd >= 0 && nd < (1ll << DEC_ROW_BITS));
-    }
-    if (ndoc == 0 || h_doc_off[ndoc] == h_doc_off[0]) return VBG_OK;
-    VBG_CHECK_ARG(x && cls && score && runs && (!TAGS || (path && lm && lc)));
-    for (int d0 = 0; d0 < ndoc; d0 += DEC_DOCS) {
-        const int nd = ndoc - d0 < DEC_DOCS ? ndoc - d0 : DEC_DOCS;
-        dec_docs docs;
-        for (int i = 0; i <= nd; ++i) docs.off[i] = h_doc_off[d0 + i];
-        for (int i = nd + 1; i <= DEC_DOCS; ++i) docs.off[i] = docs.off[nd];
-        VBG_LAUNCH(field_runs_kernel<TAGS>, dim3(nd), dim3(DEC_THREADS), 0, (hipStream_t)stream, x, path, lm, lc, docs, tags, cols,
-                   use_thresh, thresh, cls, score, runs);
-    }
-    VBG_LAUNCH_RET();
 }
 
 extern "C" int vbg_field_runs(const float* x, const int* h_doc_off, int ndoc, int C, int use_thresh, double thresh, int* cls,
@@ -418,25 +432,15 @@ extern "C" int vbg_field_runs(const float* x, const int* h_doc_off, int ndoc, in
 extern "C" int vbg_field_runs_tags(const float* marginals, const int* path, const float* lm, const float* lc, const int* h_doc_off,
                                    int ndoc, int ntag, int C, const int* h_tag_class, const int* h_tag_begin, int use_thresh,
                                    double thresh, int* cls, float* score, vbg_run_rec* runs, void* stream) {
-    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C && ntag >= 1 && ntag <= DEC_MAX_C && h_tag_class && h_tag_begin);
-    dec_tags tags = {};
-    for (int k = 0; k < ntag; ++k) {
-        VBG_CHECK_ARG(h_tag_class[k] >= 0 && h_tag_class[k] < C && (h_tag_begin[k] == 0 || h_tag_begin[k] == 1));
-        tags.cls[k] = (unsigned char)h_tag_class[k];
-        tags.begin[k] = (unsigned char)h_tag_begin[k];
-    }
+    dec_tags tags;
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && dec_make_tags(tags, ntag, C, h_tag_class, h_tag_begin));
     return runs_launch<true>(marginals, path, lm, lc, h_doc_off, ndoc, tags, ntag, use_thresh, thresh, cls, score, runs, stream);
 }
 
 extern "C" int vbg_field_decode_tags(const float* marginals, const int* path, const int* h_doc_off, int ndoc, int ntag, int C,
                                      const int* h_tag_class, const int* h_tag_begin, int use_thresh, double thresh, int* cls, float* score,
                                      vbg_decode_rec* best, void* stream) {
-    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && C >= 1 && C <= DEC_MAX_C && ntag >= 1 && ntag <= DEC_MAX_C && h_tag_class && h_tag_begin);
-    dec_tags tags = {};
-    for (int k = 0; k < ntag; ++k) {
-        VBG_CHECK_ARG(h_tag_class[k] >= 0 && h_tag_class[k] < C && (h_tag_begin[k] == 0 || h_tag_begin[k] == 1));
-        tags.cls[k] = (unsigned char)h_tag_class[k];
-        tags.begin[k] = (unsigned char)h_tag_begin[k];
-    }
+    dec_tags tags;
+    VBG_CHECK_ARG(h_doc_off && ndoc >= 0 && dec_make_tags(tags, ntag, C, h_tag_class, h_tag_begin));
     return decode_launch<true>(marginals, path, h_doc_off, ndoc, tags, ntag, C, use_thresh, thresh, cls, score, best, stream);
 }

@@ -3,7 +3,7 @@
 // per-element CE forward/backward straight from low-resolution logits (the x4 nearest upsampling of
 // model/semantic_segmentation_head.py:73 is folded into the row index, so the 268 MB/doc
 // upsampled activation never exists), order-preserving category compaction, a STABLE descending
-// radix sort (rocPRIM device primitive, <1 % of the step), gathers and sums.
+// radix sort (rocPRIM device primitive, <1 % of the step), gathers (of elements, and of whole rows with their scatter-add) and sums.
 // The host-RNG driven index selection (python `random.sample`) stays on the host, as in the reference; the opt-in route that draws and
 // selects on the device is csrc/sample.hip, and the *_dyn entries below serve its lists (capacity on the host, count on the device).
 #include "vbg_common.h"
@@ -71,6 +71,30 @@ __global__ void gather_f32_kernel(const float* __restrict__ src, const int* __re
 __global__ void gather_i32_kernel(const int* __restrict__ src, const int* __restrict__ idx, long long n, int* __restrict__ out) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = src[idx[i]];
+}
+// whole rows of C floats: the two-stage `full` classifier's gather and its scatter-add (model/field_type_classification_head.py:371,
+// 389-395: `fuse_embeddings[pred_pos_neg_mask]`)
+__global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* __restrict__ dst) {
+    const long long total = n * C;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const long long r = e / C;
+        dst[e] = src[(long long)idx[r] * C + (e - r * C)];
+    }
+}
+
+__global__ void scatter_rows_add_kernel(const float* __restrict__ src, const int* __restrict__ idx, long long n, int C, float* dst) {
+    const long long total = n * C;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const long long r = e / C;
+        unsafeAtomicAdd(dst + (long long)idx[r] * C + (e - r * C), src[e]);
+    }
+}
+
+static inline int rows_grid(long long n) {
+    long long g = (n + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 __global__ void iota_kernel(int* out, long long n) {
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -197,6 +221,22 @@ extern "C" int vbg_gather_i32(const int* src, const int* idx, long long n, int* 
     if (n == 0) return VBG_OK;
     VBG_CHECK_ARG(src && idx && out);
     VBG_LAUNCH(gather_i32_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S_, src, idx, n, out);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_gather_rows(const float* src, const int* idx, long long n, int C, float* dst, void* stream) {
+    VBG_CHECK_ARG(n >= 0 && C > 0);
+    if (n == 0) return VBG_OK;
+    VBG_CHECK_ARG(src && idx && dst);
+    VBG_LAUNCH(gather_rows_kernel, dim3(rows_grid(n * C)), dim3(256), 0, S_, src, idx, n, C, dst);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_scatter_rows_add(const float* src, const int* idx, long long n, int C, float* dst_accum, void* stream) {
+    VBG_CHECK_ARG(n >= 0 && C > 0);
+    if (n == 0) return VBG_OK;
+    VBG_CHECK_ARG(src && idx && dst_accum);
+    VBG_LAUNCH(scatter_rows_add_kernel, dim3(rows_grid(n * C)), dim3(256), 0, S_, src, idx, n, C, dst_accum);
     VBG_LAUNCH_RET();
 }
 

@@ -71,6 +71,16 @@ def _check_pred_label(pred_label):
         raise TypeError(f"pred_label must be a 2-D float32 device tensor of class scores [N, C], got {what}")
 
 
+def _segment_texts(ocr_text, n, join):
+    """the n segment texts of a document (ocr_text itself, or entry 0 of the reference's batch tuple), and the join rule checked"""
+    if join not in JOIN:
+        raise ValueError(f"join must be one of {sorted(JOIN)}, got {join!r}")
+    texts = ocr_text[0] if len(ocr_text) > 0 and not isinstance(ocr_text[0], str) else ocr_text
+    if len(texts) != n:
+        raise ValueError(f"{len(texts)} segment texts for {n} rows")
+    return texts
+
+
 def decode_fields(pred_label, thresh=None, doc_off=None):
     """-> FieldDecode.  thresh: the reference's `strcmp_tresh` (a Python float, compared in double; None at the deployment sites);
     doc_off: HOST row ranges of a batch of documents (ndoc + 1 ints; None: all rows are one document)."""
@@ -92,13 +102,9 @@ def field_strings(pred_label, num_classes, ocr_text, thresh=None, join="space_be
     """The reference's `pred_key_list` of one document: one string per class (class 0 included; callers skip it).  ocr_text: the
     document's segment texts, or the reference's batch tuple whose entry 0 holds them (`ocr_text[0][seg_index]`)."""
     _check_pred_label(pred_label)
-    if join not in JOIN:
-        raise ValueError(f"join must be one of {sorted(JOIN)}, got {join!r}")
     if int(num_classes) != pred_label.shape[1]:
         raise ValueError(f"num_classes {num_classes} != pred_label.shape[1] {pred_label.shape[1]}")
-    texts = ocr_text[0] if len(ocr_text) > 0 and not isinstance(ocr_text[0], str) else ocr_text
-    if len(texts) != pred_label.shape[0]:
-        raise ValueError(f"{len(texts)} segment texts for {pred_label.shape[0]} rows")
+    texts = _segment_texts(ocr_text, pred_label.shape[0], join)
     return join_winners(decode_fields(pred_label, thresh).best[0], texts, join)
 
 
@@ -154,11 +160,7 @@ def decode_tags(posterior, table, num_classes, thresh=None, doc_off=None):
 def crf_field_strings(posterior, table, num_classes, ocr_text, thresh=None, join="space_before"):
     """`pred_key_list` of one document in the crf mode: one string per class, joined by the rules of field_strings"""
     marginals, _ = _posterior_parts(posterior)
-    if join not in JOIN:
-        raise ValueError(f"join must be one of {sorted(JOIN)}, got {join!r}")
-    texts = ocr_text[0] if len(ocr_text) > 0 and not isinstance(ocr_text[0], str) else ocr_text
-    if len(texts) != marginals.shape[0]:
-        raise ValueError(f"{len(texts)} segment texts for {marginals.shape[0]} rows")
+    texts = _segment_texts(ocr_text, marginals.shape[0], join)
     return join_winners(decode_tags(posterior, table, num_classes, thresh).best[0], texts, join)
 
 

@@ -2031,6 +2031,27 @@ def row_softmax(x):
     return y
 
 
+def _doc_rows(name, doc_off, N):
+    """the HOST row ranges of a decode entry -> (ctypes array of ndoc + 1 ints, ndoc); None: one document, all N rows"""
+    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
+    ndoc = len(off) - 1
+    if ndoc < 0 or off[-1] > N:
+        raise VbgError(f"{name}: doc_off {off[:4]}... does not fit {N} rows")
+    return (C.c_int * (ndoc + 1))(*off), ndoc
+
+
+def _chk_tag_path(name, path, N, device):
+    if path.dtype != i32 or tuple(path.shape) != (N,) or path.device != device:
+        raise VbgError(f"{name}: path must be int32 [{N}] on {device}, got {path.dtype} {tuple(path.shape)}")
+
+
+def _tag_tables(name, tag_class, tag_begin, ntag):
+    """the two HOST lists of ntag ints (tag -> class; 1 where the tag opens a new run) as ctypes arrays"""
+    if len(tag_class) != ntag or len(tag_begin) != ntag:
+        raise VbgError(f"{name}: {len(tag_class)} / {len(tag_begin)} table entries for {ntag} tags")
+    return (C.c_int * max(ntag, 1))(*[int(v) for v in tag_class]), (C.c_int * max(ntag, 1))(*[int(v) for v in tag_begin])
+
+
 def field_decode(x, doc_off=None, thresh=None):
     """x [N, C] fp32 class scores (device) -> (cls int32 [N], score fp32 [N], best float64 [ndoc * C, 2]) in ONE launch
     (vbg_field_decode, include/vbg.h).  doc_off: HOST row ranges, ndoc + 1 ints (None: one document, all rows); thresh: a Python
@@ -2038,15 +2059,12 @@ def field_decode(x, doc_off=None, thresh=None):
     two doubles: vbg.decode views it after its one copy to the host."""
     _chk_f32(x)
     N, ncls = x.shape
-    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
-    ndoc = len(off) - 1
-    if ndoc < 0 or off[-1] > N:
-        raise VbgError(f"vbg_field_decode: doc_off {off[:4]}... does not fit {N} rows")
+    off, ndoc = _doc_rows("vbg_field_decode", doc_off, N)
     cls = torch.empty(N, dtype=i32, device=x.device)
     score = torch.empty(N, dtype=f32, device=x.device)
     best = torch.empty(ndoc * ncls, 2, dtype=torch.float64, device=x.device)
-    check(lib.vbg_field_decode(P(x.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, int(thresh is not None),
-                               0.0 if thresh is None else float(thresh), P(cls), P(score), P(best), _stream()), "vbg_field_decode")
+    check(lib.vbg_field_decode(P(x.contiguous()), off, ndoc, ncls, int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(best), _stream()),
+          "vbg_field_decode")
     return cls, score, best
 
 
@@ -2768,16 +2786,20 @@ def crf_viterbi(em, doc_off, trans, start, stop):
     return path, score
 
 
+def _chk_crf(name, em, trans, doc_off):
+    """emissions [N, ntag], transitions [ntag, ntag] (fp32, device) and int32 row ranges of a wave-kernel entry -> (N, ntag, ndoc)"""
+    _chk_f32(em, trans)
+    N, ntag = em.shape
+    if tuple(trans.shape) != (ntag, ntag) or doc_off.dtype != i32:
+        raise VbgError(f"{name}: trans {tuple(trans.shape)} / doc_off {doc_off.dtype} do not fit emissions [{N}, {ntag}]")
+    return N, ntag, doc_off.numel() - 1
+
+
 def crf_posterior(em, doc_off, trans, start, stop):
     """-> (path int32 [N], score [ndoc], logz [ndoc], marginals [N, ntag]) in ONE launch (vbg_crf_posterior, include/vbg.h): path and
     score are crf_viterbi's bit for bit; marginals[t, i] = p(y_t = i | x), each row summing to 1, the START / STOP columns exact zeros.
     No atomics: the deterministic mode takes the same route."""
-    _chk_f32(em)
-    _chk_f32(trans)
-    N, ntag = em.shape
-    ndoc = doc_off.numel() - 1
-    if tuple(trans.shape) != (ntag, ntag) or doc_off.dtype != i32:
-        raise VbgError(f"vbg_crf_posterior: trans {tuple(trans.shape)} / doc_off {doc_off.dtype} do not fit emissions [{N}, {ntag}]")
+    N, ntag, ndoc = _chk_crf("vbg_crf_posterior", em, trans, doc_off)
     ws = torch.empty((max(N, 1), 2 * ntag), device=em.device, dtype=f32)
     path = torch.empty((N,), device=em.device, dtype=i32)
     score = torch.empty((ndoc,), device=em.device, dtype=f32)
@@ -2793,12 +2815,7 @@ def crf_path_logp(em, doc_off, trans, start, stop, path):
     log p(y_t = path[t] | y_{t-1} = path[t-1], x), lc of a document's first row its lm -- lm[s] + lc[s+1 .. e].sum() is the log posterior
     of the span s .. e holding the path's tags.  path: int32 [N], any tags (crf_posterior's, gold, an alternative).  No atomics: the
     deterministic mode takes the same route."""
-    _chk_f32(em)
-    _chk_f32(trans)
-    N, ntag = em.shape
-    ndoc = doc_off.numel() - 1
-    if tuple(trans.shape) != (ntag, ntag) or doc_off.dtype != i32:
-        raise VbgError(f"vbg_crf_path_logp: trans {tuple(trans.shape)} / doc_off {doc_off.dtype} do not fit emissions [{N}, {ntag}]")
+    N, ntag, ndoc = _chk_crf("vbg_crf_path_logp", em, trans, doc_off)
     if not torch.is_tensor(path) or path.dtype != i32 or tuple(path.shape) != (N,) or path.device != em.device:
         what = (path.dtype, tuple(path.shape), path.device) if torch.is_tensor(path) else type(path)
         raise VbgError(f"vbg_crf_path_logp: path must be int32 [{N}] on {em.device}, got {what}")
@@ -2838,11 +2855,9 @@ def crf_nll_stable(em, tags, doc_off, trans, start, stop, want_grad):
     include/vbg.h).  The two tables (want_grad) are the gradient of n_d * nll[d] -- marginals less gold indicators -- from pairwise
     tables that are divided by their own sums; crf_nll_stable_bwd scales them.  No atomics: the deterministic mode takes the same route."""
     _chk_crf_stable("vbg_crf_nll_stable", em, doc_off)
-    _chk_f32(trans)
-    N, ntag = em.shape
-    ndoc = doc_off.numel() - 1
-    if tuple(trans.shape) != (ntag, ntag) or tags.dtype != i32 or tuple(tags.shape) != (N,) or tags.device != em.device:
-        raise VbgError(f"vbg_crf_nll_stable: trans {tuple(trans.shape)} / tags {tags.dtype} {tuple(tags.shape)} do not fit emissions [{N}, {ntag}]")
+    N, ntag, ndoc = _chk_crf("vbg_crf_nll_stable", em, trans, doc_off)
+    if tags.dtype != i32 or tuple(tags.shape) != (N,) or tags.device != em.device:
+        raise VbgError(f"vbg_crf_nll_stable: tags {tags.dtype} {tuple(tags.shape)} on {tags.device} do not fit emissions [{N}, {ntag}] on {em.device}")
     nll = torch.empty((ndoc,), device=em.device, dtype=f32)
     logz = torch.empty((ndoc,), device=em.device, dtype=f32)
     dem_unit = torch.empty((N, ntag), device=em.device, dtype=f32) if want_grad else None
@@ -2879,23 +2894,15 @@ def field_decode_tags(marginals, path, tag_class, tag_begin, num_classes, doc_of
     class; 1 where the tag opens a new run); doc_off, thresh and the layout of `best` as in field_decode."""
     _chk_f32(marginals)
     N, ntag = marginals.shape
-    if path.dtype != i32 or tuple(path.shape) != (N,) or path.device != marginals.device:
-        raise VbgError(f"vbg_field_decode_tags: path must be int32 [{N}] on {marginals.device}, got {path.dtype} {tuple(path.shape)}")
-    if len(tag_class) != ntag or len(tag_begin) != ntag:
-        raise VbgError(f"vbg_field_decode_tags: {len(tag_class)} / {len(tag_begin)} table entries for {ntag} tags")
-    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
-    ndoc = len(off) - 1
+    _chk_tag_path("vbg_field_decode_tags", path, N, marginals.device)
+    tc, tb = _tag_tables("vbg_field_decode_tags", tag_class, tag_begin, ntag)
+    off, ndoc = _doc_rows("vbg_field_decode_tags", doc_off, N)
     ncls = int(num_classes)
-    if ndoc < 0 or off[-1] > N:
-        raise VbgError(f"vbg_field_decode_tags: doc_off {off[:4]}... does not fit {N} rows")
     cls = torch.empty(N, dtype=i32, device=marginals.device)
     score = torch.empty(N, dtype=f32, device=marginals.device)
     best = torch.empty(ndoc * max(ncls, 0), 2, dtype=torch.float64, device=marginals.device)
-    tc = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_class])
-    tb = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_begin])
-    check(lib.vbg_field_decode_tags(P(marginals.contiguous()), P(path.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ntag, ncls, tc, tb,
-                                    int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(best),
-                                    _stream()), "vbg_field_decode_tags")
+    check(lib.vbg_field_decode_tags(P(marginals.contiguous()), P(path.contiguous()), off, ndoc, ntag, ncls, tc, tb, int(thresh is not None), 0.0 if thresh is None else float(thresh),
+                                    P(cls), P(score), P(best), _stream()), "vbg_field_decode_tags")
     return cls, score, best
 
 
@@ -2906,15 +2913,11 @@ def field_runs(x, doc_off=None, thresh=None):
     field_decode."""
     _chk_f32(x)
     N, ncls = x.shape
-    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
-    ndoc = len(off) - 1
-    if ndoc < 0 or off[-1] > N:
-        raise VbgError(f"vbg_field_runs: doc_off {off[:4]}... does not fit {N} rows")
+    off, ndoc = _doc_rows("vbg_field_runs", doc_off, N)
     cls = torch.empty(N, dtype=i32, device=x.device)
     score = torch.empty(N, dtype=f32, device=x.device)
     runs = torch.empty(N, 4, dtype=torch.float64, device=x.device)
-    check(lib.vbg_field_runs(P(x.contiguous()), (C.c_int * (ndoc + 1))(*off), ndoc, ncls, int(thresh is not None),
-                             0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs")
+    check(lib.vbg_field_runs(P(x.contiguous()), off, ndoc, ncls, int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs")
     return cls, score, runs
 
 
@@ -2922,28 +2925,18 @@ def field_runs_tags(marginals, path, lm, lc, tag_class, tag_begin, num_classes, 
     """marginals [N, ntag] fp32 and path [N] int32 (crf_posterior's), lm / lc [N] fp32 (crf_path_logp's for that path) -> (cls, score,
     runs) as field_runs gives them, in ONE launch (vbg_field_runs_tags, include/vbg.h): field_decode_tags' rows and runs, EVERY run
     listed, with logp = lm[s] + the fp64 sum of lc over the run's other rows."""
-    _chk_f32(marginals)
-    _chk_f32(lm)
-    _chk_f32(lc)
+    _chk_f32(marginals, lm, lc)
     N, ntag = marginals.shape
-    if path.dtype != i32 or tuple(path.shape) != (N,) or path.device != marginals.device:
-        raise VbgError(f"vbg_field_runs_tags: path must be int32 [{N}] on {marginals.device}, got {path.dtype} {tuple(path.shape)}")
+    _chk_tag_path("vbg_field_runs_tags", path, N, marginals.device)
     if tuple(lm.shape) != (N,) or tuple(lc.shape) != (N,) or lm.device != marginals.device or lc.device != marginals.device:
         raise VbgError(f"vbg_field_runs_tags: lm {tuple(lm.shape)} / lc {tuple(lc.shape)} must be fp32 [{N}] on {marginals.device}")
-    if len(tag_class) != ntag or len(tag_begin) != ntag:
-        raise VbgError(f"vbg_field_runs_tags: {len(tag_class)} / {len(tag_begin)} table entries for {ntag} tags")
-    off = [0, N] if doc_off is None else [int(v) for v in doc_off]
-    ndoc = len(off) - 1
-    if ndoc < 0 or off[-1] > N:
-        raise VbgError(f"vbg_field_runs_tags: doc_off {off[:4]}... does not fit {N} rows")
+    tc, tb = _tag_tables("vbg_field_runs_tags", tag_class, tag_begin, ntag)
+    off, ndoc = _doc_rows("vbg_field_runs_tags", doc_off, N)
     cls = torch.empty(N, dtype=i32, device=marginals.device)
     score = torch.empty(N, dtype=f32, device=marginals.device)
     runs = torch.empty(N, 4, dtype=torch.float64, device=marginals.device)
-    tc = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_class])
-    tb = (C.c_int * max(ntag, 1))(*[int(v) for v in tag_begin])
-    check(lib.vbg_field_runs_tags(P(marginals.contiguous()), P(path.contiguous()), P(lm.contiguous()), P(lc.contiguous()),
-                                  (C.c_int * (ndoc + 1))(*off), ndoc, ntag, int(num_classes), tc, tb, int(thresh is not None),
-                                  0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs_tags")
+    check(lib.vbg_field_runs_tags(P(marginals.contiguous()), P(path.contiguous()), P(lm.contiguous()), P(lc.contiguous()), off, ndoc, ntag,
+                                  int(num_classes), tc, tb, int(thresh is not None), 0.0 if thresh is None else float(thresh), P(cls), P(score), P(runs), _stream()), "vbg_field_runs_tags")
     return cls, score, runs
 
 

@@ -944,6 +944,16 @@ int vbg_sgd_step(float* p, const float* g, float* mom, long long n, float lr, fl
                  int first_step, float grad_scale, void* stream);
 int vbg_adamw_step(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
                    float eps, float wd, int step, float grad_scale, void* stream);
+/* Weight averaging over a flat range (EMA / SWA; vbg.optim.WeightAverage): avg[i] <- lerp(avg[i], p[i], weight), torch's statement
+ * (ATen/native/Lerp.h) and torch's bits on gfx950: d = p - a (rounded); |weight| < 0.5: fma(weight, d, a), otherwise fma(-d, 1 - weight, p)
+ * with 1 - weight rounded to fp32 first -- each branch's product and sum in one rounding.  One whole-range launch, 12 B per element,
+ * float4 access when both pointers are 16-byte aligned (all-scalar otherwise), no atomics.  avg and p must not overlap.  n == 0 is a
+ * no-op that looks at no pointer; n < 0 or a NULL pointer with n > 0 is an argument error (-1). */
+int vbg_lerp(float* avg, const float* p, long long n, float weight, void* stream);
+/* In-place exchange of a[0, n) and b[0, n) as bit patterns (NaN payloads, -0.0 and denormals included): every element is read and
+ * written by the one thread that owns it, 16 B per element, no temporary.  Same alignment rule and n == 0 / NULL / n < 0 cases as
+ * vbg_lerp; a == b or overlapping ranges is an argument error (-1). */
+int vbg_swap(float* a, float* b, long long n, void* stream);
 /* The same two steps with per-group hyper-parameters (torch param groups) in ONE launch.  `chunks` (device memory, 16-byte
  * aligned) lists the work: chunk k updates elements [start, start + length) with the hyper-parameters of groups[group]; start and
  * length are multiples of 4 elements, chunks do not overlap, and p / g / mom / m / v are 16-byte aligned.  Blocks stride over

@@ -13,7 +13,8 @@
 // the same chunk table: one row pass (grad_norm_seg_kernel: a partial per row, GradScaler's inf check and the reference's loss gate riding
 // along; entries vbg_grad_sumsq_seg, vbg_grad_sumsq_seg_inf, vbg_grad_norm_seg) and one finish (clip_coef_gate_kernel: the total norm and
 // torch's coefficient; entries vbg_clip_coef, vbg_clip_coef_gate).  vbg_grad_unscale_check_seg, GradScaler's own pass (it stores into g),
-// walks the same rows.
+// walks the same rows.  vbg_lerp / vbg_swap (weight averaging: avg <- lerp(avg, p, w) in torch's bits, and the in-place exchange of the
+// live and the averaged buffer) are two more whole-range streams of sgd_kernel's shape.
 #include <type_traits>
 #include "vbg_common.h"
 #include "../../include/vbg.h"
@@ -105,6 +106,49 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
     if (blockIdx.x == 0)
         for (long long i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) upd(p[i], g[i], m[i], v[i]);
+}
+
+// ---- weight averaging (vbg.optim.WeightAverage) --------------------------------------------------------------------------
+// avg <- lerp(avg, p, w) in torch's statement (ATen/native/Lerp.h): |w| < 0.5 ? a + w * (p - a) : p - (p - a) * (1 - w), the difference
+// and 1 - w each rounded on their own, the product and the sum of either branch in ONE rounding (a fused multiply-add: what torch's
+// device kernel was measured to do on gfx950, profiles/weight_average.txt).  Every rounding is spelled out, so the bits do not depend
+// on the compiler's contraction setting.  The branch is uniform over the launch.
+__device__ __forceinline__ float lerp_update(float a, float p, float w, float omw, bool small) {
+    const float d = __fsub_rn(p, a);
+    return small ? __fmaf_rn(w, d, a) : __fmaf_rn(-d, omw, p);
+}
+
+__global__ void lerp_kernel(float* __restrict__ avg, const float* __restrict__ p, long long n4, long long n, float w) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    const float omw = __fsub_rn(1.f, w);
+    const bool small = fabsf(w) < 0.5f;
+    auto upd = [&](float& av, float pv) { av = lerp_update(av, pv, w, omw, small); };
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float4 av = reinterpret_cast<float4*>(avg)[i];
+        const float4 pv = reinterpret_cast<const float4*>(p)[i];
+        upd(av.x, pv.x); upd(av.y, pv.y); upd(av.z, pv.z); upd(av.w, pv.w);
+        reinterpret_cast<float4*>(avg)[i] = av;
+    }
+    if (blockIdx.x == 0)
+        for (long long i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) upd(avg[i], p[i]);
+}
+
+// exchange of two disjoint ranges as bit patterns (integer moves: NaN payloads, -0.0 and denormals pass through); each element is read
+// and written by the one thread that owns it, so nothing is staged
+__global__ void swap_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long long n4, long long n) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 av = reinterpret_cast<uint4*>(a)[i];
+        const uint4 bv = reinterpret_cast<uint4*>(b)[i];
+        reinterpret_cast<uint4*>(a)[i] = bv;
+        reinterpret_cast<uint4*>(b)[i] = av;
+    }
+    if (blockIdx.x == 0)
+        for (long long i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
+            const unsigned av = a[i], bv = b[i];
+            a[i] = bv;
+            b[i] = av;
+        }
 }
 
 // ---- segmented forms ---------------------------------------------------------------------------------------------------
@@ -491,6 +535,27 @@ extern "C" int vbg_adamw_step(float* p, const float* g, float* m, float* v, long
     const BiasCorr bc = bias_corr(b1, b2, step);
     VBG_LAUNCH(adamw_kernel, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, lr, b1, b2,
                        eps, wd, bc.bc1, bc.bc2_sqrt, grad_scale);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_lerp(float* avg, const float* p, long long n, float weight, void* stream) {
+    VBG_CHECK_ARG(n >= 0);
+    if (n == 0) return VBG_OK;
+    VBG_CHECK_ARG(avg && p);
+    const long long n4 = (ALIGNED16(avg) && ALIGNED16(p)) ? n / 4 : 0;
+    VBG_LAUNCH(lerp_kernel, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, avg, p, n4, n, weight);
+    VBG_LAUNCH_RET();
+}
+
+extern "C" int vbg_swap(float* a, float* b, long long n, void* stream) {
+    VBG_CHECK_ARG(n >= 0);
+    if (n == 0) return VBG_OK;
+    VBG_CHECK_ARG(a && b);
+    const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b, hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+    VBG_CHECK_ARG(hi - lo >= (uintptr_t)n * sizeof(float));          // the same or overlapping ranges: no thread would own its element
+    const long long n4 = (ALIGNED16(a) && ALIGNED16(b)) ? n / 4 : 0;
+    VBG_LAUNCH(swap_kernel, dim3(ew_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<unsigned*>(a),
+               reinterpret_cast<unsigned*>(b), n4, n);
     VBG_LAUNCH_RET();
 }
 

@@ -297,6 +297,8 @@ SIGNATURES = {
     "vbg_seq_metrics": (c_int, [c_vp, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, TagTable, c_vp, c_vp]),
     "vbg_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_int, c_f, c_vp]),
     "vbg_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_ll, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_vp]),
+    "vbg_lerp": (c_int, [c_vp, c_vp, c_ll, c_f, c_vp]),
+    "vbg_swap": (c_int, [c_vp, c_vp, c_ll, c_vp]),
     "vbg_sgd_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroup), c_int, c_int, c_f, c_vp]),
     "vbg_adamw_step_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(AdamwGroup), c_int, c_int, c_f, c_vp]),
     "vbg_sgd_step_seg_opt": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, C.POINTER(SgdGroupOpt), c_int, c_f, c_vp]),

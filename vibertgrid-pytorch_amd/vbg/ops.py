@@ -2974,6 +2974,25 @@ def adamw_step(p, g, m, v, lr, b1, b2, eps, wd, step, grad_scale=1.0):
     check(lib.vbg_adamw_step(P(p), P(g), P(m), P(v), p.numel(), lr, b1, b2, eps, wd, step, grad_scale, _stream()), "vbg_adamw_step")
 
 
+def _flat_pair(a, b):
+    _chk_f32(a, b)
+    assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() and a.device == b.device, "two contiguous fp32 ranges of one length"
+
+
+def lerp_(avg, p, weight):
+    """avg <- lerp(avg, p, weight) in place, torch.lerp's bits (vbg_lerp); one launch on the current stream, no sync"""
+    _flat_pair(avg, p)
+    check(lib.vbg_lerp(P(avg), P(p), avg.numel(), float(weight), _stream()), "vbg_lerp")
+    return avg
+
+
+def swap_(a, b):
+    """exchange the contents of two disjoint ranges in place, bit for bit (vbg_swap); one launch on the current stream, no sync.  The
+    caller tells the weight caches (bump_weight_epoch / FlatGroup.invalidate) when one of them holds parameters"""
+    _flat_pair(a, b)
+    check(lib.vbg_swap(P(a), P(b), a.numel(), _stream()), "vbg_swap")
+
+
 class ChunkTable:
     """the work list of a segmented optimizer step: rows (start, length, group) in device memory (include/vbg.h vbg_optim_chunk), with
     what the launch has to hold the buffers against -- `numel` (no chunk reaches past it) and `ngroups` (every row's group is below it)"""

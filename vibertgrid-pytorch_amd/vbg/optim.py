@@ -11,6 +11,8 @@ pipeline/train_val_utils.py:272-284, designed for MI355X instead of translated:
   and LayerNorm weights, layer-wise learning rates) it is still ONE launch: `vbg_sgd_step_seg` / `vbg_adamw_step_seg` walk a chunk
   table over the same buffers and take every group's hyper-parameters by value; `fuse(optimizer)` gives the same single launch to an
   unchanged torch.optim.SGD / Adam / AdamW object, with torch's semantics kept whole (`vbg_sgd_step_seg_opt` / `vbg_adam_step_seg_opt`);
+* an EMA / SWA of the parameters is one more flat buffer per group: `WeightAverage.update()` is one `vbg_lerp` launch per buffer,
+  validation on the averaged weights an in-place exchange (`vbg_swap`) plus one cache invalidation -- no second model;
 * data parallel: the flat gradient buffer is cut into large contiguous buckets; a bucket is all-reduced
   (RCCL over xGMI, async, its own stream) as soon as autograd has accumulated its last gradient, so the
   exchange overlaps the rest of backward; no bucket copies (gradients ARE the bucket); the 1/world
@@ -24,6 +26,7 @@ pipeline/train_val_utils.py:272-284, designed for MI355X instead of translated:
   (`bert_model.pooler.*`, `backbone.resnet.fc.*`) are kept out of the buffers, which is what
   `find_unused_parameters=True` + "skip params with grad None" amounts to in the reference.
 """
+import contextlib
 import os
 import time
 from typing import Dict, List, Sequence, Tuple
@@ -1327,6 +1330,259 @@ def fuse_scaler(scaler):
     scaler.__class__ = _SCALERS[cls]
     scaler._vbg_fused = _ScalerState()
     return scaler
+
+
+# ---- weight averaging over the flat storage ------------------------------------------------------------------------------------
+class WeightAverage:
+    """An exponential moving average (kind="ema") or an equal-weight average (kind="swa") of a model's trainable parameters, kept
+    as ONE more flat buffer per FlatGroup -- what torch.optim.swa_utils.AveragedModel keeps as a deep copy of the whole model:
+
+        avg = vbg.optim.WeightAverage(model, kind="ema", decay=0.999)
+        ...
+        optimizer_cnn.step(); optimizer_bert.step()      # torch.optim, fuse()d, FusedSGD / FusedAdamW, scaler.step(...)
+        avg.update()                                      # one vbg_lerp per flat group; the first one copies
+        ...
+        with avg.applied():                               # averaged weights in the model, the live ones parked in the shadow
+            validate(model, ...)
+        torch.save({"model": avg.averaged_state_dict(), ...}, path)
+
+    Binding happens at the first update() (or load_state_dict()): the groups are those the model's trainable parameters live in
+    (`p._vbg_flat`; the model homes them at its first training forward).  A trainable parameter that has a gradient but no flat home
+    (VBG_HOME=0) raises ValueError -- there is no per-parameter route; parameters kept out of the buffers (`pooler.*`, `resnet.fc.*`,
+    frozen ones) never change, are their own average and are left alone.  A group whose parameters moved away since (Module.to, a
+    fresh `.data`) raises RuntimeError at the next update() / swap().
+
+    Counting is AveragedModel's: `n_averaged` is a host integer, the update at n_averaged == 0 copies the whole buffer, later ones are
+    avg <- lerp(avg, p, w) over [0, total) in torch's bits, with w = 1 - decay (ema; `decay`: a float in [0, 1] or a callable
+    n_averaged -> decay) or w = 1 / (n_averaged + 1) (swa).  Of the update() calls, numbered from 1, call c averages when c > start and
+    (c - start) % every == 0; the others return at once.  A step GradScaler skipped needs nothing special: the average moves toward
+    unchanged weights, as AveragedModel's does.
+
+    buffers="live" (torch's use_buffers=False): only parameters are averaged; BatchNorm statistics stay the live model's.
+    buffers="average": the model's floating-point buffers are averaged too (torch._foreach_lerp_ over private clones -- plumbing) and
+    exchanged along with the parameters; integer buffers stay live.
+
+    swap() exchanges live and averaged weights in place (vbg_swap, no second model) and invalidates every cached weight image;
+    applied() is the context manager around two of them.  While applied, update() and a nested applied() raise RuntimeError;
+    stepping an optimizer while applied is an error this class does not detect (the step would train the average).
+    Data parallel: after the all-reduce every rank steps identical gradients, so every rank's average is identical; no collective is
+    added."""
+
+    def __init__(self, model: torch.nn.Module, kind: str = "ema", decay=0.999, every: int = 1, start: int = 0, buffers: str = "live"):
+        if kind not in ("ema", "swa"):
+            raise ValueError(f"kind={kind!r}: 'ema' or 'swa'")
+        if buffers not in ("live", "average"):
+            raise ValueError(f"buffers={buffers!r}: 'live' or 'average'")
+        if kind == "ema" and not callable(decay) and not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"decay={decay!r}: a float in [0, 1] or a callable n_averaged -> decay")
+        if int(every) < 1 or int(start) < 0:
+            raise ValueError("every >= 1 and start >= 0")
+        self.model, self.kind, self.buffers = model, kind, buffers
+        self.decay = decay if callable(decay) else float(decay)
+        self.every, self.start = int(every), int(start)
+        self.n_averaged, self.calls = 0, 0
+        self.is_applied = False
+        self.groups: List[FlatGroup] = None
+        self.shadows: List[torch.Tensor] = None
+        self._buf_names, self._buf_avg = [], []
+
+    # ---- binding --------------------------------------------------------------------------------------------------------------
+    def _bind(self):
+        if self.groups is not None:
+            return
+        groups = []
+        for name, p in self.model.named_parameters():
+            if not p.requires_grad:
+                continue
+            g = getattr(p, "_vbg_flat", (None,))[0]
+            if g is None:
+                if p.grad is not None:
+                    raise ValueError(f"WeightAverage: parameter {name} is trained but does not live in flat storage (VBG_HOME=0, or no training "
+                                     "forward on the device yet); there is no per-parameter route here -- use "
+                                     "torch.optim.swa_utils.AveragedModel for such a model")
+                continue
+            if all(g is not h for h in groups):
+                groups.append(g)
+        if not groups:
+            raise ValueError("WeightAverage: no parameter of the model lives in flat storage yet (the model homes its parameters at its "
+                             "first training forward on the device); without flat storage use torch.optim.swa_utils.AveragedModel")
+        self.groups = groups
+        self._check_valid()
+        self.shadows = [torch.empty_like(g.pflat) for g in groups]
+        if self.buffers == "average":
+            named = [(n, b) for n, b in self.model.named_buffers() if b.is_floating_point()]
+            self._buf_names = [n for n, _ in named]
+            self._buf_avg = [b.detach().clone() for _, b in named]
+
+    def _check_valid(self):
+        for g in self.groups:
+            if not g.valid():
+                raise RuntimeError("WeightAverage: the parameters moved away from the flat buffer this average is bound to (Module.to / a "
+                                   "fresh .data); build a new WeightAverage after moving the model")
+
+    def _live_buffers(self):
+        have = dict(self.model.named_buffers())
+        return [have[n] for n in self._buf_names]
+
+    def _names(self):
+        """id(parameter) -> the model's name for it"""
+        return {id(p): n for n, p in self.model.named_parameters()}
+
+    # ---- the average ----------------------------------------------------------------------------------------------------------
+    def weight(self) -> float:
+        """the lerp weight of the next averaging update (n_averaged >= 1), in Python double as torch forms it"""
+        if self.kind == "swa":
+            return 1.0 / (self.n_averaged + 1)
+        d = self.decay(self.n_averaged) if callable(self.decay) else self.decay
+        return 1.0 - float(d)
+
+    @torch.no_grad()
+    def update(self):
+        if self.is_applied:
+            raise RuntimeError("WeightAverage.update() while the averaged weights are applied: the model holds the average, not the live weights")
+        self.calls += 1
+        if self.calls <= self.start or (self.calls - self.start) % self.every:
+            return
+        self._bind()
+        self._check_valid()
+        if self.n_averaged == 0:
+            # (a plain copy, as AveragedModel's first update: a lerp with weight 1 is not exact)
+            for g, s in zip(self.groups, self.shadows):
+                s.copy_(g.pflat)
+            if self._buf_avg:
+                torch._foreach_copy_(self._buf_avg, self._live_buffers())
+        else:
+            w = self.weight()
+            for g, s in zip(self.groups, self.shadows):
+                ops.lerp_(s, g.pflat, w)          # padding included: both sides hold the same zeros there
+            if self._buf_avg:
+                torch._foreach_lerp_(self._buf_avg, self._live_buffers(), w)
+        self.n_averaged += 1
+
+    def _invalidate(self):
+        for g in self.groups:
+            g.invalidate()
+        ops.bump_weight_epoch()
+
+    def _need_average(self, what):
+        if self.groups is None or self.n_averaged == 0:
+            raise RuntimeError(f"WeightAverage.{what}: nothing has been averaged yet (no update() past `start`)")
+        self._check_valid()
+
+    @torch.no_grad()
+    def swap(self):
+        """exchange the live and the averaged weights in place, and tell every cache of a weight image; toggles `is_applied`"""
+        self._need_average("swap()")
+        for g, s in zip(self.groups, self.shadows):
+            ops.swap_(g.pflat, s)
+        if self._buf_avg:
+            live = self._live_buffers()
+            tmp = [b.detach().clone() for b in live]
+            torch._foreach_copy_(live, self._buf_avg)
+            torch._foreach_copy_(self._buf_avg, tmp)
+        self._invalidate()
+        self.is_applied = not self.is_applied
+
+    @contextlib.contextmanager
+    def applied(self):
+        """with avg.applied(): the model computes with the averaged weights; the live ones come back on exit, also on an exception"""
+        if self.is_applied:
+            raise RuntimeError("WeightAverage.applied(): the averaged weights are applied already")
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    @torch.no_grad()
+    def copy_to(self):
+        """the averaged weights become the live weights (a copy; the average stays what it is)"""
+        if self.is_applied:
+            raise RuntimeError("WeightAverage.copy_to() while the averaged weights are applied")
+        self._need_average("copy_to()")
+        for g, s in zip(self.groups, self.shadows):
+            g.pflat.copy_(s)
+        if self._buf_avg:
+            torch._foreach_copy_(self._live_buffers(), self._buf_avg)
+        self._invalidate()
+
+    # ---- checkpoints ----------------------------------------------------------------------------------------------------------
+    def _avg_flats(self):
+        """the flat buffers that hold the average right now (while applied: the model's own)"""
+        return [g.pflat for g in self.groups] if self.is_applied else self.shadows
+
+    def _avg_buffers(self):
+        return self._live_buffers() if self.is_applied else self._buf_avg
+
+    @torch.no_grad()
+    def averaged_state_dict(self):
+        """model.state_dict() with the averaged weights: same keys and layouts (channels_last kept, doubly registered tensors under both
+        keys); every tensor that is a view of a flat group is replaced by a clone of the same view of the average, averaged buffers
+        (buffers="average") by clones of theirs, everything else is the model's.  Nothing is swapped, the model is not disturbed."""
+        self._need_average("averaged_state_dict()")
+        where = {}
+        for g, flat in zip(self.groups, self._avg_flats()):
+            for i, a in enumerate(g._ptrs):
+                where[a] = (g, flat, i)
+        bufs = dict(zip(self._buf_names, self._avg_buffers()))
+        sd = self.model.state_dict()
+        out = sd.copy()                                    # (keys in the model's order; `_metadata` carried over below)
+        if hasattr(sd, "_metadata"):
+            out._metadata = sd._metadata
+        done = {}
+        for k, t in sd.items():
+            hit = where.get(t.data_ptr()) if isinstance(t, torch.Tensor) and t.is_floating_point() else None
+            if hit is not None and hit[0].params[hit[2]].numel() == t.numel():
+                key = (id(hit[0]), hit[2])
+                if key not in done:
+                    done[key] = hit[0].view(hit[1], hit[2]).clone()
+                out[k] = done[key]
+            elif k in bufs:
+                out[k] = bufs[k].clone()
+        return out
+
+    @torch.no_grad()
+    def state_dict(self):
+        """counters, settings and the average as per-parameter tensors keyed by parameter name (no dependence on the flat layout)"""
+        sd = {"n_averaged": self.n_averaged, "calls": self.calls, "kind": self.kind, "every": self.every, "start": self.start,
+              "buffers": self.buffers, "shadow": {}, "shadow_buffers": {}}
+        if not callable(self.decay):
+            sd["decay"] = self.decay
+        if self.groups is not None and self.n_averaged > 0:
+            names = self._names()
+            for g, flat in zip(self.groups, self._avg_flats()):
+                for i, p in enumerate(g.params):
+                    sd["shadow"][names[id(p)]] = g.view(flat, i).clone()
+            sd["shadow_buffers"] = {n: b.clone() for n, b in zip(self._buf_names, self._avg_buffers())}
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if self.is_applied:
+            raise RuntimeError("WeightAverage.load_state_dict() while the averaged weights are applied")
+        if sd["kind"] != self.kind or sd.get("buffers", "live") != self.buffers:
+            raise ValueError(f"checkpoint of a kind={sd['kind']!r}, buffers={sd.get('buffers', 'live')!r} average; this one is "
+                             f"kind={self.kind!r}, buffers={self.buffers!r}")
+        self._bind()
+        self._check_valid()
+        if int(sd["n_averaged"]) > 0:
+            names = self._names()
+            want = {names[id(p)] for g in self.groups for p in g.params}
+            if set(sd["shadow"]) != want:
+                odd = sorted(set(sd["shadow"]) ^ want)
+                raise ValueError(f"checkpoint and model disagree on the averaged parameters: {odd[:4]}{'...' if len(odd) > 4 else ''}")
+            if set(sd["shadow_buffers"]) != set(self._buf_names):
+                raise ValueError("checkpoint and model disagree on the averaged buffers")
+            for g, s in zip(self.groups, self.shadows):
+                s.zero_()                                  # (the padding between slots, as in the parameter buffer)
+                for i, p in enumerate(g.params):
+                    g.view(s, i).copy_(sd["shadow"][names[id(p)]])
+            for n, b in zip(self._buf_names, self._buf_avg):
+                b.copy_(sd["shadow_buffers"][n])
+        self.n_averaged, self.calls = int(sd["n_averaged"]), int(sd["calls"])
+        self.every, self.start = int(sd["every"]), int(sd["start"])
+        if "decay" in sd and not callable(self.decay):
+            self.decay = float(sd["decay"])
 
 
 class FlatReducer:

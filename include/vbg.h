@@ -1062,6 +1062,46 @@ int vbg_clip_coef_gate(const float* partials, int n, int kind, float max_norm, f
 /* out[0] += sum(g^2) */
 int vbg_sumsq(const float* g, long long n, float* out_accum, void* stream);
 int vbg_scale_inplace(float* x, long long n, float s, void* stream);
+/* Per-parameter statistics of a flat fp32 buffer (vbg.stats.ParamStats; csrc/stats.hip): one row pass per buffer and one finish,
+ * no atomics on device memory, plain stores in a fixed order -- the same bits on every call, the same code in deterministic mode.
+ * vbg_param_stats_rows: `rows` is a device table of vbg_optim_chunk whose `group` is the PARAMETER index.  Where the contract differs
+ *   from the optimizer tables: start is a multiple of 4 elements, length is any value in [1, 2^31 - 4] and covers the parameter's own elements
+ *   only (never its slot padding), rows of one parameter are consecutive and in address order.  The last float4 of a row is read whole
+ *   (slots are padded to 8 elements, so the read is legal); lanes at or beyond `length` enter no statistic, whatever they hold.
+ *   scale_or_null: GradScaler's device scale; inv = (float)(1.0 / (double)*scale), and every element is classified and summed as the
+ *   one rounded fp32 product x * inv.  NULL: the element itself.  x is only ever read.  recs[c] (c in [0, nrows)) is one record:
+ *     sumsq      sum of (double)v * (double)v over the FINITE elements (each product is exact in double)
+ *     amax_bits  the largest bit pattern of |v| among finite elements, 0 if none
+ *     nonfinite  count of inf and NaN;  zeros: count of +0 / -0
+ *     over_f16   finite elements with |v| >= 65520.0f (what an fp16 piece turns into inf)
+ *     hist       binades of the finite non-zero elements: e = unbiased fp32 exponent (fp32 subnormals: -127),
+ *                bin = clamp(e + 46, 0, 63) -- bin k in 1..62: 2^(k-46) <= |v| < 2^(k-45); bin 0: below 2^-45; bin 63: from 2^17 up.
+ *                |v| < 2^-14 (fp16 subnormal range) is bins 0..31, |v| < 2^-25 (rounds to zero in fp16) is bins 0..20.
+ *   nrows == 0 is a no-op that looks at no pointer.
+ * vbg_param_stats_finish: row_ptr is int[nparams + 1] in device memory, a CSR over the rows.  One block per parameter sums that
+ *   parameter's records in a fixed order (a lane-strided walk, then a fixed tree), writes last[p] (this update) and, unless total is
+ *   NULL, folds it into total[p]: counts and bins add (int64), amax_bits takes the max, sumsq is the last value, updates += 1,
+ *   steps_nonfinite += (nonfinite > 0).  nparams == 0 is a no-op that looks at no pointer.
+ * Argument errors (-1, before any launch): a negative count, a NULL required pointer with a positive count, x / rows / recs / last
+ * not 16-byte aligned, total not 8-byte or row_ptr / scale not 4-byte aligned. */
+typedef struct vbg_stats_rec {                                    /* 288 bytes, 16-byte aligned in device memory */
+    double sumsq;
+    unsigned int amax_bits;
+    int nonfinite, zeros, over_f16;
+    int hist[64];
+    int pad[2];
+} vbg_stats_rec;
+typedef struct vbg_stats_total {                                  /* 568 bytes, 8-byte aligned */
+    double sumsq;
+    long long nonfinite, zeros, over_f16, updates, steps_nonfinite;
+    unsigned int amax_bits;
+    int pad;
+    long long hist[64];
+} vbg_stats_total;
+int vbg_param_stats_rows(const float* x, const vbg_optim_chunk* rows, int nrows, const float* scale_or_null, vbg_stats_rec* recs,
+                         void* stream);
+int vbg_param_stats_finish(const vbg_stats_rec* recs, const int* row_ptr, int nparams, vbg_stats_rec* last, vbg_stats_total* total,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * a16. deterministic mode (vbg.ops.set_deterministic): fixed-order forms of the float-atomic reductions (DESIGN.md

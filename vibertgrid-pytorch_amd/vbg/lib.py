@@ -142,6 +142,16 @@ class AdamGroupOpt(C.Structure):             # include/vbg.h vbg_adam_group_opt
     _fields_ = [("lr", c_f), ("b1", c_f), ("b2", c_f), ("eps", c_f), ("wd", c_f), ("step", c_int), ("flags", c_int)]
 
 
+class StatsRec(C.Structure):                 # include/vbg.h vbg_stats_rec (one per row, and one per parameter for the last update)
+    _fields_ = [("sumsq", c_d), ("amax_bits", C.c_uint), ("nonfinite", c_int), ("zeros", c_int), ("over_f16", c_int),
+                ("hist", c_int * 64), ("pad", c_int * 2)]
+
+
+class StatsTotal(C.Structure):               # include/vbg.h vbg_stats_total (one per parameter, the running table)
+    _fields_ = [("sumsq", c_d), ("nonfinite", c_ll), ("zeros", c_ll), ("over_f16", c_ll), ("updates", c_ll), ("steps_nonfinite", c_ll),
+                ("amax_bits", C.c_uint), ("pad", c_int), ("hist", c_ll * 64)]
+
+
 class SampleCat(C.Structure):                # include/vbg.h vbg_sample_cat
     _fields_ = [("value", c_int), ("eq", c_int), ("k", c_int), ("take_order", c_int)]
 
@@ -313,6 +323,8 @@ SIGNATURES = {
     "vbg_grad_sumsq_seg_inf": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "vbg_grad_norm_seg": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_d, c_vp]),
     "vbg_clip_coef_gate": (c_int, [c_vp, c_int, c_int, c_f, c_f, c_vp, c_vp, c_int, c_d, c_vp, c_vp]),
+    "vbg_param_stats_rows": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "vbg_param_stats_finish": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "vbg_colsum_det_ws_elems": (c_ll, [c_ll, c_int]),
     "vbg_colsum_det": (c_int, [c_vp, c_ll, c_ll, c_int, c_vp, c_int, c_vp, c_vp]),
     "vbg_sum_det_ws_elems": (c_int, []),

@@ -11,7 +11,7 @@ import torch
 
 from .lib import (ADAM_AMSGRAD, ADAM_COUPLED, ADAM_MAXIMIZE, SGD_FIRST, SGD_MAXIMIZE, SGD_NESTEROV, ATTN_DKV, ATTN_DQ, ATTN_FWD, EPI_GELU_DUAL, EPI_MUL_GELU_GRAD, EPI_NONE, EPI_RELU, OP_CONV_K, OP_CONV_R, OP_DENSE_K, OP_DENSE_R, OP_WT_R, ConvGeo,
                   AdamGroupOpt, AdamwGroup, AttnDesc, OhemCats, SampleCats, SAMPLE_MAX_CATS, SAMPLE_MAX_K, BertLayerBwdDesc, BertLayerFwdDesc, BnEpilogue, GemmDesc, OPTIM_MAX_GROUPS, PlaneGemmDesc, SgdGroup, SgdGroupOpt, TagTable, VbgError, check, lib,
-                  IMAGE_F32_CHW, IMAGE_U8_CHW, IMAGE_U8_HWC, TRANSFORM_MAX_IMAGES, TransformImage)
+                  IMAGE_F32_CHW, IMAGE_U8_CHW, IMAGE_U8_HWC, TRANSFORM_MAX_IMAGES, TransformImage, StatsRec, StatsTotal)
 
 f32 = torch.float32
 i32 = torch.int32
@@ -3249,3 +3249,78 @@ def clip_coef_gate(partials, n, max_norm, norm_scale=1.0, grad_scale=None, kind=
     check(lib.vbg_clip_coef_gate(P(partials), int(n), int(kind), float(max_norm), float(norm_scale), P(grad_scale), P(loss), f64, thr, P(out),
                                  _stream()), "vbg_clip_coef_gate")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Per-parameter statistics of a flat buffer (csrc/stats.hip; vbg.stats.ParamStats)
+# ----------------------------------------------------------------------------------------------
+STATS_REC_BYTES, STATS_TOTAL_BYTES = C.sizeof(StatsRec), C.sizeof(StatsTotal)
+
+
+class StatsTable:
+    """the work list of a statistics pass: rows (start, length, parameter) in device memory (include/vbg.h vbg_optim_chunk), the CSR
+    `row_ptr` over them (int32[nparams + 1], device), and what a launch holds its buffers against: `n` rows, `nparams`, `numel`"""
+
+    def __init__(self, rows, row_ptr, n, nparams, numel):
+        self.rows, self.row_ptr, self.n, self.nparams, self.numel = rows, row_ptr, n, nparams, numel
+
+
+def stats_table(rows, row_ptr, numel, device):
+    """StatsTable of `rows` ([n, 3] integers: start, length, parameter) and `row_ptr` (nparams + 1 integers) for a buffer of `numel`
+    elements.  The kernels trust the table, so it is checked here, once: starts multiples of 4, lengths in [1, 2^31 - 4], the whole float4s
+    a row reads inside the buffer, rows disjoint and in address order, the rows of parameter p exactly [row_ptr[p], row_ptr[p + 1])."""
+    import numpy as np
+    c = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    rp = np.asarray(row_ptr, dtype=np.int64).reshape(-1)
+    if len(rp) < 1 or rp[0] != 0 or rp[-1] != len(c) or (np.diff(rp) < 0).any():
+        raise ValueError("statistics table: row_ptr must rise from 0 to the number of rows")
+    if len(c) >= 1 << 31:
+        raise ValueError("statistics table: too many rows")
+    nparams = len(rp) - 1
+    if len(c):
+        start, length, param = c[:, 0], c[:, 1], c[:, 2]
+        # (the kernel rounds a length up to whole float4s and indexes elements in 32-bit integers)
+        if (start % 4).any() or (start < 0).any() or (length < 1).any() or (length > (1 << 31) - 4).any():
+            raise ValueError("statistics table: row starts must be non-negative multiples of 4 elements, lengths in [1, 2^31 - 4]")
+        if ((start + (length + 3) // 4 * 4) > numel).any():
+            raise ValueError(f"statistics table: a row's last float4 lies outside the buffer ({numel} elements)")
+        if (start[1:] < (start + length)[:-1]).any():
+            raise ValueError("statistics table: rows overlap or are not in address order")
+        if not np.array_equal(param, np.repeat(np.arange(nparams), np.diff(rp))):
+            raise ValueError("statistics table: the rows of parameter p must be exactly rows [row_ptr[p], row_ptr[p + 1])")
+    packed = np.zeros((len(c),), dtype=np.dtype([("start", "<i8"), ("length", "<i4"), ("group", "<i4")]))
+    packed["start"], packed["length"], packed["group"] = c[:, 0], c[:, 1], c[:, 2]
+    drows = torch.from_numpy(packed.view(np.int32).reshape(-1, 4).copy()).to(device)
+    return StatsTable(drows, torch.from_numpy(rp.astype(np.int32)).to(device), len(c), nparams, int(numel))
+
+
+def _stats_bytes(what, t, nbytes, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < nbytes or t.device != device:
+        raise ValueError(f"parameter statistics: {what} must be a contiguous uint8 buffer of at least {nbytes} bytes on the table's device")
+
+
+def param_stats_rows(x, table, recs, scale=None):
+    """vbg_param_stats_rows: one vbg_stats_rec per row of `table` (a StatsTable) over x into `recs` (uint8, table.n * STATS_REC_BYTES);
+    scale: GradScaler's device scale when x holds scaled gradients (every element enters as x * (1 / scale)), or None.  x is only read.
+    One launch on the current stream, no sync"""
+    _table_bufs("parameter statistics", table, x)
+    _stats_bytes("recs", recs, table.n * STATS_REC_BYTES, table.rows.device)
+    _one_f32("parameter statistics", table.rows.device, ("scale",), scale=scale)
+    _device_memory("parameter statistics", x, table.rows, recs, scale)
+    check(lib.vbg_param_stats_rows(P(x), P(table.rows), table.n, P(scale), P(recs), _stream()), "vbg_param_stats_rows")
+    return recs
+
+
+def param_stats_finish(recs, table, last, total=None):
+    """vbg_param_stats_finish: the records of `table`'s rows summed per parameter into last (uint8, table.nparams * STATS_REC_BYTES) and
+    folded into the running table total (uint8, table.nparams * STATS_TOTAL_BYTES; None: no running table).  One launch, no sync"""
+    dev = table.rows.device
+    if table.row_ptr.numel() != table.nparams + 1 or table.row_ptr.dtype != torch.int32 or table.row_ptr.device != dev:
+        raise ValueError("parameter statistics: row_ptr must hold nparams + 1 int32 on the table's device")
+    _stats_bytes("recs", recs, table.n * STATS_REC_BYTES, dev)
+    _stats_bytes("last", last, table.nparams * STATS_REC_BYTES, dev)
+    if total is not None:
+        _stats_bytes("total", total, table.nparams * STATS_TOTAL_BYTES, dev)
+    _device_memory("parameter statistics", recs, table.row_ptr, last, total)
+    check(lib.vbg_param_stats_finish(P(recs), P(table.row_ptr), table.nparams, P(last), P(total), _stream()), "vbg_param_stats_finish")
+    return last
